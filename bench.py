@@ -34,6 +34,8 @@ HBM_PEAK_GBS = 8000.0       # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.m
 HBM_MEASURED_GBS = 6290.0   # same guide: achievable streaming copy rate (report against both)
 WATCHDOG_S = 240            # N>1: the exchange legs (never run on real xGMI here) may take this long before the line is printed without them
 WORKLOADS = ["cage4", "scircuit", "webbase-1M", "mc2depi", "cage15", "webbase-1M-r2", "cage15-r2", "scircuit-r2", "mc2depi-r2"]
+DUMP_ROWPTR_MAX = 1 << 21    # --dump-outputs: at most this many row-pointer values and DUMP_ENTRIES_MAX entries of C (as row, column,
+DUMP_ENTRIES_MAX = 1 << 20   # value) are written, 40 MiB of float64 in all; larger outputs are sampled at seeded positions
 
 
 def kernel_alg_bytes(name, d):
@@ -68,6 +70,25 @@ def kernels_sha():
     return h.hexdigest()[:16]
 
 
+def seeded_positions(n, k, seed):
+    """k sorted positions out of range(n), the same for the same (n, k, seed); all of them when n <= k"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(d, rp, ci, v, row0=0, prefix="", share=1):
+    """C (or this rank's rows of it) as pem_c_export_csr hands it to a caller -> d/<prefix>c_rowptr.npy and the row, column
+    and value of each entry in d/<prefix>c_{row,col,val}.npy.  Whole when small, else at seeded positions; indices as float64
+    (exact), values in C's own type."""
+    os.makedirs(d, exist_ok=True)
+    pr = seeded_positions(len(rp), DUMP_ROWPTR_MAX // share, 1)
+    pe = seeded_positions(len(ci), DUMP_ENTRIES_MAX // share, 2)
+    row = np.searchsorted(rp, pe, side="right") - 1 + row0
+    for name, a in (("c_rowptr", rp[pr]), ("c_row", row), ("c_col", ci[pe]), ("c_val", v[pe])):
+        np.save(os.path.join(d, f"{prefix}{name}.npy"), a if a.dtype.kind == "f" else a.astype(np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -93,8 +114,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-gather", action="store_true", help="N>1: leave the C slices on their ranks")
     ap.add_argument("--no-tune-split", action="store_true", help="N>1, A^2 row blocks: keep the first cut (balanced tile-level products) "
                                                                  "instead of re-cutting it from measured per-rank times")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the C of the last one as DIR/*.npy (a seeded sample when large; N>1: per rank)")
     ap.add_argument("--shared-input", default=None, metavar="DIR", help=argparse.SUPPRESS)   # set by the self-launcher
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -365,6 +391,10 @@ def main(argv=None):
         ctx.set_graph_replay(True)   # the timed passes replay the captured pass as one hipGraph: same kernels, no launch gaps
         step()                       # capture + first replay, outside the timed region
     elapsed = timed(step, args.steps)
+    if args.dump_outputs:
+        rp, ci, v = plan.export_csr()
+        dump_outputs(args.dump_outputs, rp, ci, v, row0=plan.info()["row_begin"], prefix=f"rank{rank}_" if world > 1 else "", share=world)
+        del rp, ci, v
     # the same passes one by one (each ends in the library's own stream synchronisation): min / mean / max
     per_pass = []
     for _ in range(max(args.steps, 1)):

@@ -322,6 +322,8 @@ extern "C" pem_status pem_ctx_create_on_stream(int device, void *stream, pem_ctx
     PEM_HIP(hipMemsetAsync(ctx->d_flags, 0, sizeof(int) * NUM_FLAGS, ctx->stream));
     for (auto &ev : ctx->ev) PEM_HIP(hipEventCreate(&ev));
     for (auto &a : ctx->aux) PEM_HIP(hipStreamCreateWithFlags(&a, hipStreamNonBlocking));
+    const char *hwq_env = getenv("GPU_MAX_HW_QUEUES");   // read by the HIP runtime itself; see step 1's S1Lanes
+    if (hwq_env && atoi(hwq_env) > 0) ctx->hw_queues = atoi(hwq_env);
     const char *graph_env = getenv("PEM_GRAPH");   // default for pem_set_graph_replay (tools, CLI)
     ctx->graph_replay = graph_env && !strcmp(graph_env, "1");
     const char *gd_env = getenv("PEM_DEBUG_GRAPH_DESTROY");   // diagnostic, tools/graph_churn.py: see retire_graph

@@ -78,7 +78,9 @@ extern "C" pem_status pem_mgpu_create(int ndev, const int *devices, pem_mgpu **o
             return fail(PEM_E_HIP);
         }
     }
-    ncclResult_t r = ncclCommInitAll(m->comm.data(), ndev, devices);
+    // one device: no communicator -- there is nothing to exchange (every RCCL call below is behind n > 1), and RCCL's own set-up
+    // has hung a one-device run outright
+    ncclResult_t r = ndev > 1 ? ncclCommInitAll(m->comm.data(), ndev, devices) : ncclSuccess;
     if (r != ncclSuccess) {
         set_error("ncclCommInitAll over %d devices: %s", ndev, ncclGetErrorString(r));
         for (auto &c : m->comm) c = nullptr;

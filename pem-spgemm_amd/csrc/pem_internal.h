@@ -201,6 +201,7 @@ struct pem_ctx {
     // fork/join inside a step: an independent long-tailed kernel runs on an auxiliary stream
     hipStream_t aux[3] = {};           // step 1's row bins and its oversized-row chain: with the main stream, the runtime's four hardware queues
     hipEvent_t ev_fork = nullptr, ev_join[3] = {};
+    int hw_queues = 4;                 // the runtime's hardware queues per device (GPU_MAX_HW_QUEUES; 4 by default)
     pem_timings timings = {};
     bool profiling = false;
     hipError_t launch_err = hipSuccess;   // first kernel launch the runtime refused since the last report (PEM_LAUNCH)

@@ -1815,7 +1815,11 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
                        A->tile_rowptr.as<int>(), p->tr_lo, p->a_lo, p->aseg.as<int2>(), p->live_j.as<int>(), p->live_ab.as<int2>(), bits_tc, local,
                        p->sk0.as<uint64_t>(), p->sv0.as<uint32_t>(), p->prod_a.as<int>(), p->prod_b.as<int>());
         };
-        S1Lanes lanes(ctx, p->opt_s1_serial != 0);
+        // A pass captured into a hipGraph forks onto the auxiliary streams only when the runtime has a hardware queue for each of the
+        // four: hipGraphLaunch of a capture forked onto more streams than queues has ended in a segmentation fault inside the runtime
+        // (five streams on four queues, four on two).  Fewer queues: the bins run one after another on the main stream, as under
+        // PEM_OPT_S1_SERIAL -- same kernels, same results.
+        S1Lanes lanes(ctx, p->opt_s1_serial != 0 || (ctx->capturing && ctx->hw_queues < 4));
         launch_rowsorts(ctx, p, lanes, counts, mt, bits_tc, force64, nsegs);
         if (xl_local) {
             lanes.on(3);
