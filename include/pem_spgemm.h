@@ -145,6 +145,43 @@ typedef struct {
 pem_status pem_tiled_save(pem_ctx *ctx, const pem_tiled *t, const char *path, const pem_cache_key *key);
 pem_status pem_tiled_load(pem_ctx *ctx, const char *path, const pem_cache_key *expect, pem_tiled **out);
 
+/* ---- numeric refresh (new; the reference re-runs its whole loop) ----------------------------
+ * Replaces the values of a tiling in place; its structure, and every plan's steps 1-2 built on it, stay valid.  V holds
+ * exactly nnz values in one of two orders of the TILED matrix (after any transpose at conversion):
+ *   PEM_VALUES_ROW_MAJOR: by (row, col) ascending -- the order of a CSR with sorted columns (scipy canonical form);
+ *   PEM_VALUES_COL_MAJOR: by (col, row) ascending -- for a tiling built with transpose = 1 this is the source matrix's CSR
+ *                         order, i.e. the caller passes the same array to A and to its A^T tiling.
+ * The order is a property of the tiled arrays, not of the input the tiling came from: any tiling works, also one made by
+ * pem_tiled_load.  Values are copied bit for bit (NaN payloads, -0.0, inf and subnormals arrive unchanged).
+ *
+ * The numeric-only product is the existing pem_spgemm_step3: after steps 1 and 2 have run on a plan, set_values on its A
+ * and/or B followed by pem_spgemm_step3 recomputes C from the new values.  pem_spgemm on such a plan does the same (its
+ * repeat pass re-runs steps 1-2 on the unchanged structure).
+ *
+ * Host forms upload the values, refresh them and wait.  `_device` forms take a device array, are ordered on the context's
+ * stream and return without waiting or reading anything back; a kernel failure surfaces at pem_ctx_synchronize, as for
+ * pem_c_export_csr_device.  PEM_E_INVALID for a null context or tiling, a null V with nnz > 0, an order that is not 0 or 1,
+ * or a value type that does not match the tiling (the rule of the export entry points).  A tiling with nnz = 0: no-op, PEM_OK.
+ *
+ * The first refresh in an order builds that order's map (int32 per entry, the position of every entry's value in V) and, on
+ * the tiling's first refresh, the map of its vals_t slots: 4 bytes per entry each, carved from the context's arena and kept
+ * with the tiling.  Later refreshes are one kernel that gathers V into vals and vals_t.
+ *
+ * Staleness.  Every tiling carries a value version, bumped by each refresh; a plan records its A's and B's versions when
+ * pem_spgemm or pem_spgemm_step3 completes.  While either operand has been refreshed since, the pem_c_export_* entry points
+ * and pem_cplan_get_array(PEM_C_VALS) return PEM_E_STATE; the symbolic arrays (pairs, masks, offsets) stay readable.
+ * pem_spgemm_step3 (or pem_spgemm) makes C current again.
+ *
+ * Graph replay (pem_set_graph_replay).  vals and vals_t are rewritten in place, never reallocated, so a graph pem_spgemm
+ * captured earlier stays valid and reads the new values on its next replay.  Buffers a refresh allocates the first time (the
+ * maps; the host forms' staging buffer when it has to grow) come from the arena, and the arena generation that bumps makes
+ * such a graph re-capture once. */
+typedef enum { PEM_VALUES_ROW_MAJOR = 0, PEM_VALUES_COL_MAJOR = 1 } pem_values_order;
+pem_status pem_tiled_set_values(pem_ctx *ctx, pem_tiled *t, const double *V, int order);
+pem_status pem_tiled_set_values_device(pem_ctx *ctx, pem_tiled *t, const double *dV, int order);
+pem_status pem_tiled_set_values_f32(pem_ctx *ctx, pem_tiled *t, const float *V, int order);
+pem_status pem_tiled_set_values_device_f32(pem_ctx *ctx, pem_tiled *t, const float *dV, int order);
+
 /* ---- a8: flop count (spgemm.cu:1068-1079), computed on the device ------------------------ */
 pem_status pem_flop_count(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, uint64_t *flop);
 

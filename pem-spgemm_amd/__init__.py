@@ -38,8 +38,12 @@ ABI_SYMBOLS = [
     "pem_tiled_from_coo_f32", "pem_tiled_from_coo_device_f32", "pem_tiled_from_csr_f32", "pem_c_export_csr_f32",
     "pem_c_export_csr_device_f32", "pem_c_export_coo_f32", "pem_set_graph_replay",
     "pem_ctx_reserve", "pem_ctx_trim", "pem_ctx_memory_stats", "pem_cplan_set_option", "pem_cplan_get_option", "pem_debug_scan_i32",
-    "pem_debug_refused_launch",
+    "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
+    "pem_tiled_set_values_device_f32",
 ]
+
+# enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
+VALUE_ORDERS = dict(row=0, col=1)
 
 # enum pem_option (include/pem_spgemm.h): kernel variants / test hooks of a plan
 OPTIONS = dict(prune=0, step1_global_sort=1, wide=2, warm=3, s3_band=4, s1_force_key64=5, s1_xlcap=6, export_rows=7, s1_serial=8, s3_decode=9, s1_xl_global=10, s3_epw=11, s3_idx64=12, s3_mark=13, s3_xcd=14, s1_segments=15, s2_transposed=16)
@@ -240,6 +244,33 @@ class Tiled:
         _check(fn(ctx._h, int(rows), int(cols), _p(rowptr, C.c_int32), _p(colidx, C.c_int32), _p(V, C.c_float if f32 else C.c_double),
                   C.byref(h)))
         return cls(ctx, h)
+
+    def _order(self, order):
+        if order not in VALUE_ORDERS:
+            raise ValueError(f"order must be one of {sorted(VALUE_ORDERS)}, not {order!r}")
+        return VALUE_ORDERS[order]
+
+    def set_values(self, V, order="row"):
+        """Numeric refresh: replace the values in place, structure kept (every plan's steps 1-2 stay valid; step 3 recomputes C).
+        V: nnz values ordered by (row, col) of the tiled matrix ("row", sorted CSR order) or by (col, row) ("col": for a tiling
+        built with transpose=True, the source's CSR order).  Cast to the tiling's dtype as from_coo does; waits."""
+        f32 = self.value_bytes == 4
+        V = np.ascontiguousarray(V, dtype=self.dtype)
+        if V.shape != (self.nnz,):
+            raise ValueError(f"set_values: {V.shape} values for a tiling of {self.nnz} entries")
+        fn = lib().pem_tiled_set_values_f32 if f32 else lib().pem_tiled_set_values
+        _check(fn(self.ctx._h, self._h, _p(V, C.c_float if f32 else C.c_double), self._order(order)))
+
+    def set_values_device(self, dV, order="row"):
+        """set_values from device memory, ordered on the context's stream; returns without waiting (errors surface at
+        Context.synchronize()).  dV: a device pointer (int) to nnz values of the tiling's dtype, or a torch tensor of them."""
+        if hasattr(dV, "data_ptr"):
+            if not dV.is_cuda or dV.numel() != self.nnz or not dV.is_contiguous() or str(dV.dtype) != f"torch.{self.dtype.name}":
+                raise ValueError(f"set_values_device: want a contiguous device tensor of {self.nnz} {self.dtype.name} values, "
+                                 f"got {dV.dtype} x {dV.numel()} on {dV.device}")
+            dV = dV.data_ptr()
+        fn = lib().pem_tiled_set_values_device_f32 if self.value_bytes == 4 else lib().pem_tiled_set_values_device
+        _check(fn(self.ctx._h, self._h, C.c_void_p(int(dV)), self._order(order)))
 
     def save(self, path, key=None):
         """Write the sorted tile payload to a cache file."""

@@ -295,6 +295,7 @@ static pem_status export_csr_device_impl(pem_ctx *ctx, const pem_cplan *p, int32
         set_error("pem_c_export_csr: step 3 has not run");
         return PEM_E_STATE;
     }
+    PEM_TRY(c_values_current(p, "pem_c_export_csr"));
     if (!export_type_ok(p, (int)sizeof(VT), "pem_c_export_csr")) return PEM_E_INVALID;
     if (p->nnz_c > 0 && (!d_colidx || !d_vals)) return PEM_E_INVALID;
     PEM_ENTER(ctx);
@@ -358,6 +359,7 @@ static pem_status export_csr_impl(pem_ctx *ctx, const pem_cplan *p, int64_t *nnz
     }
     if (nnz) *nnz = p->nnz_c;
     if (!rowptr) return PEM_OK;   // size query
+    PEM_TRY(c_values_current(p, "pem_c_export_csr"));
     if (!export_type_ok(p, (int)sizeof(VT), "pem_c_export_csr")) return PEM_E_INVALID;
     PEM_ENTER(ctx);
     const int r0 = p->tr_lo * 16, r1 = p->tr_hi * 16 < p->A->rows ? p->tr_hi * 16 : p->A->rows;
@@ -391,6 +393,7 @@ static pem_status export_coo_impl(pem_ctx *ctx, const pem_cplan *p, int64_t *nnz
     }
     if (nnz) *nnz = p->nnz_c;
     if (!rows) return PEM_OK;
+    PEM_TRY(c_values_current(p, "pem_c_export_coo"));
     const int r0 = p->tr_lo * 16, r1 = p->tr_hi * 16 < p->A->rows ? p->tr_hi * 16 : p->A->rows;
     std::vector<int> rp((size_t)(r1 - r0) + 1);
     PEM_TRY(export_csr_impl<VT>(ctx, p, nullptr, rp.data(), cols, vals));

@@ -304,6 +304,11 @@ struct pem_tiled {
     pem::DevBuf tile_colocc;          // derived: int2[T] = (tile_colidx, tile_occ): step 1's expansion reads both of every B tile
     pem::DevBuf tile_occ;             // derived: uint32[T] = occupied columns (low 16 bits) | occupied rows << 16 (step-1 pruning)
     std::vector<int> h_tile_rowptr;   // host copy (tile_rows+1 ints) for plan creation / splits
+    // numeric refresh (values.hip): maps built on the first pem_tiled_set_values* that needs them, then kept
+    pem::DevBuf vmap[2];              // int32[nnz] per pem_values_order: for every entry in tile order, where its value sits in V
+    pem::DevBuf vmap_t;               // int32[nnz]: for every entry in tile order, its slot in vals_t
+    bool vmap_ready[2] = {false, false}, vmap_t_ready = false;
+    uint64_t value_version = 0;       // bumped by every refresh; a plan's C is current while it equals what step 3 read
 };
 
 struct pem_cplan {
@@ -360,7 +365,8 @@ struct pem_cplan {
     bool wide = true;                  // step 2 ran the fused kernel (step 3 then runs entry-per-lane); false: 16-lanes-per-tile baseline
     bool compact_valid = false;        // c_tile_colidx / pairs_offset hold the dense layout (else: row-local scratch, see ensure_compact)
     pem::DevBuf group_nnz;             // C entries per S2_GROUP tiles (s2_tiles_kernel -> scan -> s2_entries_kernel)
-    // sizes of the last complete pass on this plan.  A and B are immutable, so a repeat pass has the same
+    uint64_t a_version = 0, b_version = 0;   // A's / B's value_version when step 3 last completed (c_values_current)
+    // sizes of the last complete pass on this plan.  The structure of A and B is immutable, so a repeat pass has the same
     // sizes: it skips the three host read-backs and a device-side check compares them at the end instead.
     pem_ctx *owner = nullptr;              // the context the plan was created on
     hipGraphExec_t graph_exec = nullptr;   // PEM_GRAPH=1: the captured warm pass

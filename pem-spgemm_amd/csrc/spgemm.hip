@@ -269,6 +269,7 @@ extern "C" pem_status pem_spgemm_step3(pem_ctx *ctx, pem_cplan *plan)
     PEM_TRY(step3_impl(ctx, plan));
     PEM_HIP(hipStreamSynchronize(ctx->stream));
     PEM_TRY(launch_status(ctx));
+    note_c_values(plan);
     return step_elapsed(ctx, 4, 5, &ctx->timings.step3_ms);
 }
 
@@ -342,7 +343,7 @@ extern "C" pem_status pem_spgemm(pem_ctx *ctx, pem_cplan *plan)
                 PEM_TRY(read_flags(ctx, hf));
             }
             PEM_TRY(check_internal(hf));
-            if (hf[FLAG_CAPACITY]) {   // sizes differ from the captured ones (cannot happen while A and B are immutable)
+            if (hf[FLAG_CAPACITY]) {   // sizes differ from the captured ones (cannot happen while the structure of A and B is immutable)
                 retire_graph(ctx, plan);
                 plan->warm = false;
             } else {
@@ -365,7 +366,7 @@ extern "C" pem_status pem_spgemm(pem_ctx *ctx, pem_cplan *plan)
                 PEM_TRY(read_flags(ctx, hf));
             }
             PEM_TRY(check_internal(hf));
-            if (hf[FLAG_CAPACITY]) {        // cannot happen while A and B are immutable; recover by a full pass
+            if (hf[FLAG_CAPACITY]) {        // cannot happen while the structure of A and B is immutable; recover by a full pass
                 plan->warm = false;
                 PEM_TRY(step1_impl(ctx, plan, false));
                 PEM_TRY(step2_impl(ctx, plan));
@@ -375,6 +376,7 @@ extern "C" pem_status pem_spgemm(pem_ctx *ctx, pem_cplan *plan)
     }
     PEM_HIP(hipStreamSynchronize(ctx->stream));
     PEM_TRY(launch_status(ctx));
+    note_c_values(plan);
     plan->warm = plan->pairs_ready && plan->state == 3;
     ctx->timings.spgemm_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     if (graphed) {   // a replayed graph carries no per-step events (recorded inside a capture they do not time the replay)
@@ -427,7 +429,12 @@ extern "C" pem_status pem_cplan_get_array(pem_ctx *ctx, const pem_cplan *p, pem_
         want = NZ;
         need = 2;
         break;
-    case PEM_C_VALS: src = p->c_vals.p; want = (size_t)p->A->value_bytes * NZ; need = 3; break;   // native type
+    case PEM_C_VALS:
+        if (p->state >= 3) PEM_TRY(c_values_current(p, "pem_cplan_get_array(PEM_C_VALS)"));
+        src = p->c_vals.p;
+        want = (size_t)p->A->value_bytes * NZ;   // native type
+        need = 3;
+        break;
     default: set_error("unknown pem_cplan_array %d", (int)which); return PEM_E_INVALID;
     }
     if (p->state < need) {

@@ -50,4 +50,19 @@ pem_status ensure_c_rowidx(pem_ctx *ctx, const pem_cplan *p);       // _C_tileRo
 pem_status ensure_c_rowptr(pem_ctx *ctx, const pem_cplan *p);       // Ctiles_rowPtr
 pem_status ensure_c_rowcolidx(pem_ctx *ctx, const pem_cplan *cp);   // Ctiles_rowColIdx
 
+// C's values were computed from the operands' current values: PEM_E_STATE after a numeric refresh (pem_tiled_set_values*) of
+// A or B that no step 3 has followed yet
+inline pem_status c_values_current(const pem_cplan *p, const char *fn)
+{
+    if (p->a_version == p->A->value_version && p->b_version == p->B->value_version) return PEM_OK;
+    set_error("%s: the values of %s were refreshed (pem_tiled_set_values) after C was computed; run pem_spgemm_step3 or pem_spgemm first", fn,
+              p->a_version != p->A->value_version ? "A" : "B");
+    return PEM_E_STATE;
+}
+inline void note_c_values(pem_cplan *p)   // step 3 has just completed
+{
+    p->a_version = p->A->value_version;
+    p->b_version = p->B->value_version;
+}
+
 }  // namespace pem
