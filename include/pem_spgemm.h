@@ -192,6 +192,19 @@ pem_status pem_cplan_create(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B
                             int32_t tile_row_begin, int32_t tile_row_end, pem_cplan **out);
 pem_status pem_cplan_destroy(pem_ctx *ctx, pem_cplan *plan);
 
+/* Masked product C<M> = A*B (the GraphBLAS mxm with a structural mask): only the entries of A*B at the stored positions of M
+ * (explicit zeros included; M's values are never read) -- or, with PEM_MASK_COMPLEMENT, only those where M stores nothing.
+ * M is any tiling of the shape of C, A.rows x B.cols, fp32 or fp64 whatever the type of A and B; it may be A or B itself, and
+ * it must outlive the plan.  The pattern of C is that of the unmasked plan (the symbolic product, entries that cancel
+ * numerically included) intersected with M's (or with its complement); every kept value equals the unmasked product's at the
+ * same position bit for bit.  pem_cplan_get_info and every pem_cplan_array describe C<M> (npairs_all stays the unmasked P; C
+ * tiles the mask empties may remain in the tile list).  A tile-row range uses M's tile rows of the same (global) indices.
+ * Masked plans always run the row-local step 1 and the fused step 2: setting PEM_OPT_STEP1_GLOBAL_SORT = 1 or PEM_OPT_WIDE = 0
+ * on one returns PEM_E_INVALID.  M null, other flags or another shape: PEM_E_INVALID. */
+typedef enum { PEM_MASK_STRUCTURE = 0, PEM_MASK_COMPLEMENT = 1 } pem_mask_flags;
+pem_status pem_cplan_create_masked(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const pem_tiled *M, int mask_flags,
+                                   int32_t tile_row_begin, int32_t tile_row_end, pem_cplan **out);
+
 /* Plan options.  A new plan takes its defaults from the environment once, in pem_cplan_create (PEM_PRUNE=0, PEM_STEP1=esc,
  * PEM_WIDE=0, PEM_NO_WARM=1, PEM_S3_BAND=0, PEM_EXPORT=rows); after that only pem_cplan_set_option changes them -- no entry
  * point reads the environment at call time.  Changing an option sends the plan back to the last step the option does not touch

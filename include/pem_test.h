@@ -32,6 +32,10 @@ extern "C" {
                                                    transposed masks (one trip per inner index occupied on both sides), 2 (default): 1 on repeat
                                                    passes of plans with two or more pairs per C tile (cage15-class), else 0            */
 
+/* a further value of pem_cplan_array: int32[T_C] of a masked plan (pem_cplan_create_masked), for every C tile M's tile id at its
+ * (tile row, tile column), -1 where M has none (complement masks only); readable after step 1 */
+#define PEM_C_MTILE ((pem_cplan_array)11)
+
 /* The device exclusive scan (replaces thrust::exclusive_scan, spgemm.cu:1168, 1242, 1288, and NSPARSE/utils_cuda_scan.h)
  * on a caller's array: out[0..n] = exclusive prefix sums, out[n] = *total.  regime 0: chosen by n like the hot path;
  * 1: one block; 2: the single-launch chained scan (n <= 262144); 3: the three-launch scan.  in_place scans the device

@@ -26,6 +26,11 @@ T_ARRAYS = dict(tile_keys=(0, np.int64), tile_nnz_ptr=(1, np.int32), masks=(2, n
 C_ARRAYS = dict(c_tile_rowptr=(0, np.int32), c_tile_rowidx=(1, np.int32), c_tile_colidx=(2, np.int32), pairs_offset=(3, np.int32),
                 pairs_a=(4, np.int32), pairs_b=(5, np.int32), c_mask=(6, np.uint32), c_tile_nnz_ptr=(7, np.int32),
                 c_rowptr=(8, np.uint8), c_rowcolidx=(9, np.uint8), c_vals=(10, np.float64))
+# pem_test.h's further pem_cplan_array values (CPlan.array takes them too): of masked plans, M's tile id per C tile
+C_TEST_ARRAYS = dict(c_mtile=(11, np.int32))
+
+# enum pem_mask_flags (include/pem_spgemm.h)
+MASK_STRUCTURE, MASK_COMPLEMENT = 0, 1
 
 # every symbol include/pem_spgemm.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -39,7 +44,7 @@ ABI_SYMBOLS = [
     "pem_c_export_csr_device_f32", "pem_c_export_coo_f32", "pem_set_graph_replay",
     "pem_ctx_reserve", "pem_ctx_trim", "pem_ctx_memory_stats", "pem_cplan_set_option", "pem_cplan_get_option", "pem_debug_scan_i32",
     "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
-    "pem_tiled_set_values_device_f32",
+    "pem_tiled_set_values_device_f32", "pem_cplan_create_masked",
 ]
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
@@ -328,12 +333,20 @@ def tile_row_weights(ctx, A, B):
 
 
 class CPlan:
-    """pem_cplan: C = A*B over tile rows [tile_row_begin, tile_row_end) of A (steps 1-3)."""
+    """pem_cplan: C = A*B over tile rows [tile_row_begin, tile_row_end) of A (steps 1-3).
 
-    def __init__(self, ctx, A, B, tile_row_begin=0, tile_row_end=-1):
-        self.ctx, self.A, self.B = ctx, A, B
+    mask: a Tiled M of C's shape (A.rows x B.cols): the plan computes C<M>, only the entries of A*B at M's stored positions --
+    with complement=True only those where M stores nothing (pem_cplan_create_masked).  The plan keeps a reference to M."""
+
+    def __init__(self, ctx, A, B, tile_row_begin=0, tile_row_end=-1, mask=None, complement=False):
+        self.ctx, self.A, self.B, self.mask = ctx, A, B, mask
         self._h = C.c_void_p()
-        _check(lib().pem_cplan_create(ctx._h, A._h, B._h, int(tile_row_begin), int(tile_row_end), C.byref(self._h)))
+        if mask is None:
+            _check(lib().pem_cplan_create(ctx._h, A._h, B._h, int(tile_row_begin), int(tile_row_end), C.byref(self._h)))
+        else:
+            flags = MASK_COMPLEMENT if complement else MASK_STRUCTURE
+            _check(lib().pem_cplan_create_masked(ctx._h, A._h, B._h, mask._h, flags, int(tile_row_begin), int(tile_row_end),
+                                                 C.byref(self._h)))
 
     def set_option(self, name, value):
         """pem_cplan_set_option: kernel variants / test hooks (OPTIONS); the next pass is a full one"""
@@ -362,11 +375,11 @@ class CPlan:
         return {k: getattr(i, k) for k, _ in CPlanInfo._fields_}
 
     def array(self, name):
-        which, dt = C_ARRAYS[name]
+        which, dt = C_ARRAYS[name] if name in C_ARRAYS else C_TEST_ARRAYS[name]
         i = self.info()
         TC, P, NZ, mt = i["ntiles_c"], i["npairs"], i["nnz_c"], i["tile_row_end"] - i["tile_row_begin"]
         cnt = dict(c_tile_rowptr=mt + 1, c_tile_rowidx=TC, c_tile_colidx=TC, pairs_offset=TC + 1, pairs_a=P, pairs_b=P, c_mask=8 * TC,
-                   c_tile_nnz_ptr=TC + 1, c_rowptr=16 * TC, c_rowcolidx=NZ, c_vals=NZ)[name]
+                   c_tile_nnz_ptr=TC + 1, c_rowptr=16 * TC, c_rowcolidx=NZ, c_vals=NZ, c_mtile=TC)[name]
         if name == "c_vals":
             dt = self.A.dtype
         out = np.zeros(cnt, dtype=dt)

@@ -313,6 +313,17 @@ struct pem_tiled {
 
 struct pem_cplan {
     const pem_tiled *A = nullptr, *B = nullptr;
+    // masked plan (pem_cplan_create_masked, mask.hip): C<M> = A*B.  Step 1 ends with a filter of its lists by M's tile set, step 2
+    // ANDs every C tile's mask with M's tile there (or its complement); nothing after that knows about the mask
+    const pem_tiled *M = nullptr;
+    int mask_complement = 0;
+    pem::DevBuf c_mtile;               // int per (kept) C tile: M's tile id at its (row, column), -1 where M has none (complement only)
+    pem::DevBuf mf_tile_off, mf_tile_mt, mf_keep_t, mf_keep_p;   // the filter's per-tile scratch (unmasked tile list)
+    // the step-1 lists are compacted into these and then swapped in; every pass swaps back first, so step 1 and the filter write the
+    // same buffers on every pass (a captured graph replays them)
+    pem::DevBuf mf_pair_col, mf_pairs_a, mf_pairs_b, mf_blk_heads;
+    bool mf_swapped = false;
+    int64_t w_Pm = 0, w_TCm = 0;       // kept pairs / C tiles of the last complete pass (a repeat pass does not read them back)
     int tr_lo = 0, tr_hi = 0;
     int a_lo = 0, a_hi = 0;            // A tile id range of the slice
     int max_row_tiles = 0;             // A tiles in the slice's longest tile row

@@ -94,6 +94,35 @@ extern "C" pem_status pem_cplan_create(pem_ctx *ctx, const pem_tiled *A, const p
     return PEM_OK;
 }
 
+// C<M> = A*B (include/pem_spgemm.h; the filter is in mask.hip, the AND in step 2's s2_tiles_kernel<.., MASKED>)
+extern "C" pem_status pem_cplan_create_masked(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const pem_tiled *M, int mask_flags, int32_t tr_lo,
+                                              int32_t tr_hi, pem_cplan **out)
+{
+    if (!ctx || !A || !B || !out) return PEM_E_INVALID;
+    *out = nullptr;
+    if (!M) {
+        set_error("pem_cplan_create_masked: the mask M is null");
+        return PEM_E_INVALID;
+    }
+    if (mask_flags != PEM_MASK_STRUCTURE && mask_flags != PEM_MASK_COMPLEMENT) {
+        set_error("pem_cplan_create_masked: unknown mask flags %d (PEM_MASK_STRUCTURE = 0 or PEM_MASK_COMPLEMENT = 1)", mask_flags);
+        return PEM_E_INVALID;
+    }
+    PEM_TRY(pem_cplan_create(ctx, A, B, tr_lo, tr_hi, out));
+    if (M->rows != A->rows || M->cols != B->cols) {
+        set_error("pem_cplan_create_masked: M is %d x %d but C = A*B is %d x %d", M->rows, M->cols, A->rows, B->cols);
+        delete *out;
+        *out = nullptr;
+        return PEM_E_INVALID;
+    }
+    pem_cplan *p = *out;
+    p->M = M;
+    p->mask_complement = mask_flags == PEM_MASK_COMPLEMENT;
+    p->opt_step1_esc = 0;   // the filter works on the row-local step 1's lists, the AND sits in the fused step 2
+    p->opt_wide = 1;
+    return PEM_OK;
+}
+
 // A plan's instantiated graph is not destroyed the moment the plan lets go of it.  Round 3 saw hipGraphLaunch fault (a segmentation
 // fault inside the runtime, hip::Graph::UpdateStreams by the rocgdb backtrace of the time, which was not kept) after 8-12 create /
 // capture / replay / destroy rounds of plans with forked streams (tools/split_tune_emulate.py).  Round 4 ran that script once under
@@ -179,6 +208,11 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
     int *slot = plan_option_slot(plan, which);
     if (!slot || value < 0 || value > 0x7FFFFFFF) {
         set_error("pem_cplan_set_option: unknown option %d or value %lld out of range", (int)which, (long long)value);
+        return PEM_E_INVALID;
+    }
+    if (plan->M && ((which == PEM_OPT_STEP1_GLOBAL_SORT && value != 0) || (which == PEM_OPT_WIDE && value == 0))) {
+        set_error("pem_cplan_set_option: a masked plan runs the row-local step 1 and the fused step 2 (%s = %lld refused)",
+                  which == PEM_OPT_WIDE ? "PEM_OPT_WIDE" : "PEM_OPT_STEP1_GLOBAL_SORT", (long long)value);
         return PEM_E_INVALID;
     }
     const int v = (which == PEM_OPT_S1_XLCAP || which == PEM_OPT_S3_EPW || which == PEM_OPT_S2_TRANSPOSED) ? (int)value : (value != 0);
@@ -295,8 +329,7 @@ extern "C" pem_status pem_spgemm(pem_ctx *ctx, pem_cplan *plan)
     } chain(ctx);
     auto launch_verify = [&]() {
         if (plan->verify_folded) return;   // step 2's last kernel has already compared the sizes
-        const WarmCheck wc = {1, plan->w_P, plan->w_Pall, plan->w_TC, plan->w_nnz, plan->w_nxl,
-                              {plan->w_counts[0], plan->w_counts[1], plan->w_counts[2], plan->w_counts[3], plan->w_counts[4]}, plan->w_nsegs, nullptr};
+        const WarmCheck wc = warm_check_of(plan);
         PEM_LAUNCH(ctx, warm_verify_kernel, 1, 1, reinterpret_cast<const long long *>(ctx->d_scalars), plan->bin_count.as<int>(), wc, ctx->d_flags);
     };
     // Graph replay (pem_set_graph_replay): a repeat pass has fixed grids, sizes and buffer addresses, so its ~28 launches,
@@ -396,7 +429,7 @@ extern "C" pem_status pem_cplan_get_array(pem_ctx *ctx, const pem_cplan *p, pem_
     const void *src = nullptr;
     size_t want = 0;
     int need = 1;
-    switch (which) {
+    switch ((int)which) {                              // (pem_test.h adds PEM_C_MTILE)
     case PEM_C_TILE_ROWPTR: src = p->c_tile_rowptr.p; want = 4 * (mt + 1); break;
     case PEM_C_TILE_ROWIDX:
         PEM_TRY(ensure_c_rowidx(ctx, p));
@@ -428,6 +461,14 @@ extern "C" pem_status pem_cplan_get_array(pem_ctx *ctx, const pem_cplan *p, pem_
         src = p->c_rowcolidx.p;
         want = NZ;
         need = 2;
+        break;
+    case PEM_C_MTILE:
+        if (!p->M) {
+            set_error("pem_cplan_get_array(PEM_C_MTILE): not a masked plan");
+            return PEM_E_INVALID;
+        }
+        src = p->c_mtile.p;
+        want = 4 * TC;
         break;
     case PEM_C_VALS:
         if (p->state >= 3) PEM_TRY(c_values_current(p, "pem_cplan_get_array(PEM_C_VALS)"));

@@ -21,6 +21,8 @@ struct WarmCheck {
     long long P, Pall, TC, nnz, nxl;
     int c[5];
     int nsegs;    int *host_flags;     // where set: the pass's status flags are left in host memory by the checking thread (no copy node after the pass)
+    int masked;                        // masked plan: the mask filter's kept pairs and C tiles (d_scalars[4], [5]) are compared too
+    long long Pm, TCm;
 };
 __device__ __forceinline__ void warm_check(const WarmCheck &w, const long long *__restrict__ d_scalars, const int *__restrict__ bin_count,
                                            int *__restrict__ flags)
@@ -28,10 +30,18 @@ __device__ __forceinline__ void warm_check(const WarmCheck &w, const long long *
     if (d_scalars[0] != w.P || d_scalars[1] != w.TC || d_scalars[2] != w.nnz || d_scalars[3] != w.Pall || bin_count[0] != w.c[0] ||
         bin_count[1] != w.c[1] || bin_count[2] != w.c[2] || bin_count[3] != w.c[3] || bin_count[4] != w.c[4] || bin_count[BC_XL_TOTAL] != w.nxl || bin_count[BC_SEGS] != w.nsegs)
         flags[FLAG_CAPACITY] = 1;
+    if (w.masked && (d_scalars[4] != w.Pm || d_scalars[5] != w.TCm)) flags[FLAG_CAPACITY] = 1;
     if (w.host_flags) {
         // the caller guarantees that nothing after this thread sets a flag in this pass (s2_offsets_kernel + step 3: none do)
         for (int i = 0; i < NUM_FLAGS; ++i) w.host_flags[i] = flags[i];
     }
+}
+
+// the size check of a repeat pass of this plan (host_flags unset)
+inline WarmCheck warm_check_of(const pem_cplan *p)
+{
+    return WarmCheck{1, p->w_P, p->w_Pall, p->w_TC, p->w_nnz, p->w_nxl, {p->w_counts[0], p->w_counts[1], p->w_counts[2], p->w_counts[3], p->w_counts[4]},
+                     p->w_nsegs, nullptr, p->M != nullptr, p->w_Pm, p->w_TCm};
 }
 
 // one fused multiply-add per product in the operands' own precision (the oracle's chain; the reference computes in
@@ -45,6 +55,9 @@ void retire_graph(pem_ctx *ctx, pem_cplan *plan);
 pem_status step1_impl(pem_ctx *ctx, pem_cplan *p, bool allow_warm);
 pem_status step2_impl(pem_ctx *ctx, pem_cplan *p);
 pem_status step3_impl(pem_ctx *ctx, pem_cplan *p);
+// masked plans (mask.hip): step 1's lists -> those of C<M>; *P / *TC: the unmasked counts in, the kept ones out
+void mask_restore_lists(pem_cplan *p);
+pem_status mask_filter(pem_ctx *ctx, pem_cplan *p, int64_t *P, int64_t *TC);
 pem_status ensure_compact(pem_ctx *ctx, const pem_cplan *cp);       // _C_tileColIdx / pair offsets in the reference layout
 pem_status ensure_c_rowidx(pem_ctx *ctx, const pem_cplan *p);       // _C_tileRowIdx
 pem_status ensure_c_rowptr(pem_ctx *ctx, const pem_cplan *p);       // Ctiles_rowPtr

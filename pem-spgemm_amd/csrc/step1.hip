@@ -1686,6 +1686,7 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
     p->c_rowidx_valid = false;
     p->compact_valid = false;
     p->ntiles_c = p->npairs = p->nnz_c = 0;
+    if (p->M) mask_restore_lists(p);   // masked plan: back to the buffers step 1 wrote on the pass before (mask.hip)
     if (!ctx->capturing) PEM_HIP(hipEventRecord(ctx->ev[0], st));
     PEM_TRY(p->c_tile_rowptr.reserve(sizeof(int) * ((size_t)mt + 4)));
     PEM_TRY(p->row_list.reserve(sizeof(int) * (S1_NLIST * (size_t)mt + 4)));
@@ -1857,6 +1858,10 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
         // _C_tileColIdx and the pair offsets in the reference's dense layout are written by step 2's fused kernel
         // straight from the row-local scratch; a caller that stops after step 1 gets them from ensure_compact()
         p->pairs_ready = true;
+    }
+    if (p->M) {   // masked plan: the lists of C<M> from here on (mask.hip)
+        PEM_TRY(mask_filter(ctx, p, &P, &TC));
+        p->npairs = P;
     }
     p->ntiles_c = TC;
     if (!ctx->capturing) PEM_HIP(hipEventRecord(ctx->ev[1], st));

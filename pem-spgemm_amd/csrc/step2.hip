@@ -203,13 +203,18 @@ __device__ __forceinline__ unsigned s2_wave_shl1(unsigned v)   // lane i <- lane
     return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true);
 }
 
-template <bool TRANSPOSED>
-__global__ void __launch_bounds__(256, 8) s2_tiles_kernel(const int *__restrict__ pair_col, const int *__restrict__ pairs_a, const int *__restrict__ pairs_b,
+// MASKED (masked plans, mask.hip): every C tile's mask is ANDed with the 16 row masks of M's tile c_mtile[t] (m_inv = ~0u: with
+// their complement; c_mtile[t] < 0: M has no tile there, nothing to AND) before it is counted and stored -- the entry counts, the
+// offsets, step 3 and the exports then see C<M> alone.  (The mask rows do not fit the 64 VGPRs of eight workgroups per CU: the masked
+// forms run four.)
+template <bool TRANSPOSED, bool MASKED = false>
+__global__ void __launch_bounds__(256, MASKED ? 4 : 8) s2_tiles_kernel(const int *__restrict__ pair_col, const int *__restrict__ pairs_a, const int *__restrict__ pairs_b,
                                                        long long npairs, const int *__restrict__ blk_base,
                                                        const uint16_t *__restrict__ a_masks_t, const uint16_t *__restrict__ b_masks,
                                                        const uint32_t *__restrict__ a_occ, const uint32_t *__restrict__ b_occ, long long ntc,
                                                        int *__restrict__ c_colidx, int *__restrict__ pairs_offset, uint32_t *__restrict__ c_mask,
-                                                       int *__restrict__ group_nnz, uint16_t *__restrict__ c_cnt)
+                                                       int *__restrict__ group_nnz, uint16_t *__restrict__ c_cnt, const int *__restrict__ c_mtile,
+                                                       const uint16_t *__restrict__ m_masks, unsigned m_inv)
 {
     __shared__ unsigned bl[TRANSPOSED ? 16 : 8][256];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -226,7 +231,20 @@ __global__ void __launch_bounds__(256, 8) s2_tiles_kernel(const int *__restrict_
     unsigned ccw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long c_t = 0;
     int c_j = 0, c_p0 = 0;
-    auto store_tile = [&](const long long t, const int j, const int p0, const unsigned (&cw)[8]) {
+    auto store_tile = [&](const long long t, const int j, const int p0, const unsigned (&cw_in)[8]) {
+        unsigned cw[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) cw[q] = cw_in[q];
+        if constexpr (MASKED) {
+            const int mt = c_mtile[t];
+            if (mt >= 0) {   // M's row masks in the natural layout: dword q = row 2q | row 2q+1 << 16
+                const uint4 M0 = *reinterpret_cast<const uint4 *>(m_masks + 16 * (size_t)mt);
+                const uint4 M1 = *reinterpret_cast<const uint4 *>(m_masks + 16 * (size_t)mt + 8);
+                const unsigned mw[8] = {M0.x, M0.y, M0.z, M0.w, M1.x, M1.y, M1.z, M1.w};
+#pragma unroll
+                for (int q = 0; q < 8; ++q) cw[q] &= mw[q] ^ m_inv;
+            }
+        }
         int nnz_t = 0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) nnz_t += __popc(cw[q]);
@@ -534,18 +552,25 @@ pem_status pem::step2_impl(pem_ctx *ctx, pem_cplan *p)
             // the sparse ones (r2 stand-in 0.39 -> 0.46 ms, scircuit 0.077 -> 0.093: two more gathers per pair): by default on the
             // repeat passes of plans with two or more pairs per C tile, whose sizes the pass before left
             const bool transposed = p->opt_s2_transposed == 1 || (p->opt_s2_transposed == 2 && p->warm_pass && p->w_P >= 2 * p->w_TC);
-            if (transposed)
-                PEM_LAUNCH_NAMED(ctx, "s2_tiles_kernel<transposed>", s2_tiles_kernel<true>, (unsigned)((n + 1023) / 1024), 256, p->pair_col.as<int>(),
-                                 p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)n, p->blk_heads.as<int>(), A->masks_t.as<uint16_t>(),
-                                 B->masks.as<uint16_t>(), A->tile_occ.as<uint32_t>(), B->tile_occ.as<uint32_t>(), (long long)ntc,
-                                 p->c_tile_colidx.as<int>(), p->pairs_offset.as<int>(), p->c_mask.as<uint32_t>(), group_nnz,
-                                 decode ? p->c_tile_cnt.as<uint16_t>() : (uint16_t *)nullptr);
+            const uint16_t *a_m = transposed ? A->masks_t.as<uint16_t>() : A->masks.as<uint16_t>();
+            uint16_t *c_cnt = decode ? p->c_tile_cnt.as<uint16_t>() : (uint16_t *)nullptr;
+            const int *c_mtile = p->M ? p->c_mtile.as<int>() : (const int *)nullptr;
+            const uint16_t *m_masks = p->M ? p->M->masks.as<uint16_t>() : (const uint16_t *)nullptr;
+            const unsigned m_inv = p->mask_complement ? ~0u : 0u;
+#define PEM_S2_TILES(NAME, ...)                                                                                                      \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s2_tiles_kernel<__VA_ARGS__>), (unsigned)((n + 1023) / 1024), 256, p->pair_col.as<int>(), p->pairs_a.as<int>(), \
+                     p->pairs_b.as<int>(), (long long)n, p->blk_heads.as<int>(), a_m, B->masks.as<uint16_t>(), A->tile_occ.as<uint32_t>(),     \
+                     B->tile_occ.as<uint32_t>(), (long long)ntc, p->c_tile_colidx.as<int>(), p->pairs_offset.as<int>(), p->c_mask.as<uint32_t>(), \
+                     group_nnz, c_cnt, c_mtile, m_masks, m_inv)
+            if (p->M && transposed)
+                PEM_S2_TILES("s2_tiles_kernel<transposed, masked>", true, true);
+            else if (p->M)
+                PEM_S2_TILES("s2_tiles_kernel<masked>", false, true);
+            else if (transposed)
+                PEM_S2_TILES("s2_tiles_kernel<transposed>", true);
             else
-                PEM_LAUNCH_NAMED(ctx, "s2_tiles_kernel", s2_tiles_kernel<false>, (unsigned)((n + 1023) / 1024), 256, p->pair_col.as<int>(),
-                                 p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)n, p->blk_heads.as<int>(), A->masks.as<uint16_t>(),
-                                 B->masks.as<uint16_t>(), A->tile_occ.as<uint32_t>(), B->tile_occ.as<uint32_t>(), (long long)ntc,
-                                 p->c_tile_colidx.as<int>(), p->pairs_offset.as<int>(), p->c_mask.as<uint32_t>(), group_nnz,
-                                 decode ? p->c_tile_cnt.as<uint16_t>() : (uint16_t *)nullptr);
+                PEM_S2_TILES("s2_tiles_kernel", false);
+#undef PEM_S2_TILES
             PEM_TRY(exclusive_scan_i32(ctx, group_nnz, group_nnz, ngroups, ctx->d_scalars + 2));
             if (p->warm_pass) {
                 nnzc = p->w_nnz;
@@ -567,7 +592,7 @@ pem_status pem::step2_impl(pem_ctx *ctx, pem_cplan *p)
                                              {&p->c_vals, (size_t)A->value_bytes * ((size_t)nnzc + 1)}}));
             PEM_TRY(p->s3_chunk_tile.reserve(sizeof(int) * ((size_t)nnzc / S3_CHUNK + 4)));
             WarmCheck wc = {};
-            if (p->warm_pass) wc = WarmCheck{1, p->w_P, p->w_Pall, p->w_TC, p->w_nnz, p->w_nxl, {p->w_counts[0], p->w_counts[1], p->w_counts[2], p->w_counts[3], p->w_counts[4]}, p->w_nsegs, nullptr};
+            if (p->warm_pass) wc = warm_check_of(p);
             p->verify_folded = p->warm_pass;
             // s2_offsets_kernel's checking thread is the last writer of a flag in the pass: it leaves all of them in host memory
             if (p->warm_pass && decode && ctx->h_flags_dev) {

@@ -609,12 +609,12 @@ pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
     const bool s3_many = (size_t)p->nnz_c >= 4 * s3_slots * (2 * (size_t)S3_EPW);
     const size_t s3_epw = (size_t)S3_EPW * (size_t)(p->opt_epw > 0 ? p->opt_epw : (ntc > 0 && (size_t)p->nnz_c >= 8 * ntc && !deep && s3_many) ? 2 : 1);
     // 32-bit byte offsets on scalar bases where every array the shallow kernel touches is smaller than 4 GiB; the marked
-    // entry -> tile lookup where no C tile is empty (pruned lists)
+    // entry -> tile lookup where no C tile is empty (pruned lists; a mask can empty a C tile)
     const size_t gib4 = (size_t)1 << 32, vb = (size_t)A->value_bytes;
     const bool idx32 = !p->opt_idx64 && 32 * (ntc + 1) < gib4 && 4 * ((size_t)p->npairs + 4) < gib4 && 64 * ((size_t)A->ntiles + 1) < gib4 &&
                        64 * ((size_t)B->ntiles + 1) < gib4 && vb * ((size_t)A->nnz + 1) < gib4 && vb * ((size_t)B->nnz + 1) < gib4 &&
                        vb * ((size_t)p->nnz_c + 1) < gib4;
-    const bool mark = p->opt_mark && p->opt_prune;
+    const bool mark = p->opt_mark && p->opt_prune && !p->M;
     const int s3_xcd = p->opt_s3_xcd;
     if (ntc > 0 && f32)
         PEM_S3_LAUNCH(float);

@@ -331,9 +331,12 @@ int main(int argc, char *argv[])
     // `--gpus N`: N tile-row blocks of A on N devices, C gathered to device 0 over RCCL (see run_multi); the blocks are
     // re-cut from measured pass times first (`--no-tune-split` keeps the product-balanced cut), and the product is also run as
     // `--chunks K` chunks per rank with the gather overlapped (default: K from C's size; 0: off).
+    // `--mask <M.mtx>` computes the masked product C<M> = A*B: only the entries at M's stored positions (pem_cplan_create_masked);
+    // with `--mask-complement` only those where M stores nothing.  M has C's shape; the flop count stays the unmasked product's.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
-    const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr;
+    const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
+    bool mask_complement = false;
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -349,6 +352,8 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--out") && r + 1 < argc) out_path = argv[++r];
             else if (!strcmp(argv[r], "--cache") && r + 1 < argc) cache_dir = argv[++r];
             else if (!strcmp(argv[r], "--fp32")) fp32 = true;
+            else if (!strcmp(argv[r], "--mask") && r + 1 < argc) mask_path = argv[++r];
+            else if (!strcmp(argv[r], "--mask-complement")) mask_complement = true;
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -372,6 +377,14 @@ int main(int argc, char *argv[])
     const bool save = argc >= 3 && atoi(argv[2]) != 0;     // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     const bool aat = argc == 4;                            // spgemm.cu:788: presence of a 3rd argument, value ignored
 
+    if (mask_complement && !mask_path) {
+        printf("--mask-complement needs --mask <M.mtx>. Exiting.\n");
+        return 1;
+    }
+    if (ngpu > 0 && mask_path) {
+        printf("--gpus does not combine with --mask (masked products run on one device). Exiting.\n");
+        return 1;
+    }
     if (ngpu > 0) {
         if (fp32 || cache_dir) {
             printf("--gpus does not combine with --fp32 / --cache. Exiting.\n");
@@ -548,16 +561,38 @@ int main(int argc, char *argv[])
             printf("input is rectangular. Only AAt is possible. Exiting.\n");   // spgemm.cu:782-786
         return 1;
     }
+    pem_tiled *Mt = nullptr;   // --mask: M's structure (its values are never read, so it is converted as fp64 whatever --fp32 says)
+    pem_coo cm;
+    memset(&cm, 0, sizeof cm);
+    if (mask_path) {
+        if (read_input(mask_path, &cm) != 0) return 1;
+        if (cm.rows != ia.rows || cm.cols != ib.cols) {
+            printf("mask %s is %d x %d but C = A*B%s is %d x %d. Exiting.\n", mask_path, cm.rows, cm.cols, aat ? "^T" : "", ia.rows, ib.cols);
+            pem_coo_free(&cm);
+            return 1;
+        }
+        if (pem_tiled_from_coo(ctx, cm.rows, cm.cols, cm.nnz, cm.I, cm.J, cm.V, 0, &Mt) != PEM_OK) {
+            fprintf(stderr, "pemspgemm: conversion of %s failed: %s\n", mask_path, pem_last_error());
+            pem_coo_free(&cm);
+            return 2;
+        }
+    }
     if (fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", argv[1], ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
     printf("MATRIX B\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", b_path ? b_path : argv[1], ib.rows, ib.cols, (long long)ib.nnz);
     if (cache_dir) printf("tiled-format cache %s: %d loaded, %d rebuilt\n", cache_dir, cache_hits, cache_misses);
+    if (mask_path)
+        printf("MASK%s\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", mask_complement ? " (complement)" : "", mask_path, cm.rows, cm.cols,
+               (long long)cm.nnz);
     const double conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - conv_start).count();
     uint64_t flop = 0;
     CHECK(pem_flop_count(ctx, A, B, &flop));   // spgemm.cu:1068-1079
 
     pem_cplan *plan = nullptr;
-    CHECK(pem_cplan_create(ctx, A, B, 0, -1, &plan));
+    if (Mt)
+        CHECK(pem_cplan_create_masked(ctx, A, B, Mt, mask_complement ? PEM_MASK_COMPLEMENT : PEM_MASK_STRUCTURE, 0, -1, &plan));
+    else
+        CHECK(pem_cplan_create(ctx, A, B, 0, -1, &plan));
     std::vector<double> s1, s2, s3, wall;
     double cold_ms = 0.0;   // the first pass on the plan: every allocation + the three size read-backs (what the reference pays per iteration)
     for (int n = 0; n < WARMUP + REPEAT; ++n) {   // spgemm.cu:1133-1357
@@ -604,6 +639,7 @@ int main(int argc, char *argv[])
     printf("pemSpGEMM took %.2fms ----- GFlops: %.2f\nKernel time %.2fms\nmalloc time %.2fms\n", total, gflops, kernel, malloc_ms);
     printf("first pass (allocations + size read-backs) %.2fms; the passes above re-use the plan's buffers and sizes\n", cold_ms);
     printf("Flop count: %llu\n\n", (unsigned long long)flop);
+    if (Mt) printf("masked product C<%sM>: the flop count and GFlops above count the unmasked product A*B\n", mask_complement ? "!" : "");
     printf("C tiles: %lld\n", (long long)ci.ntiles_c);
     printf("C nnz: %lld\n", (long long)ci.nnz_c);
     printf("Compression ratio %.2f\n", ratio);
@@ -671,6 +707,8 @@ int main(int argc, char *argv[])
     }
     printf("CLEANING UP RESOURCES\n\n");
     pem_cplan_destroy(ctx, plan);
+    if (Mt) pem_tiled_destroy(ctx, Mt);
+    pem_coo_free(&cm);
     if (B != A) pem_tiled_destroy(ctx, B);
     pem_tiled_destroy(ctx, A);
     pem_ctx_destroy(ctx);
