@@ -205,6 +205,37 @@ typedef enum { PEM_MASK_STRUCTURE = 0, PEM_MASK_COMPLEMENT = 1 } pem_mask_flags;
 pem_status pem_cplan_create_masked(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const pem_tiled *M, int mask_flags,
                                    int32_t tile_row_begin, int32_t tile_row_end, pem_cplan **out);
 
+/* Semirings.  Step 3 reduces the products of every C entry (i, j) -- all k where A(i,k) and B(k,j)
+ * are stored -- under the plan's semiring; the structure of C never depends on it (C stores exactly the entries the plus-times
+ * plan stores, masked or not: the symbolic product), only the value at each entry does.
+ *   PEM_SEMIRING_PLUS_TIMES (default)  the fma chain of every other entry point, bit for bit
+ *   PEM_SEMIRING_MIN_PLUS              fmin over the products of (a + b), starting from +inf
+ *   PEM_SEMIRING_MAX_PLUS              fmax over the products of (a + b), starting from -inf
+ *   PEM_SEMIRING_MAX_TIMES             fmax over the products of (a * b), starting from -inf
+ *   PEM_SEMIRING_PLUS_PAIR             the number of products, as a value of C's type (A's and B's values are never read)
+ *   PEM_SEMIRING_LOR_LAND              1 if some product has a != 0 and b != 0 (NaN counts as != 0), else 0
+ * Each a + b and a * b is rounded once in C's type, to nearest; the min/max semirings involve no fma.  min and max follow C's
+ * fmin / fmax: a NaN product is skipped, an entry whose every product is NaN keeps the start value, and the sign of a zero result
+ * is not specified.  Min/max results therefore do not depend on the order of the products.  plus_pair counts exactly up to 2^53
+ * (fp64) / 2^24 (fp32).  lor_land stores 0.0 where every product has a zero operand: the entry stays, as plus-times keeps entries
+ * that cancel.
+ * pem_cplan_set_semiring is allowed at any time, on every plan (masked or not, fp64 or fp32, any option); setting the current
+ * semiring is a no-op.  Changing it makes C's values stale, as a numeric refresh does: the pem_c_export_* entry points and
+ * pem_cplan_get_array(PEM_C_VALS) return PEM_E_STATE until pem_spgemm_step3 or pem_spgemm runs again (the symbolic arrays stay
+ * readable).  The intended use: one symbolic pass, then set_semiring + pem_spgemm_step3 per semiring.  A graph captured under
+ * the old semiring (pem_set_graph_replay) is dropped; the next pem_spgemm captures again.  An unknown value or a null plan:
+ * PEM_E_INVALID.  The pem_mgpu_* entry points always multiply under plus-times. */
+typedef enum {
+    PEM_SEMIRING_PLUS_TIMES = 0,
+    PEM_SEMIRING_MIN_PLUS = 1,
+    PEM_SEMIRING_MAX_PLUS = 2,
+    PEM_SEMIRING_MAX_TIMES = 3,
+    PEM_SEMIRING_PLUS_PAIR = 4,
+    PEM_SEMIRING_LOR_LAND = 5
+} pem_semiring;
+pem_status pem_cplan_set_semiring(pem_cplan *plan, int semiring);
+pem_status pem_cplan_get_semiring(const pem_cplan *plan, int *semiring);
+
 /* Plan options.  A new plan takes its defaults from the environment once, in pem_cplan_create (PEM_PRUNE=0, PEM_STEP1=esc,
  * PEM_WIDE=0, PEM_NO_WARM=1, PEM_S3_BAND=0, PEM_EXPORT=rows); after that only pem_cplan_set_option changes them -- no entry
  * point reads the environment at call time.  Changing an option sends the plan back to the last step the option does not touch

@@ -32,6 +32,9 @@ C_TEST_ARRAYS = dict(c_mtile=(11, np.int32))
 # enum pem_mask_flags (include/pem_spgemm.h)
 MASK_STRUCTURE, MASK_COMPLEMENT = 0, 1
 
+# enum pem_semiring (include/pem_spgemm.h): how step 3 reduces the products of a C entry
+SEMIRINGS = dict(plus_times=0, min_plus=1, max_plus=2, max_times=3, plus_pair=4, lor_land=5)
+
 # every symbol include/pem_spgemm.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "pem_last_error", "pem_version", "pem_ctx_create", "pem_ctx_create_on_stream", "pem_ctx_destroy", "pem_ctx_synchronize",
@@ -44,7 +47,7 @@ ABI_SYMBOLS = [
     "pem_c_export_csr_device_f32", "pem_c_export_coo_f32", "pem_set_graph_replay",
     "pem_ctx_reserve", "pem_ctx_trim", "pem_ctx_memory_stats", "pem_cplan_set_option", "pem_cplan_get_option", "pem_debug_scan_i32",
     "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
-    "pem_tiled_set_values_device_f32", "pem_cplan_create_masked",
+    "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
 ]
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
@@ -336,9 +339,12 @@ class CPlan:
     """pem_cplan: C = A*B over tile rows [tile_row_begin, tile_row_end) of A (steps 1-3).
 
     mask: a Tiled M of C's shape (A.rows x B.cols): the plan computes C<M>, only the entries of A*B at M's stored positions --
-    with complement=True only those where M stores nothing (pem_cplan_create_masked).  The plan keeps a reference to M."""
+    with complement=True only those where M stores nothing (pem_cplan_create_masked).  The plan keeps a reference to M.
+    semiring: a name of SEMIRINGS -- how step 3 reduces the products of each entry (pem_cplan_set_semiring)."""
 
-    def __init__(self, ctx, A, B, tile_row_begin=0, tile_row_end=-1, mask=None, complement=False):
+    def __init__(self, ctx, A, B, tile_row_begin=0, tile_row_end=-1, mask=None, complement=False, semiring="plus_times"):
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
         self.ctx, self.A, self.B, self.mask = ctx, A, B, mask
         self._h = C.c_void_p()
         if mask is None:
@@ -347,6 +353,20 @@ class CPlan:
             flags = MASK_COMPLEMENT if complement else MASK_STRUCTURE
             _check(lib().pem_cplan_create_masked(ctx._h, A._h, B._h, mask._h, flags, int(tile_row_begin), int(tile_row_end),
                                                  C.byref(self._h)))
+        if semiring != "plus_times":
+            self.set_semiring(semiring)
+
+    def set_semiring(self, name):
+        """pem_cplan_set_semiring: C's values are stale (exports raise PEM_E_STATE) until step3() or spgemm() runs again"""
+        if name not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {name!r}; one of {sorted(SEMIRINGS)}")
+        _check(lib().pem_cplan_set_semiring(self._h, SEMIRINGS[name]))
+
+    @property
+    def semiring(self):
+        v = C.c_int()
+        _check(lib().pem_cplan_get_semiring(self._h, C.byref(v)))
+        return {v_: k for k, v_ in SEMIRINGS.items()}[v.value]
 
     def set_option(self, name, value):
         """pem_cplan_set_option: kernel variants / test hooks (OPTIONS); the next pass is a full one"""

@@ -377,6 +377,8 @@ struct pem_cplan {
     bool compact_valid = false;        // c_tile_colidx / pairs_offset hold the dense layout (else: row-local scratch, see ensure_compact)
     pem::DevBuf group_nnz;             // C entries per S2_GROUP tiles (s2_tiles_kernel -> scan -> s2_entries_kernel)
     uint64_t a_version = 0, b_version = 0;   // A's / B's value_version when step 3 last completed (c_values_current)
+    int semiring = 0;                  // pem_semiring of step 3 (pem_cplan_set_semiring)
+    int c_semiring = 0;                // ... under which step 3 last completed (c_values_current)
     // sizes of the last complete pass on this plan.  The structure of A and B is immutable, so a repeat pass has the same
     // sizes: it skips the three host read-backs and a device-side check compares them at the end instead.
     pem_ctx *owner = nullptr;              // the context the plan was created on

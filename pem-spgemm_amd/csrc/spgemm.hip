@@ -245,6 +245,29 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
     return PEM_OK;
 }
 
+// The semiring of step 3 (include/pem_spgemm.h).  Only step 3's values depend on it: the plan keeps its steps 1-2 and its warm
+// sizes, C's values turn stale (c_values_current) and a graph captured under the old semiring is dropped.
+extern "C" pem_status pem_cplan_set_semiring(pem_cplan *plan, int semiring)
+{
+    if (!plan) return PEM_E_INVALID;
+    if (semiring < PEM_SEMIRING_PLUS_TIMES || semiring > PEM_SEMIRING_LOR_LAND) {
+        set_error("pem_cplan_set_semiring: unknown semiring %d (PEM_SEMIRING_PLUS_TIMES = 0 .. PEM_SEMIRING_LOR_LAND = 5)", semiring);
+        return PEM_E_INVALID;
+    }
+    if (plan->semiring == semiring) return PEM_OK;
+    plan->semiring = semiring;
+    if (plan->graph_exec) retire_graph(plan->owner, plan);
+    plan->graph_failed = false;
+    return PEM_OK;
+}
+
+extern "C" pem_status pem_cplan_get_semiring(const pem_cplan *plan, int *semiring)
+{
+    if (!plan || !semiring) return PEM_E_INVALID;
+    *semiring = plan->semiring;
+    return PEM_OK;
+}
+
 extern "C" pem_status pem_cplan_get_option(const pem_cplan *plan, pem_option which, int64_t *value)
 {
     if (!plan || !value) return PEM_E_INVALID;

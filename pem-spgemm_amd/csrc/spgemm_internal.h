@@ -49,6 +49,47 @@ inline WarmCheck warm_check_of(const pem_cplan *p)
 __device__ __forceinline__ double pem_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float pem_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
+// Step 3's reduction as a compile-time policy (include/pem_spgemm.h, pem_semiring): the accumulator's start value, how one
+// product (a, b) enters it, and whether the operands' values are read at all.  A policy without values (plus_pair) adds the
+// number of products a (pair, entry) meets, __popc(Amask[r] & BT[c]), through count(); the kernels then gather no value.
+// SrPlusTimes is today's chain: start VT(0), one pem_fma per product.  The min/max policies round every a + b / a * b once in
+// VT (-ffp-contract=off: no fma) and reduce with fmin / fmax, which skip NaN.
+template <typename VT> __device__ __forceinline__ VT pem_inf() { return sizeof(VT) == 8 ? (VT)__builtin_huge_val() : (VT)__builtin_huge_valf(); }
+template <typename VT> __device__ __forceinline__ VT pem_fmin(VT x, VT y) { if constexpr (sizeof(VT) == 8) return __builtin_fmin(x, y); else return __builtin_fminf(x, y); }
+template <typename VT> __device__ __forceinline__ VT pem_fmax(VT x, VT y) { if constexpr (sizeof(VT) == 8) return __builtin_fmax(x, y); else return __builtin_fmaxf(x, y); }
+struct SrPlusTimes {
+    static constexpr bool vals = true;
+    template <typename VT> static __device__ __forceinline__ VT start() { return VT(0); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT a, VT b, VT acc) { return pem_fma(a, b, acc); }
+};
+struct SrMinPlus {
+    static constexpr bool vals = true;
+    template <typename VT> static __device__ __forceinline__ VT start() { return pem_inf<VT>(); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT a, VT b, VT acc) { return pem_fmin(acc, a + b); }
+};
+struct SrMaxPlus {
+    static constexpr bool vals = true;
+    template <typename VT> static __device__ __forceinline__ VT start() { return -pem_inf<VT>(); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT a, VT b, VT acc) { return pem_fmax(acc, a + b); }
+};
+struct SrMaxTimes {
+    static constexpr bool vals = true;
+    template <typename VT> static __device__ __forceinline__ VT start() { return -pem_inf<VT>(); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT a, VT b, VT acc) { return pem_fmax(acc, a * b); }
+};
+struct SrPlusPair {
+    static constexpr bool vals = false;
+    template <typename VT> static __device__ __forceinline__ VT start() { return VT(0); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT, VT, VT acc) { return acc + VT(1); }
+    // the products of one (pair, entry): the bits of m
+    template <typename VT> static __device__ __forceinline__ VT count(unsigned m, VT acc) { return acc + VT(__popc(m)); }
+};
+struct SrLorLand {
+    static constexpr bool vals = true;
+    template <typename VT> static __device__ __forceinline__ VT start() { return VT(0); }
+    template <typename VT> static __device__ __forceinline__ VT combine(VT a, VT b, VT acc) { return (a != VT(0) && b != VT(0)) ? VT(1) : acc; }
+};
+
 // host side (each in the unit of its step)
 pem_status step_elapsed(pem_ctx *ctx, int e0, int e1, double *dst);
 void retire_graph(pem_ctx *ctx, pem_cplan *plan);
@@ -67,6 +108,10 @@ pem_status ensure_c_rowcolidx(pem_ctx *ctx, const pem_cplan *cp);   // Ctiles_ro
 // A or B that no step 3 has followed yet
 inline pem_status c_values_current(const pem_cplan *p, const char *fn)
 {
+    if (p->c_semiring != p->semiring) {   // ... or after pem_cplan_set_semiring
+        set_error("%s: the plan's semiring was changed (pem_cplan_set_semiring) after C was computed; run pem_spgemm_step3 or pem_spgemm first", fn);
+        return PEM_E_STATE;
+    }
     if (p->a_version == p->A->value_version && p->b_version == p->B->value_version) return PEM_OK;
     set_error("%s: the values of %s were refreshed (pem_tiled_set_values) after C was computed; run pem_spgemm_step3 or pem_spgemm first", fn,
               p->a_version != p->A->value_version ? "A" : "B");
@@ -76,6 +121,7 @@ inline void note_c_values(pem_cplan *p)   // step 3 has just completed
 {
     p->a_version = p->A->value_version;
     p->b_version = p->B->value_version;
+    p->c_semiring = p->semiring;
 }
 
 }  // namespace pem

@@ -1,5 +1,6 @@
 // step3.hip -- row a13: the numeric step.
 #include "spgemm_internal.h"
+#include <type_traits>
 
 using namespace pem;
 
@@ -7,9 +8,9 @@ using namespace pem;
 // step 3 (spgemm.cu:593-661).  16 lanes per C tile, one C entry per lane (strided by 16);
 // pairs ascending in k-tile, bits of Amask[r] & BT[c] ascending, one fma per product, the
 // accumulator lives in a register and is stored once (no global RMW, no dependence on
-// zero-filled memory -- SURVEY 2.3 #1).
+// zero-filled memory -- SURVEY 2.3 #1).  SR: the semiring (spgemm_internal.h); SrPlusTimes is the chain above.
 // ------------------------------------------------------------------------------------------
-template <typename VT>
+template <typename VT, typename SR = SrPlusTimes>
 __global__ void __launch_bounds__(256) s3_accumulate_kernel(
     const int *__restrict__ pairs_offset, const int *__restrict__ pairs_a, const int *__restrict__ pairs_b, long long ntc,
     const int *__restrict__ c_tile_nnz_ptr, const uint8_t *__restrict__ c_rowcolidx, VT *__restrict__ c_vals,
@@ -26,12 +27,16 @@ __global__ void __launch_bounds__(256) s3_accumulate_kernel(
         const unsigned rc = c_rowcolidx[off + n];
         const int r = rc >> 4, c = rc & 15;
         const unsigned clt = (1u << c) - 1u;
-        VT acc = VT(0);
+        VT acc = SR::template start<VT>();
         for (int p = p0; p < p1; ++p) {
             const int a = pairs_a[p], b = pairs_b[p];
             const unsigned am = a_masks[16 * (size_t)a + r];
             unsigned m = am & b_masks_t[16 * (size_t)b + c];
             if (!m) continue;
+            if constexpr (!SR::vals) {
+                acc = SR::template count<VT>(m, acc);
+                continue;
+            }
             const VT *av = a_vals + a_nnz_ptr[a] + a_rowptr[16 * (size_t)a + r];
             const VT *bvbase = b_vals + b_nnz_ptr[b];
             while (m) {
@@ -39,7 +44,7 @@ __global__ void __launch_bounds__(256) s3_accumulate_kernel(
                 m &= m - 1;
                 const int ao = __popc(am & ((1u << kk) - 1u));
                 const int bo = __popc((unsigned)b_masks[16 * (size_t)b + kk] & clt);
-                acc = pem_fma(av[ao], bvbase[b_rowptr[16 * (size_t)b + kk] + bo], acc);
+                acc = SR::template combine<VT>(av[ao], bvbase[b_rowptr[16 * (size_t)b + kk] + bo], acc);
             }
         }
         c_vals[off + n] = acc;
@@ -52,7 +57,8 @@ __global__ void __launch_bounds__(256) s3_accumulate_kernel(
 // 6-step shuffle search and costs no memory traffic.  Per (entry, pair): one gather of the A
 // row record (mask | rowptr<<16), one of B's transposed mask; per product one B row record and
 // the two operand values.  Pairs ascend in k-tile, bits ascend, one fma per product: the same
-// chain as the oracle.
+// chain as the oracle.  SR (the semiring, spgemm_internal.h) replaces each fma and the start value; a policy without values
+// (plus_pair) sums __popc(Amask[r] & BT[c]) per pair and leaves the value offsets and value gathers out of the kernel.
 constexpr int S3_EPW = S3_CHUNK;   // C entries per wave
 constexpr int S3_BAND_MIN = 8;       // C tiles with at least this many pairs go to s3_band_kernel (deep plans)
 constexpr int S3_BAND_CH = 16;       // pairs whose records one wave stages in LDS at a time (multiple of 4, at most 64)
@@ -78,7 +84,7 @@ template <bool IDX32, typename T> __device__ __forceinline__ T s3_ld(const T *__
 // without the six-step shuffle search -- the tiles that start inside the trip's 64 entries mark their first entry in a
 // 64-word LDS strip, one ballot turns the strip into a bit mask, and an entry's tile is (tiles started before the trip) +
 // (marks at or below its lane) - 1.
-template <typename VT, bool DEEP, bool BAND = false, bool DECODE = false, bool IDX32 = false, bool MARK = false>
+template <typename VT, bool DEEP, bool BAND = false, bool DECODE = false, bool IDX32 = false, bool MARK = false, typename SR = SrPlusTimes>
 #ifndef PEM_S3_DEEP_WAVES
 #define PEM_S3_DEEP_WAVES 1   // (8 = at most 64 VGPRs for the deep variants too: 6 of them spill and a cage15 share's step 3 is 6.83 against 6.74 ms)
 #endif
@@ -121,11 +127,11 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
         // one pair, so most entries get their whole pair record by shuffle instead of four loads of their own (the step is
         // bound by the number of vector-memory instructions, section 4 of DESIGN.md)
         const int my_a0 = s3_ld<IDX32>(pairs_a, my_p0), my_b0 = s3_ld<IDX32>(pairs_b, my_p0);
-        const int my_av0 = s3_ld<IDX32>(a_nnz_ptr, my_a0), my_bv0 = s3_ld<IDX32>(b_nnz_ptr, my_b0);
+        const int my_av0 = SR::vals ? s3_ld<IDX32>(a_nnz_ptr, my_a0) : 0, my_bv0 = SR::vals ? s3_ld<IDX32>(b_nnz_ptr, my_b0) : 0;
         // ... and the second pair of the tiles that have one (7 %): their entries' second trip then costs 4 instructions, not 8
         const bool two = my_p1 - my_p0 >= 2;
         const int my_a1 = two ? s3_ld<IDX32>(pairs_a, (long long)my_p0 + 1) : 0, my_b1 = two ? s3_ld<IDX32>(pairs_b, (long long)my_p0 + 1) : 0;
-        const int my_av1 = two ? s3_ld<IDX32>(a_nnz_ptr, my_a1) : 0, my_bv1 = two ? s3_ld<IDX32>(b_nnz_ptr, my_b1) : 0;
+        const int my_av1 = SR::vals && two ? s3_ld<IDX32>(a_nnz_ptr, my_a1) : 0, my_bv1 = SR::vals && two ? s3_ld<IDX32>(b_nnz_ptr, my_b1) : 0;
         const long long tend = t0 + 64 < ntc ? t0 + 64 : ntc;
         const int chunk_end = c_tile_nnz_ptr[tend];
         const int first = __shfl(my_off, 0, 64);
@@ -228,7 +234,7 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
             r = rc >> 4;
             c = rc & 15;
         }
-        VT acc = VT(0);
+        VT acc = SR::template start<VT>();
         int p = p0;
         if (!DEEP) {   // first pair: everything but the two records and the values is already here
             // The step is bound by the LATENCY of its dependent gathers (records -> values), eight waves per SIMD being all the
@@ -259,7 +265,7 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 aw1 = s3_ld<IDX32>(a_rec, 16ll * a1 + r);
                 bw1 = s3_ld<IDX32>(b_rec_t, 16ll * b1 + c);
             }
-            if (staged && lane < Pn) {
+            if (SR::vals && staged && lane < Pn) {
                 sav = s3_ld<IDX32>(a_nnz_ptr, sa);
                 sbv = s3_ld<IDX32>(b_nnz_ptr, sb);
             }
@@ -267,34 +273,38 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
             unsigned m = am & bm, m1 = am1 & bm1;
             const int ao = av0 + (int)(aw >> 16), bo = bv0 + (int)(bw >> 16), ao1 = av1 + (int)(aw1 >> 16), bo1 = bv1 + (int)(bw1 >> 16);
             VT x0 = VT(0), y0 = VT(0), x1 = VT(0), y1 = VT(0);
-            if (m) {
+            if (SR::vals && m) {
                 const unsigned below = (1u << __builtin_ctz(m)) - 1u;
                 x0 = s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below));
                 y0 = s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below));
             }
-            if (m1) {
+            if (SR::vals && m1) {
                 const unsigned below = (1u << __builtin_ctz(m1)) - 1u;
                 x1 = s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below));
                 y1 = s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below));
             }
-            if (m) {
-                acc = pem_fma(x0, y0, acc);
-                m &= m - 1;
-                while (m) {
-                    const int kk = __builtin_ctz(m);
+            if constexpr (!SR::vals) {
+                acc = SR::template count<VT>(m1, SR::template count<VT>(m, acc));
+            } else {
+                if (m) {
+                    acc = SR::template combine<VT>(x0, y0, acc);
                     m &= m - 1;
-                    const unsigned below = (1u << kk) - 1u;
-                    acc = pem_fma(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
+                    while (m) {
+                        const int kk = __builtin_ctz(m);
+                        m &= m - 1;
+                        const unsigned below = (1u << kk) - 1u;
+                        acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
+                    }
                 }
-            }
-            if (m1) {
-                acc = pem_fma(x1, y1, acc);
-                m1 &= m1 - 1;
-                while (m1) {
-                    const int kk = __builtin_ctz(m1);
+                if (m1) {
+                    acc = SR::template combine<VT>(x1, y1, acc);
                     m1 &= m1 - 1;
-                    const unsigned below = (1u << kk) - 1u;
-                    acc = pem_fma(s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below)), s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below)), acc);
+                    while (m1) {
+                        const int kk = __builtin_ctz(m1);
+                        m1 &= m1 - 1;
+                        const unsigned below = (1u << kk) - 1u;
+                        acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below)), s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below)), acc);
+                    }
                 }
             }
             p += has2 ? 2 : has1 ? 1 : 0;
@@ -309,12 +319,14 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                         const unsigned amq = awq & 0xFFFFu, bmq = bwq & 0xFFFFu;
                         unsigned mq = amq & bmq;
                         const int aoq = av + (int)(awq >> 16), boq = bv + (int)(bwq >> 16);
-                        while (mq) {
-                            const int kk = __builtin_ctz(mq);
-                            mq &= mq - 1;
-                            const unsigned below = (1u << kk) - 1u;
-                            acc = pem_fma(s3_ld<IDX32>(a_vals, (long long)aoq + __popc(amq & below)), s3_ld<IDX32>(b_vals_t, (long long)boq + __popc(bmq & below)), acc);
-                        }
+                        if constexpr (!SR::vals) acc = SR::template count<VT>(mq, acc);
+                        else
+                            while (mq) {
+                                const int kk = __builtin_ctz(mq);
+                                mq &= mq - 1;
+                                const unsigned below = (1u << kk) - 1u;
+                                acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)aoq + __popc(amq & below)), s3_ld<IDX32>(b_vals_t, (long long)boq + __popc(bmq & below)), acc);
+                            }
                     }
                 }
                 p = p1;
@@ -339,8 +351,8 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    av4[k] = a_nnz_ptr[a4[k]];
-                    bv4[k] = b_nnz_ptr[b4[k]];
+                    av4[k] = SR::vals ? a_nnz_ptr[a4[k]] : 0;
+                    bv4[k] = SR::vals ? b_nnz_ptr[b4[k]] : 0;
                 }
             }
             for (; p + 4 <= p1; p += 4) {
@@ -359,21 +371,25 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    nav4[k] = more ? a_nnz_ptr[na4[k]] : 0;
-                    nbv4[k] = more ? b_nnz_ptr[nb4[k]] : 0;
+                    nav4[k] = SR::vals && more ? a_nnz_ptr[na4[k]] : 0;
+                    nbv4[k] = SR::vals && more ? b_nnz_ptr[nb4[k]] : 0;
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const unsigned am = aw4[k] & 0xFFFFu, bm = bw4[k] & 0xFFFFu;
                     unsigned m = am & bm;
                     if (!m) continue;
+                    if constexpr (!SR::vals) {
+                        acc = SR::template count<VT>(m, acc);
+                        continue;
+                    }
                     const VT *av = a_vals + av4[k] + (aw4[k] >> 16);
                     const VT *bv = b_vals_t + bv4[k] + (bw4[k] >> 16);
                     while (m) {
                         const int kk = __builtin_ctz(m);
                         m &= m - 1;
                         const unsigned below = (1u << kk) - 1u;
-                        acc = pem_fma(av[__popc(am & below)], bv[__popc(bm & below)], acc);
+                        acc = SR::template combine<VT>(av[__popc(am & below)], bv[__popc(bm & below)], acc);
                     }
                 }
 #pragma unroll
@@ -395,12 +411,16 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
             const unsigned bm = bw & 0xFFFFu;
             unsigned m = am & bm;
             if (!m) continue;
+            if constexpr (!SR::vals) {
+                acc = SR::template count<VT>(m, acc);
+                continue;
+            }
             const int ao = s3_ld<IDX32>(a_nnz_ptr, a) + (int)(aw >> 16), bo = s3_ld<IDX32>(b_nnz_ptr, b) + (int)(bw >> 16);
             while (m) {
                 const int kk = __builtin_ctz(m);
                 m &= m - 1;
                 const unsigned below = (1u << kk) - 1u;
-                acc = pem_fma(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
+                acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
             }
         }
         // (streamed past the L2 -- nontemporal: C's values are never read here, and the records and values the gathers come back
@@ -425,8 +445,9 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
 // two masks); when a queue fills, all lanes gather their operands together.  Products are queued and summed in ascending
 // pair order, so the fma chain -- and every bit of C -- equals the entry-per-lane kernel's.
 // Grid: one wave per 64 consecutive C tiles; the wave finds the many-pair tiles among them by ballot.
+// SR: the semiring, as in the entry-per-lane kernel (without values: the queue holds masks only and nothing is gathered).
 // ------------------------------------------------------------------------------------------
-template <typename VT>
+template <typename VT, typename SR = SrPlusTimes>
 __global__ void __launch_bounds__(256) s3_band_kernel(const int *__restrict__ pairs_offset, const int *__restrict__ pairs_a,
                                                       const int *__restrict__ pairs_b, long long ntc, const int *__restrict__ c_tile_nnz_ptr,
                                                       const uint8_t *__restrict__ c_rowcolidx, VT *__restrict__ c_vals,
@@ -462,15 +483,15 @@ __global__ void __launch_bounds__(256) s3_band_kernel(const int *__restrict__ pa
             unsigned src = 0;
             if (mine) src = c_rowcolidx[e];
             const unsigned *rowA = recA + (src >> 4) * S3_BAND_RS, *colB = recB + (src & 15) * S3_BAND_RS;
-            VT acc = VT(0);
+            VT acc = SR::template start<VT>();
             for (int pcs = 0; pcs < np; pcs += S3_BAND_CH) {        // S3_BAND_CH pairs per stage: lane k holds pair pcs + k
                 const int M = np - pcs < S3_BAND_CH ? np - pcs : S3_BAND_CH, M4 = (M + 3) & ~3;
                 int ia = 0, ib = 0, oa = 0, ob = 0;
                 if (lane < M) {
                     ia = pairs_a[pb + pcs + lane];
                     ib = pairs_b[pb + pcs + lane];
-                    oa = a_nnz_ptr[ia];
-                    ob = b_nnz_ptr[ib];
+                    oa = SR::vals ? a_nnz_ptr[ia] : 0;
+                    ob = SR::vals ? b_nnz_ptr[ib] : 0;
                 }
                 // the stage's records: word w of pair k is A's row word (w < 16) or B's column word; lanes 0-31 take the even pairs,
                 // 32-63 the odd ones.  All the loads first, then the LDS writes: one round trip per stage.
@@ -518,22 +539,26 @@ __global__ void __launch_bounds__(256) s3_band_kernel(const int *__restrict__ pa
                         bm[h] = on ? bw & 0xFFFFu : 0u;
                         av[h] = a_vals + kav + (aw >> 16);
                         bv[h] = b_vals_t + kbv + (bw >> 16);
-                        const unsigned mm = am[h] & bm[h];
-                        const unsigned below = mm ? (1u << __builtin_ctz(mm)) - 1u : 0u;
-                        va[h] = mm ? av[h][__popc(am[h] & below)] : a_vals[0];
-                        vb[h] = mm ? bv[h][__popc(bm[h] & below)] : b_vals_t[0];
+                        if constexpr (SR::vals) {
+                            const unsigned mm = am[h] & bm[h];
+                            const unsigned below = mm ? (1u << __builtin_ctz(mm)) - 1u : 0u;
+                            va[h] = mm ? av[h][__popc(am[h] & below)] : a_vals[0];
+                            vb[h] = mm ? bv[h][__popc(bm[h] & below)] : b_vals_t[0];
+                        }
                     }
 #pragma unroll
                     for (int h = 0; h < S3_BAND_H; ++h) {
                         unsigned mm = am[h] & bm[h];
-                        if (mm) {
-                            acc = pem_fma(va[h], vb[h], acc);
+                        if constexpr (!SR::vals) {
+                            acc = SR::template count<VT>(mm, acc);
+                        } else if (mm) {
+                            acc = SR::template combine<VT>(va[h], vb[h], acc);
                             mm &= mm - 1;
                             while (mm) {
                                 const int kk = __builtin_ctz(mm);
                                 mm &= mm - 1;
                                 const unsigned below = (1u << kk) - 1u;
-                                acc = pem_fma(av[h][__popc(am[h] & below)], bv[h][__popc(bm[h] & below)], acc);
+                                acc = SR::template combine<VT>(av[h][__popc(am[h] & below)], bv[h][__popc(bm[h] & below)], acc);
                             }
                         }
                     }
@@ -542,6 +567,74 @@ __global__ void __launch_bounds__(256) s3_band_kernel(const int *__restrict__ pa
             if (mine) __builtin_nontemporal_store(acc, c_vals + e);   // (never re-read here: keep the L2 for the operand records and values)
         }
     }
+}
+
+// The launches of one (value type, semiring).  Kernel names: pem_kernel_stats_get and the committed profiles key on them, so
+// plus-times keeps the names it always had and the other semirings append theirs ("s3_band_kernel<double,min_plus>").
+struct S3Names {
+    const char *wide3, *band, *deep, *dec_i32_mark, *dec_i32, *dec_mark, *dec, *wide, *base;
+};
+#define PEM_S3_NAMES(VT, SFX)                                                                                                                  \
+    S3Names{"s3_accumulate_wide_kernel<" #VT ",deep,band" SFX ">", "s3_band_kernel<" #VT SFX ">", "s3_accumulate_wide_kernel<" #VT ",deep" SFX ">", \
+            "s3_accumulate_wide_kernel<" #VT ",decode,idx32,mark" SFX ">", "s3_accumulate_wide_kernel<" #VT ",decode,idx32" SFX ">",            \
+            "s3_accumulate_wide_kernel<" #VT ",decode,mark" SFX ">", "s3_accumulate_wide_kernel<" #VT ",decode" SFX ">",                        \
+            "s3_accumulate_wide_kernel<" #VT SFX ">", "s3_accumulate_kernel<" #VT SFX ">"}
+
+template <typename VT, typename SR>
+static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, bool idx32, bool mark, size_t s3_epw, int s3_xcd)
+{
+    const pem_tiled *A = p->A, *B = p->B;
+    const size_t ntc = (size_t)p->ntiles_c;
+    const bool wide = p->wide;   // step 2's choice: the entry-per-lane kernel needs the chunk index the fused path wrote
+#define PEM_S3_WIDE(DEEP, NAME)                                                                                                                \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, DEEP, false, false, false, false, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
+                     p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
+                     (long long)p->nnz_c, p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),       \
+                     A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
+                     p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
+#define PEM_S3_DECODE(I32, MK, NAME)                                                                                                           \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, false, false, true, I32, MK, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
+                     p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
+                     (long long)p->nnz_c, (const uint8_t *)nullptr, p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),           \
+                     A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
+                     p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
+    if (wide && deep && p->opt_band) {
+        PEM_LAUNCH_NAMED(ctx, nm.wide3, (s3_accumulate_wide_kernel<VT, true, true, false, false, false, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256,
+                         p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),
+                         (long long)p->nnz_c, p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),
+                         A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),
+                         p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd);
+        PEM_LAUNCH_NAMED(ctx, nm.band, (s3_band_kernel<VT, SR>), (grid_for(ntc, 256) + 7u) & ~7u, 256, p->pairs_offset.as<int>(),
+                         p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),
+                         p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),
+                         A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>());
+    } else if (wide && deep) {
+        PEM_S3_WIDE(true, nm.deep);
+    } else if (wide && p->s3_decode) {
+        // The semirings other than plus-times skip the IDX32 and MARK specialisations (code size and build time): their shallow
+        // plans always take the 64-bit, shuffle-search decode form.
+        if constexpr (std::is_same_v<SR, SrPlusTimes>) {
+            if (idx32 && mark)
+                PEM_S3_DECODE(true, true, nm.dec_i32_mark);
+            else if (idx32)
+                PEM_S3_DECODE(true, false, nm.dec_i32);
+            else if (mark)
+                PEM_S3_DECODE(false, true, nm.dec_mark);
+            else
+                PEM_S3_DECODE(false, false, nm.dec);
+        } else {
+            PEM_S3_DECODE(false, false, nm.dec);
+        }
+    } else if (wide) {
+        PEM_S3_WIDE(false, nm.wide);
+    } else {
+        PEM_LAUNCH_NAMED(ctx, nm.base, (s3_accumulate_kernel<VT, SR>), grid_for(ntc * 16, 256), 256, p->pairs_offset.as<int>(), p->pairs_a.as<int>(),
+                         p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(), p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(),
+                         A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(), A->masks.as<uint16_t>(), A->rowptr.as<uint8_t>(),
+                         B->tile_nnz_ptr.as<int>(), B->vals.as<VT>(), B->masks.as<uint16_t>(), B->rowptr.as<uint8_t>(), B->masks_t.as<uint16_t>());
+    }
+#undef PEM_S3_WIDE
+#undef PEM_S3_DECODE
 }
 
 pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
@@ -554,52 +647,7 @@ pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
     hipStream_t st = ctx->stream;
     const size_t ntc = (size_t)p->ntiles_c;
     if (!ctx->chain_events) PEM_HIP(hipEventRecord(ctx->ev[4], st));
-    const bool wide = p->wide;   // step 2's choice: the entry-per-lane kernel needs the chunk index the fused path wrote
     const bool f32 = A->value_bytes == 4;
-#define PEM_S3_WIDE(VT, DEEP, NAME)                                                                                                            \
-    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, DEEP>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256,     \
-                     p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
-                     (long long)p->nnz_c, p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),       \
-                     A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
-                     p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
-#define PEM_S3_DECODE(VT, I32, MK, NAME)                                                                                                       \
-    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, false, false, true, I32, MK>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
-                     p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
-                     (long long)p->nnz_c, (const uint8_t *)nullptr, p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),           \
-                     A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
-                     p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
-#define PEM_S3_WIDE3(VT, NAME)                                                                                                                 \
-    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, true, true>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
-                     p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
-                     (long long)p->nnz_c, p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),       \
-                     A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
-                     p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
-#define PEM_S3_LAUNCH(VT)                                                                                                                      \
-    do {                                                                                                                                       \
-        if (wide && deep && p->opt_band) {                                                                                                     \
-            PEM_S3_WIDE3(VT, "s3_accumulate_wide_kernel<" #VT ",deep,band>");                                                                  \
-            PEM_LAUNCH_NAMED(ctx, "s3_band_kernel<" #VT ">", (s3_band_kernel<VT>), (grid_for(ntc, 256) + 7u) & ~7u, 256, p->pairs_offset.as<int>(),         \
-                             p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),                          \
-                             p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),                    \
-                             A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>());         \
-        } else if (wide && deep)                                                                                                               \
-            PEM_S3_WIDE(VT, true, "s3_accumulate_wide_kernel<" #VT ",deep>");                                                                  \
-        else if (wide && p->s3_decode && idx32 && mark)                                                                                        \
-            PEM_S3_DECODE(VT, true, true, "s3_accumulate_wide_kernel<" #VT ",decode,idx32,mark>");                                             \
-        else if (wide && p->s3_decode && idx32)                                                                                                \
-            PEM_S3_DECODE(VT, true, false, "s3_accumulate_wide_kernel<" #VT ",decode,idx32>");                                                 \
-        else if (wide && p->s3_decode && mark)                                                                                                 \
-            PEM_S3_DECODE(VT, false, true, "s3_accumulate_wide_kernel<" #VT ",decode,mark>");                                                  \
-        else if (wide && p->s3_decode)                                                                                                         \
-            PEM_S3_DECODE(VT, false, false, "s3_accumulate_wide_kernel<" #VT ",decode>");                                                      \
-        else if (wide)                                                                                                                         \
-            PEM_S3_WIDE(VT, false, "s3_accumulate_wide_kernel<" #VT ">");                                                                      \
-        else                                                                                                                                   \
-            PEM_LAUNCH(ctx, s3_accumulate_kernel<VT>, grid_for(ntc * 16, 256), 256, p->pairs_offset.as<int>(), p->pairs_a.as<int>(),           \
-                       p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(), p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(),    \
-                       A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(), A->masks.as<uint16_t>(), A->rowptr.as<uint8_t>(),                          \
-                       B->tile_nnz_ptr.as<int>(), B->vals.as<VT>(), B->masks.as<uint16_t>(), B->rowptr.as<uint8_t>(), B->masks_t.as<uint16_t>()); \
-    } while (0)
     const bool deep = p->npairs >= 2 * p->ntiles_c;   // two or more pairs per C tile on average (see the kernel)
     // entries per wave: 256, or 512 where the C tiles hold 8+ entries on average (see the kernel; 562 / 534 / 536 / 574 us at 256 / 512 /
     // 1024 / 2048 on the round-3 webbase-1M stand-in); PEM_OPT_S3_EPW forces 256 * value
@@ -616,14 +664,20 @@ pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
                        vb * ((size_t)p->nnz_c + 1) < gib4;
     const bool mark = p->opt_mark && p->opt_prune && !p->M;
     const int s3_xcd = p->opt_s3_xcd;
-    if (ntc > 0 && f32)
-        PEM_S3_LAUNCH(float);
-    else if (ntc > 0)
-        PEM_S3_LAUNCH(double);
-#undef PEM_S3_LAUNCH
-#undef PEM_S3_WIDE
-#undef PEM_S3_WIDE3
-#undef PEM_S3_DECODE
+#define PEM_S3_SR(SRT, SFX)                                                                                                                    \
+    (f32 ? s3_launch<float, SRT>(ctx, p, PEM_S3_NAMES(float, SFX), deep, idx32, mark, s3_epw, s3_xcd)                                         \
+         : s3_launch<double, SRT>(ctx, p, PEM_S3_NAMES(double, SFX), deep, idx32, mark, s3_epw, s3_xcd))
+    if (ntc > 0) {
+        switch (p->semiring) {
+        case PEM_SEMIRING_MIN_PLUS: PEM_S3_SR(SrMinPlus, ",min_plus"); break;
+        case PEM_SEMIRING_MAX_PLUS: PEM_S3_SR(SrMaxPlus, ",max_plus"); break;
+        case PEM_SEMIRING_MAX_TIMES: PEM_S3_SR(SrMaxTimes, ",max_times"); break;
+        case PEM_SEMIRING_PLUS_PAIR: PEM_S3_SR(SrPlusPair, ",plus_pair"); break;
+        case PEM_SEMIRING_LOR_LAND: PEM_S3_SR(SrLorLand, ",lor_land"); break;
+        default: PEM_S3_SR(SrPlusTimes, ""); break;
+        }
+    }
+#undef PEM_S3_SR
     if (!ctx->capturing) PEM_HIP(hipEventRecord(ctx->ev[5], st));
     p->state = 3;
     return PEM_OK;

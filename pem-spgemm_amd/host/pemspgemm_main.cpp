@@ -333,10 +333,13 @@ int main(int argc, char *argv[])
     // `--chunks K` chunks per rank with the gather overlapped (default: K from C's size; 0: off).
     // `--mask <M.mtx>` computes the masked product C<M> = A*B: only the entries at M's stored positions (pem_cplan_create_masked);
     // with `--mask-complement` only those where M stores nothing.  M has C's shape; the flop count stays the unmasked product's.
+    // `--semiring NAME`: step 3 reduces under plus_times (default), min_plus, max_plus, max_times,
+    // plus_pair or lor_land; C's structure, the flop count (the tile product's) and the CSV columns do not change.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
     bool mask_complement = false;
+    const char *semiring_name = nullptr;
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -354,6 +357,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--fp32")) fp32 = true;
             else if (!strcmp(argv[r], "--mask") && r + 1 < argc) mask_path = argv[++r];
             else if (!strcmp(argv[r], "--mask-complement")) mask_complement = true;
+            else if (!strcmp(argv[r], "--semiring") && r + 1 < argc) semiring_name = argv[++r];
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -379,6 +383,21 @@ int main(int argc, char *argv[])
 
     if (mask_complement && !mask_path) {
         printf("--mask-complement needs --mask <M.mtx>. Exiting.\n");
+        return 1;
+    }
+    static const char *const semiring_names[] = {"plus_times", "min_plus", "max_plus", "max_times", "plus_pair", "lor_land"};   // pem_semiring
+    int semiring = PEM_SEMIRING_PLUS_TIMES;
+    if (semiring_name) {
+        semiring = -1;
+        for (int i = 0; i < 6; ++i)
+            if (!strcmp(semiring_name, semiring_names[i])) semiring = i;
+        if (semiring < 0) {
+            printf("--semiring %s: unknown semiring (plus_times, min_plus, max_plus, max_times, plus_pair, lor_land). Exiting.\n", semiring_name);
+            return 1;
+        }
+    }
+    if (ngpu > 0 && semiring != PEM_SEMIRING_PLUS_TIMES) {
+        printf("--gpus does not combine with --semiring %s (the multi-GPU path multiplies under plus_times). Exiting.\n", semiring_names[semiring]);
         return 1;
     }
     if (ngpu > 0 && mask_path) {
@@ -593,6 +612,7 @@ int main(int argc, char *argv[])
         CHECK(pem_cplan_create_masked(ctx, A, B, Mt, mask_complement ? PEM_MASK_COMPLEMENT : PEM_MASK_STRUCTURE, 0, -1, &plan));
     else
         CHECK(pem_cplan_create(ctx, A, B, 0, -1, &plan));
+    CHECK(pem_cplan_set_semiring(plan, semiring));
     std::vector<double> s1, s2, s3, wall;
     double cold_ms = 0.0;   // the first pass on the plan: every allocation + the three size read-backs (what the reference pays per iteration)
     for (int n = 0; n < WARMUP + REPEAT; ++n) {   // spgemm.cu:1133-1357
@@ -640,6 +660,8 @@ int main(int argc, char *argv[])
     printf("first pass (allocations + size read-backs) %.2fms; the passes above re-use the plan's buffers and sizes\n", cold_ms);
     printf("Flop count: %llu\n\n", (unsigned long long)flop);
     if (Mt) printf("masked product C<%sM>: the flop count and GFlops above count the unmasked product A*B\n", mask_complement ? "!" : "");
+    if (semiring != PEM_SEMIRING_PLUS_TIMES)
+        printf("semiring %s: step 3 reduced under it; the flop count and GFlops above count the tile product's multiply-adds\n", semiring_names[semiring]);
     printf("C tiles: %lld\n", (long long)ci.ntiles_c);
     printf("C nnz: %lld\n", (long long)ci.nnz_c);
     printf("Compression ratio %.2f\n", ratio);
@@ -698,7 +720,9 @@ int main(int argc, char *argv[])
         } else {
             CHECK(pem_c_export_csr(ctx, plan, &nnz, rp.data(), cidx.data(), cv.data()));
         }
-        if (pem_write_mtx_csr(out_path, ia.rows, ib.cols, rp.data(), cidx.data(), cv.data(), "C = A*B by pemspgemm (pem-spgemm_amd)") != 0) {
+        const std::string comment = semiring == PEM_SEMIRING_PLUS_TIMES ? std::string("C = A*B by pemspgemm (pem-spgemm_amd)")
+                                                                         : std::string("C = A*B over the ") + semiring_names[semiring] + " semiring by pemspgemm (pem-spgemm_amd)";
+        if (pem_write_mtx_csr(out_path, ia.rows, ib.cols, rp.data(), cidx.data(), cv.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
             rc = 2;
         } else {
