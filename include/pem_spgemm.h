@@ -236,6 +236,28 @@ typedef enum {
 pem_status pem_cplan_set_semiring(pem_cplan *plan, int semiring);
 pem_status pem_cplan_get_semiring(const pem_cplan *plan, int *semiring);
 
+/* Chained products: the C of a plan as the operand of the next product, built on the device from the
+ * plan's tiled result -- no export, no host round trip, no entry-level sort.
+ *   pem_tiled_from_cplan  a new tiling of C (transpose = 0: A.rows x B.cols) or of C^T (transpose = 1: B.cols x A.rows).  The shape
+ *       is the full one also for a plan over a tile-row range: the tile rows outside the range are empty (for C^T, those tile
+ *       columns), so a row block stays a row block under right multiplication.  The tiling holds exactly the stored entries of C
+ *       (the symbolic product, entries that cancel included, as the exports); values are copied bit for bit in C's value type.  It
+ *       equals, array for array, the tiling pem_tiled_from_csr builds from pem_c_export_csr of the same plan (with transpose = 1:
+ *       pem_tiled_from_coo(..., transpose = 1) of the exported COO); C tiles without entries (PEM_OPT_PRUNE = 0, masked plans) are
+ *       dropped.  The plan must have completed step 3 with current values (the rule of the exports): PEM_E_STATE before step 3,
+ *       after a refresh of A or B or after pem_cplan_set_semiring.  A null argument or transpose not 0/1: PEM_E_INVALID.  An empty
+ *       C gives a valid tiling with nnz = 0.  The tiling owns its arrays: the plan may be destroyed, re-run or re-optioned after.
+ *       It works everywhere a tiling does (A, B, mask, save / load, set_values*, flop count, split).
+ *   pem_tiled_set_values_from_cplan  the plan's current C values into such a tiling's vals and vals_t, in place; bumps its value
+ *       version (plans built on it turn stale under the rule of pem_tiled_set_values until their step 3 runs).  Stream-ordered, never
+ *       waits, reads nothing back.  PEM_E_INVALID if t was not made from this plan (every plan carries a process-wide serial the
+ *       tiling records) or the plan's nnz differs from t's; PEM_E_STATE if the plan's C is not current.  C's value order does not
+ *       depend on the plan's options or semiring, so the refresh stays valid after pem_cplan_set_option / set_semiring once step 3
+ *       has run again.  A C^T tiling builds an int32 map per entry on its first refresh (4 bytes per entry, kept with the tiling);
+ *       that and the vals_t map of pem_tiled_set_values are arena allocations, which make a captured graph re-capture once. */
+pem_status pem_tiled_from_cplan(pem_ctx *ctx, const pem_cplan *plan, int transpose, pem_tiled **out);
+pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t, const pem_cplan *plan);
+
 /* Plan options.  A new plan takes its defaults from the environment once, in pem_cplan_create (PEM_PRUNE=0, PEM_STEP1=esc,
  * PEM_WIDE=0, PEM_NO_WARM=1, PEM_S3_BAND=0, PEM_EXPORT=rows); after that only pem_cplan_set_option changes them -- no entry
  * point reads the environment at call time.  Changing an option sends the plan back to the last step the option does not touch

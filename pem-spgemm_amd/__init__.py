@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "pem_ctx_reserve", "pem_ctx_trim", "pem_ctx_memory_stats", "pem_cplan_set_option", "pem_cplan_get_option", "pem_debug_scan_i32",
     "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
     "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
+    "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan",
 ]
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
@@ -279,6 +280,20 @@ class Tiled:
             dV = dV.data_ptr()
         fn = lib().pem_tiled_set_values_device_f32 if self.value_bytes == 4 else lib().pem_tiled_set_values_device
         _check(fn(self.ctx._h, self._h, C.c_void_p(int(dV)), self._order(order)))
+
+    @classmethod
+    def from_cplan(cls, plan, transpose=False):
+        """Chained products: the C of `plan` (or C^T) as a new tiling built on the device, the same
+        arrays as from_csr of plan.export_csr(), in C's dtype.  The plan must have run step 3 with current values; the tiling owns its
+        arrays and outlives the plan."""
+        h = C.c_void_p()
+        _check(lib().pem_tiled_from_cplan(plan.ctx._h, plan._h, int(transpose) if transpose in (0, 1) else -1, C.byref(h)))
+        return cls(plan.ctx, h)
+
+    def set_values_from_cplan(self, plan):
+        """Refresh a tiling made by from_cplan(plan) with the plan's current C values, in place (after the plan's step 3 ran on new
+        operand values).  Ordered on the context's stream; returns without waiting."""
+        _check(lib().pem_tiled_set_values_from_cplan(self.ctx._h, self._h, plan._h))
 
     def save(self, path, key=None):
         """Write the sorted tile payload to a cache file."""

@@ -7,6 +7,7 @@
 // then fall out of the sorted keys with wave64 ballots / 16-lane scans.  The arrays produced
 // are bit-identical to the reference's (layouts in include/pem_spgemm.h).
 #include "pem_internal.h"
+#include "tiled_internal.h"
 #include <chrono>
 #include <cerrno>
 #include <cstdio>
@@ -453,7 +454,7 @@ extern "C" pem_status pem_kernel_stats_get(pem_ctx *ctx, int idx, char *name, in
 // conversion driver
 // ------------------------------------------------------------------------------------------
 // sizing phase "tiles": every per-tile array of a tiling (and the small sort of its tile CSC) in one driver allocation
-static pem_status reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T)
+pem_status pem::reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T)
 {
     const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
     return arena_phase(ctx->arena,
@@ -468,9 +469,9 @@ static pem_status reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T)
 
 // Everything that follows from the sorted tile payload (tile_keys, tile_nnz_ptr, rowcolidx, vals): masks, intra-tile
 // row pointers, transposed masks (a5/a6), the step-3 records, the column-major values and the tile-level CSR/CSC
-// indices (a7).  Shared by the conversion and by the cache loader.  headx = exclusive scan of the tile-head flags;
+// indices (a7).  Shared by the conversion, the cache loader and the tilings made from a plan's C (chain.hip).  headx = exclusive scan of the tile-head flags;
 // ctx->ev[6] was recorded by the caller where its payload kernels start.
-static pem_status derive_tiled(pem_ctx *ctx, pem_tiled *T, const int *headx, int bits_tr, int bits_tc)
+pem_status pem::derive_tiled(pem_ctx *ctx, pem_tiled *T, const int *headx, int bits_tr, int bits_tc)
 {
     const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
     const int64_t ntiles = T->ntiles;

@@ -309,10 +309,17 @@ struct pem_tiled {
     pem::DevBuf vmap_t;               // int32[nnz]: for every entry in tile order, its slot in vals_t
     bool vmap_ready[2] = {false, false}, vmap_t_ready = false;
     uint64_t value_version = 0;       // bumped by every refresh; a plan's C is current while it equals what step 3 read
+    // a tiling made from a plan's C (chain.hip, pem_tiled_from_cplan): the plan's serial (0: not made from a plan), whether it
+    // holds C^T, and for C^T the int32[nnz] map from every entry to its value's position in the plan's c_vals (first refresh)
+    uint64_t src_plan_serial = 0;
+    int src_transpose = 0;
+    pem::DevBuf cmap;
+    bool cmap_ready = false;
 };
 
 struct pem_cplan {
     const pem_tiled *A = nullptr, *B = nullptr;
+    uint64_t serial = 0;               // process-wide, unique per plan created (never 0): what a tiling made from C records
     // masked plan (pem_cplan_create_masked, mask.hip): C<M> = A*B.  Step 1 ends with a filter of its lists by M's tile set, step 2
     // ANDs every C tile's mask with M's tile there (or its complement); nothing after that knows about the mask
     const pem_tiled *M = nullptr;

@@ -50,7 +50,9 @@ extern "C" pem_status pem_cplan_create(pem_ctx *ctx, const pem_tiled *A, const p
         set_error("pem_cplan_create: tile-row range [%d, %d) outside [0, %d]", tr_lo, tr_hi, A->tile_rows);
         return PEM_E_INVALID;
     }
+    static std::atomic<uint64_t> s_plan_serial{0};
     pem_cplan *p = new pem_cplan();
+    p->serial = ++s_plan_serial;
     p->owner = ctx;
     p->A = A;
     p->B = B;

@@ -20,6 +20,7 @@
 // vmap_t's 4 bytes but read ~100 bytes of records per TILE and idle most lanes on the sparse tiles of web graphs (a few
 // entries per tile); the entry-parallel kernel's traffic does not depend on how full the tiles are.
 #include "spgemm_internal.h"
+#include "tiled_internal.h"
 
 using namespace pem;
 
@@ -140,16 +141,22 @@ __global__ void __launch_bounds__(256) vals_refresh_kernel(const VT *__restrict_
 // host side
 // ------------------------------------------------------------------------------------------
 // The maps of one order (and vmap_t) on the first refresh that needs them.  Everything stays on the stream: no read-back.
+pem_status pem::ensure_vmap_t(pem_ctx *ctx, pem_tiled *T)
+{
+    if (T->vmap_t_ready) return PEM_OK;
+    const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
+    PEM_TRY(T->vmap_t.reserve(sizeof(int) * (nnz + 4)));
+    PEM_LAUNCH(ctx, vmap_t_kernel, grid_for(16 * nt, 256), 256, T->tile_rec.as<uint32_t>(), T->tile_rec_t.as<uint32_t>(), T->tile_nnz_ptr.as<int>(),
+               (long long)nt, T->vmap_t.as<int>());
+    T->vmap_t_ready = true;
+    return PEM_OK;
+}
+
 static pem_status ensure_maps(pem_ctx *ctx, pem_tiled *T, int order)
 {
     const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
     const unsigned grid = grid_for(16 * nt, 256);
-    if (!T->vmap_t_ready) {
-        PEM_TRY(T->vmap_t.reserve(sizeof(int) * (nnz + 4)));
-        PEM_LAUNCH(ctx, vmap_t_kernel, grid, 256, T->tile_rec.as<uint32_t>(), T->tile_rec_t.as<uint32_t>(), T->tile_nnz_ptr.as<int>(),
-                   (long long)nt, T->vmap_t.as<int>());
-        T->vmap_t_ready = true;
-    }
+    PEM_TRY(ensure_vmap_t(ctx, T));
     if (T->vmap_ready[order]) return PEM_OK;
     DevBuf slots;   // (tile row, local row, tile) resp. (tile column, local column, tile) populations -> their exclusive scan
     PEM_TRY(arena_phase(ctx->arena, {{&T->vmap[order], sizeof(int) * (nnz + 4)}, {&slots, sizeof(int) * (16 * nt + 4)}}));

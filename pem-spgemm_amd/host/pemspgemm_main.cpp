@@ -335,11 +335,14 @@ int main(int argc, char *argv[])
     // with `--mask-complement` only those where M stores nothing.  M has C's shape; the flop count stays the unmasked product's.
     // `--semiring NAME`: step 3 reduces under plus_times (default), min_plus, max_plus, max_times,
     // plus_pair or lor_land; C's structure, the flop count (the tile product's) and the CSV columns do not change.
+    // `--power K` computes A^K = (...(A*A)*A...)*A as K-1 products, every C turned into the next left
+    // operand on the device; with --semiring every product uses it.  The report and the CSV row describe the last product.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
     bool mask_complement = false;
     const char *semiring_name = nullptr;
+    int power = 0;   // --power K: A^K as K-1 chained products (0: off)
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -358,6 +361,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--mask") && r + 1 < argc) mask_path = argv[++r];
             else if (!strcmp(argv[r], "--mask-complement")) mask_complement = true;
             else if (!strcmp(argv[r], "--semiring") && r + 1 < argc) semiring_name = argv[++r];
+            else if (!strcmp(argv[r], "--power") && r + 1 < argc) power = atoi(argv[++r]);
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -399,6 +403,16 @@ int main(int argc, char *argv[])
     if (ngpu > 0 && semiring != PEM_SEMIRING_PLUS_TIMES) {
         printf("--gpus does not combine with --semiring %s (the multi-GPU path multiplies under plus_times). Exiting.\n", semiring_names[semiring]);
         return 1;
+    }
+    if (power != 0) {
+        const char *clash = power < 2 ? "K >= 2" : ngpu > 0 ? "--gpus" : mask_path ? "--mask" : b_path ? "--B" : aat ? "the A*A^T argument" : nullptr;
+        if (clash) {
+            if (power < 2)
+                printf("--power %d: K must be at least 2. Exiting.\n", power);
+            else
+                printf("--power does not combine with %s (A^K multiplies A by itself on one device). Exiting.\n", clash);
+            return 1;
+        }
     }
     if (ngpu > 0 && mask_path) {
         printf("--gpus does not combine with --mask (masked products run on one device). Exiting.\n");
@@ -603,15 +617,42 @@ int main(int argc, char *argv[])
     if (mask_path)
         printf("MASK%s\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", mask_complement ? " (complement)" : "", mask_path, cm.rows, cm.cols,
                (long long)cm.nnz);
-    const double conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - conv_start).count();
+    double conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - conv_start).count();
+    // --power K: the first K-2 products run once each; every C becomes the next left operand on the device (pem_tiled_from_cplan),
+    // the right operand is always A.  The timed product below is the last one, L * A; its conversion column adds the derived ones.
+    pem_tiled *L = A;
+    for (int k = 2; k < power; ++k) {
+        uint64_t f = 0;
+        CHECK(pem_flop_count(ctx, L, A, &f));
+        pem_cplan *p = nullptr;
+        CHECK(pem_cplan_create(ctx, L, A, 0, -1, &p));
+        CHECK(pem_cplan_set_semiring(p, semiring));
+        CHECK(pem_spgemm(ctx, p));
+        pem_timings t;
+        CHECK(pem_get_timings(ctx, &t));
+        pem_tiled *next = nullptr;
+        CHECK(pem_tiled_from_cplan(ctx, p, 0, &next));
+        pem_cplan_info pi;
+        pem_tiled_info ni;
+        CHECK(pem_cplan_get_info(p, &pi));
+        CHECK(pem_tiled_get_info(next, &ni));
+        printf("power: A^%d = A^%d * A: flop %llu, C nnz %lld, pass %.2fms, C -> operand %.2fms\n", k, k - 1, (unsigned long long)f,
+               (long long)pi.nnz_c, t.spgemm_wall_ms, ni.conv_ms);
+        conv_ms += ni.conv_ms;
+        pem_cplan_destroy(ctx, p);
+        if (L != A) pem_tiled_destroy(ctx, L);
+        L = next;
+    }
+    pem_tiled_info il;
+    CHECK(pem_tiled_get_info(L, &il));
     uint64_t flop = 0;
-    CHECK(pem_flop_count(ctx, A, B, &flop));   // spgemm.cu:1068-1079
+    CHECK(pem_flop_count(ctx, L, B, &flop));   // spgemm.cu:1068-1079
 
     pem_cplan *plan = nullptr;
     if (Mt)
         CHECK(pem_cplan_create_masked(ctx, A, B, Mt, mask_complement ? PEM_MASK_COMPLEMENT : PEM_MASK_STRUCTURE, 0, -1, &plan));
     else
-        CHECK(pem_cplan_create(ctx, A, B, 0, -1, &plan));
+        CHECK(pem_cplan_create(ctx, L, B, 0, -1, &plan));
     CHECK(pem_cplan_set_semiring(plan, semiring));
     std::vector<double> s1, s2, s3, wall;
     double cold_ms = 0.0;   // the first pass on the plan: every allocation + the three size read-backs (what the reference pays per iteration)
@@ -664,9 +705,11 @@ int main(int argc, char *argv[])
         printf("semiring %s: step 3 reduced under it; the flop count and GFlops above count the tile product's multiply-adds\n", semiring_names[semiring]);
     printf("C tiles: %lld\n", (long long)ci.ntiles_c);
     printf("C nnz: %lld\n", (long long)ci.nnz_c);
+    if (power >= 2)
+        printf("power: A^%d = A^%d * A: flop %llu, C nnz %lld, pass %.2fms\n", power, power - 1, (unsigned long long)flop, (long long)ci.nnz_c, total);
     printf("Compression ratio %.2f\n", ratio);
     // roofline bookkeeping
-    const double b_alg = 12.0 * ((double)ia.nnz + (double)ib.nnz + (double)ci.nnz_c) + 4.0 * ((double)ia.rows + 1) + 4.0 * ((double)ib.rows + 1) +
+    const double b_alg = 12.0 * ((double)il.nnz + (double)ib.nnz + (double)ci.nnz_c) + 4.0 * ((double)ia.rows + 1) + 4.0 * ((double)ib.rows + 1) +
                          4.0 * ((double)ia.rows + 1);
     const double frac_kernel = kernel > 0 ? b_alg / (kernel * 1e-3) / 8.0e12 : 0.0, frac_total = total > 0 ? b_alg / (total * 1e-3) / 8.0e12 : 0.0;
     printf("B_alg %.0f bytes; HBM roofline fraction (8 TB/s): kernel %.4f, total %.4f\n", b_alg, frac_kernel, frac_total);
@@ -731,6 +774,7 @@ int main(int argc, char *argv[])
     }
     printf("CLEANING UP RESOURCES\n\n");
     pem_cplan_destroy(ctx, plan);
+    if (L != A) pem_tiled_destroy(ctx, L);
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
     if (B != A) pem_tiled_destroy(ctx, B);
