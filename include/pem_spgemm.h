@@ -258,6 +258,49 @@ pem_status pem_cplan_get_semiring(const pem_cplan *plan, int *semiring);
 pem_status pem_tiled_from_cplan(pem_ctx *ctx, const pem_cplan *plan, int transpose, pem_tiled **out);
 pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t, const pem_cplan *plan);
 
+/* Element-wise combination of two tilings: with pem_tiled_from_cplan, C = alpha*A*B + beta*D and its
+ * semiring forms stay on the device.
+ *   pem_tiled_ewise  a new tiling R of A's shape and value type, owning its arrays, from A and B.  A and B must have the same rows x
+ *       cols and value type; they may be the same handle, and either may be a tiling built with transpose = 1 (it is the tiling of its
+ *       own matrix).  R works everywhere a tiling does (A, B, mask, save / load, set_values*, flop count, split).
+ *     Pattern.  PEM_EWISE_UNION: every position stored in A or in B.  PEM_EWISE_INTERSECT: every position stored in both.  Explicit
+ *       zeros and results that come out as 0 stay entries (the rule of sections 3f / 3g); tiles an intersection leaves without entries
+ *       are not in R (1..256 entries per tile).
+ *     Values, in the value type T, no fma and no wider intermediate.  a' = a if alpha == 1, else (T)alpha * a rounded once; b' from
+ *       beta alike (alpha = beta = 1 copies the values bit for bit).  Where both are stored: op(a', b') --
+ *         PEM_BINOP_PLUS a' + b', PEM_BINOP_TIMES a' * b' (each rounded once);
+ *         PEM_BINOP_MIN / PEM_BINOP_MAX: C's fmin / fmax (a NaN side is skipped; the sign of a zero result is not specified);
+ *         PEM_BINOP_LOR: 1 if a' != 0 || b' != 0, else 0;  PEM_BINOP_LAND: 1 if a' != 0 && b' != 0, else 0  (NaN counts as != 0).
+ *       Where only one is stored (UNION only): a' or b' unchanged, whatever the op (GraphBLAS eWiseAdd).  A NaN that arithmetic
+ *       produces has an unspecified payload.
+ *     PEM_E_INVALID: a null argument, an unknown pattern or op, different shapes or different value types.  Empty operands or an empty
+ *       intersection give a valid tiling with nnz = 0.  A's and B's values are read as they are when the call is made (stream order);
+ *       the call waits, like pem_tiled_from_cplan, and its allocations come from the context's arena (a captured graph re-captures).
+ *       Besides the tiling's own arrays R keeps 8 bytes per tile of R (the A and B tiles each of its tiles comes from) for the refresh.
+ *   pem_tiled_set_values_from_ewise  recomputes t's values (vals and vals_t) in place from the current values of A and B, as
+ *       pem_tiled_ewise would, and bumps t's value version.  Stream-ordered, never waits, reads nothing back; only the first call
+ *       allocates (an int32 pair per entry: where its operand values sit in A and B).  PEM_E_INVALID unless t was made by
+ *       pem_tiled_ewise from exactly this A and this B in this order: every tiling carries a process-wide serial, and t records both
+ *       operands' (swapped operands, or a tiling recreated at a reused address, are refused). */
+typedef enum { PEM_EWISE_UNION = 0, PEM_EWISE_INTERSECT = 1 } pem_ewise_pattern;
+typedef enum {
+    PEM_BINOP_PLUS = 0,
+    PEM_BINOP_TIMES = 1,
+    PEM_BINOP_MIN = 2,
+    PEM_BINOP_MAX = 3,
+    PEM_BINOP_LOR = 4,
+    PEM_BINOP_LAND = 5
+} pem_binop;
+pem_status pem_tiled_ewise(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int pattern, int op, double alpha, double beta,
+                           pem_tiled **out);
+pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B);
+
+/* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
+ * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
+ * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */
+pem_status pem_tiled_export_csr(pem_ctx *ctx, const pem_tiled *t, int64_t *nnz, int32_t *rowptr, int32_t *colidx, double *vals);
+pem_status pem_tiled_export_csr_f32(pem_ctx *ctx, const pem_tiled *t, int64_t *nnz, int32_t *rowptr, int32_t *colidx, float *vals);
+
 /* Plan options.  A new plan takes its defaults from the environment once, in pem_cplan_create (PEM_PRUNE=0, PEM_STEP1=esc,
  * PEM_WIDE=0, PEM_NO_WARM=1, PEM_S3_BAND=0, PEM_EXPORT=rows); after that only pem_cplan_set_option changes them -- no entry
  * point reads the environment at call time.  Changing an option sends the plan back to the last step the option does not touch

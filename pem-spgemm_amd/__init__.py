@@ -48,8 +48,13 @@ ABI_SYMBOLS = [
     "pem_ctx_reserve", "pem_ctx_trim", "pem_ctx_memory_stats", "pem_cplan_set_option", "pem_cplan_get_option", "pem_debug_scan_i32",
     "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
     "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
-    "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan",
+    "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan", "pem_tiled_ewise", "pem_tiled_set_values_from_ewise",
+    "pem_tiled_export_csr", "pem_tiled_export_csr_f32",
 ]
+
+# enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
+EWISE_PATTERNS = dict(union=0, intersect=1)
+BINOPS = dict(plus=0, times=1, min=2, max=3, lor=4, land=5)
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
 VALUE_ORDERS = dict(row=0, col=1)
@@ -294,6 +299,33 @@ class Tiled:
         """Refresh a tiling made by from_cplan(plan) with the plan's current C values, in place (after the plan's step 3 ran on new
         operand values).  Ordered on the context's stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_cplan(self.ctx._h, self._h, plan._h))
+
+    @classmethod
+    def ewise(cls, A, B, op="plus", pattern="union", alpha=1.0, beta=1.0):
+        """Element-wise combination: a new tiling of A's shape and dtype holding op(alpha*a, beta*b) on the
+        union (or intersection) of A's and B's patterns; where only one side is stored (union), that side's scaled value.  op: one of
+        BINOPS, pattern: one of EWISE_PATTERNS.  Waits."""
+        if op not in BINOPS:
+            raise ValueError(f"unknown op {op!r}; one of {sorted(BINOPS)}")
+        if pattern not in EWISE_PATTERNS:
+            raise ValueError(f"unknown pattern {pattern!r}; one of {sorted(EWISE_PATTERNS)}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_ewise(A.ctx._h, A._h, B._h, EWISE_PATTERNS[pattern], BINOPS[op], C.c_double(alpha), C.c_double(beta), C.byref(h)))
+        return cls(A.ctx, h)
+
+    def set_values_from_ewise(self, A, B):
+        """Refresh a tiling made by ewise(A, B, ...) from A's and B's current values, in place.  Ordered on the context's stream;
+        returns without waiting."""
+        _check(lib().pem_tiled_set_values_from_ewise(self.ctx._h, self._h, A._h, B._h))
+
+    def export_csr(self):
+        """(rowptr int32[rows + 1], colidx int32[nnz], vals[nnz] in the tiling's dtype): the tiled matrix as canonical CSR."""
+        f32 = self.value_bytes == 4
+        rp, ci, v = np.zeros(self.rows + 1, np.int32), np.zeros(self.nnz, np.int32), np.zeros(self.nnz, self.dtype)
+        n = C.c_int64()
+        fn = lib().pem_tiled_export_csr_f32 if f32 else lib().pem_tiled_export_csr
+        _check(fn(self.ctx._h, self._h, C.byref(n), _p(rp, C.c_int32), _p(ci, C.c_int32), _p(v, C.c_float if f32 else C.c_double)))
+        return rp, ci, v
 
     def save(self, path, key=None):
         """Write the sorted tile payload to a cache file."""

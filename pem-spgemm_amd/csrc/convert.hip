@@ -994,6 +994,12 @@ extern "C" pem_status pem_tiled_load(pem_ctx *ctx, const char *path, const pem_c
     return PEM_OK;
 }
 
+uint64_t pem::next_tiled_serial()
+{
+    static std::atomic<uint64_t> s_tiled_serial{0};
+    return ++s_tiled_serial;
+}
+
 extern "C" pem_status pem_tiled_destroy(pem_ctx *ctx, pem_tiled *t)
 {
     // the tiling's blocks go back to the arena and may be handed out again at once: whatever still reads them must be done

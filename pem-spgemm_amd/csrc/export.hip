@@ -94,29 +94,55 @@ __device__ __forceinline__ void ex_pack_counts(const uint4 M0, const uint4 M1, u
                ((unsigned long long)__popc(w[2 * j + 1] >> 16) << 32) | ((unsigned long long)__popc(w[2 * j + 1] & 0xFFFFu) << 48);
 }
 
+// The balanced kernels below read the masks of a plan's C (PEM_C_MASK: uint32[8T], word q = (row 2q) << 16 | row 2q+1) or, with
+// TILED, a tiling's (PEM_T_MASKS: uint16[16T] by row, so its 32-bit word q is row 2q | row 2q+1 << 16).  ex_mask4 turns half h of
+// tile t's masks into the plan's layout; everything after it is one copy of the logic.  The __global__ kernels of the plan export
+// keep their names and instantiate the bodies with TILED = false; the _tiled kernels serve pem_tiled_export_csr.
+template <bool TILED>
+__device__ __forceinline__ uint4 ex_mask4(const uint32_t *mask, long long t, int h)
+{
+    uint4 v = *reinterpret_cast<const uint4 *>(mask + 8 * t + 4 * h);
+    if constexpr (TILED) {
+        v.x = (v.x << 16) | (v.x >> 16);
+        v.y = (v.y << 16) | (v.y >> 16);
+        v.z = (v.z << 16) | (v.z >> 16);
+        v.w = (v.w << 16) | (v.w >> 16);
+    }
+    return v;
+}
+
+// (a macro, not a device function: inlining a function with an early return lays the plan kernel's blocks out differently)
+#define EX_CHUNKHIST_BODY(TILED)                                                                                               \
+    const int lane = threadIdx.x & 63;                                                                                         \
+    const int ch = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;                                                               \
+    if (ch >= chunkptr[mt]) return; /* (the grid covers the host's bound on the number of chunks) */                           \
+    const int i = chunk_row[ch];                                                                                               \
+    const int t0 = c_tile_rowptr[i] + ((ch - chunkptr[i]) << 6);                                                               \
+    const int ntl = c_tile_rowptr[i + 1] - t0 < 64 ? c_tile_rowptr[i + 1] - t0 : 64;                                           \
+    unsigned long long pk[4] = {0, 0, 0, 0};                                                                                   \
+    if (lane < ntl) {                                                                                                          \
+        const long long t = t0 + lane;                                                                                         \
+        ex_pack_counts(ex_mask4<TILED>(c_mask, t, 0), ex_mask4<TILED>(c_mask, t, 1), pk);                                      \
+    }                                                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                              \
+        _Pragma("unroll") for (int d = 32; d > 0; d >>= 1) pk[j] += __shfl_xor(pk[j], d, 64);                                  \
+    if (lane < 16) {                                                                                                           \
+        const unsigned long long sel = (lane >> 2) == 0 ? pk[0] : (lane >> 2) == 1 ? pk[1] : (lane >> 2) == 2 ? pk[2] : pk[3]; \
+        chunkhist[16 * (size_t)ch + lane] = (int)((sel >> (16 * (lane & 3))) & 0xFFFFull);                                     \
+    }
+
 __global__ void __launch_bounds__(256) ex_chunkhist_kernel(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
                                                            const int *__restrict__ c_tile_rowptr, const uint32_t *__restrict__ c_mask,
                                                            int *__restrict__ chunkhist)
 {
-    const int lane = threadIdx.x & 63;
-    const int ch = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (ch >= chunkptr[mt]) return;        // (the grid covers the host's bound on the number of chunks)
-    const int i = chunk_row[ch];
-    const int t0 = c_tile_rowptr[i] + ((ch - chunkptr[i]) << 6);
-    const int ntl = c_tile_rowptr[i + 1] - t0 < 64 ? c_tile_rowptr[i + 1] - t0 : 64;
-    unsigned long long pk[4] = {0, 0, 0, 0};
-    if (lane < ntl) {
-        const long long t = t0 + lane;
-        ex_pack_counts(*reinterpret_cast<const uint4 *>(c_mask + 8 * t), *reinterpret_cast<const uint4 *>(c_mask + 8 * t + 4), pk);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) pk[j] += __shfl_xor(pk[j], d, 64);
-    if (lane < 16) {
-        const unsigned long long sel = (lane >> 2) == 0 ? pk[0] : (lane >> 2) == 1 ? pk[1] : (lane >> 2) == 2 ? pk[2] : pk[3];
-        chunkhist[16 * (size_t)ch + lane] = (int)((sel >> (16 * (lane & 3))) & 0xFFFFull);
-    }
+    EX_CHUNKHIST_BODY(false)
+}
+
+__global__ void __launch_bounds__(256) ex_chunkhist_tiled_kernel(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
+                                                                 const int *__restrict__ c_tile_rowptr, const uint32_t *__restrict__ c_mask,
+                                                                 int *__restrict__ chunkhist)
+{
+    EX_CHUNKHIST_BODY(true)
 }
 
 // one wave per tile row, lane = (chunk of the trip c4, row r): counts -> exclusive bases inside the tile row (in place), and
@@ -153,16 +179,17 @@ __global__ void __launch_bounds__(256) ex_chunkscan_kernel(const int *__restrict
     if (i == mt - 1 && lane == 15) rowptr[nrows] = seg + pre;       // closing entry = C_nnz of the slice
 }
 
-template <typename VT>
-__global__ void __launch_bounds__(256) ex_chunkfill_kernel(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
-                                                           const int *__restrict__ c_tile_rowptr, const int *__restrict__ c_tile_colidx,
-                                                           const uint32_t *__restrict__ c_mask, const int *__restrict__ c_tile_nnz_ptr,
-                                                           const VT *__restrict__ c_vals, const int *__restrict__ chunkbase,
-                                                           const int *__restrict__ rowptr, int *__restrict__ colidx, VT *__restrict__ vals)
+// s_rp: uint4[4 * 64]   [wave][tile] prefix counts of the tile's rows, a byte each
+// s_ex: uint4[4 * 64 * 2] [wave][tile] entries of row r in the chunk's earlier tiles, 16 bits each
+// s_mw: unsigned[4 * 8 * 64] [wave][word q][tile]
+template <typename VT, bool TILED>
+__device__ __forceinline__ void ex_chunkfill(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
+                                             const int *__restrict__ c_tile_rowptr, const int *__restrict__ c_tile_colidx,
+                                             const uint32_t *__restrict__ c_mask, const int *__restrict__ c_tile_nnz_ptr,
+                                             const VT *__restrict__ c_vals, const int *__restrict__ chunkbase,
+                                             const int *__restrict__ rowptr, int *__restrict__ colidx, VT *__restrict__ vals, uint4 *s_rp,
+                                             uint4 *s_ex, unsigned *s_mw)
 {
-    __shared__ __attribute__((aligned(16))) uint4 s_rp[4 * 64];            // [wave][tile] prefix counts of the tile's rows, a byte each
-    __shared__ __attribute__((aligned(16))) uint4 s_ex[4 * 64 * 2];        // [wave][tile] entries of row r in the chunk's earlier tiles, 16 bits each
-    __shared__ unsigned s_mw[4 * 8 * 64];                                  // [wave][word q][tile]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ch = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (ch >= chunkptr[mt]) return;
@@ -176,8 +203,8 @@ __global__ void __launch_bounds__(256) ex_chunkfill_kernel(const int *__restrict
     const long long t = t0 + (live ? lane : 0);
     uint4 M0 = make_uint4(0, 0, 0, 0), M1 = M0;
     if (live) {
-        M0 = *reinterpret_cast<const uint4 *>(c_mask + 8 * t);
-        M1 = *reinterpret_cast<const uint4 *>(c_mask + 8 * t + 4);
+        M0 = ex_mask4<TILED>(c_mask, t, 0);
+        M1 = ex_mask4<TILED>(c_mask, t, 1);
     }
     const int my_off = live ? c_tile_nnz_ptr[t] : 0x7FFFFFFF;
     const int e_end = c_tile_nnz_ptr[t0 + ntl];
@@ -264,6 +291,34 @@ __global__ void __launch_bounds__(256) ex_chunkfill_kernel(const int *__restrict
     }
 }
 
+template <typename VT>
+__global__ void __launch_bounds__(256) ex_chunkfill_kernel(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
+                                                           const int *__restrict__ c_tile_rowptr, const int *__restrict__ c_tile_colidx,
+                                                           const uint32_t *__restrict__ c_mask, const int *__restrict__ c_tile_nnz_ptr,
+                                                           const VT *__restrict__ c_vals, const int *__restrict__ chunkbase,
+                                                           const int *__restrict__ rowptr, int *__restrict__ colidx, VT *__restrict__ vals)
+{
+    __shared__ __attribute__((aligned(16))) uint4 s_rp[4 * 64];
+    __shared__ __attribute__((aligned(16))) uint4 s_ex[4 * 64 * 2];
+    __shared__ unsigned s_mw[4 * 8 * 64];
+    ex_chunkfill<VT, false>(chunkptr, chunk_row, mt, c_tile_rowptr, c_tile_colidx, c_mask, c_tile_nnz_ptr, c_vals, chunkbase, rowptr, colidx, vals,
+                            s_rp, s_ex, s_mw);
+}
+
+template <typename VT>
+__global__ void __launch_bounds__(256) ex_chunkfill_tiled_kernel(const int *__restrict__ chunkptr, const int *__restrict__ chunk_row, int mt,
+                                                                 const int *__restrict__ tile_rowptr, const int *__restrict__ tile_colidx,
+                                                                 const uint32_t *__restrict__ masks, const int *__restrict__ tile_nnz_ptr,
+                                                                 const VT *__restrict__ t_vals, const int *__restrict__ chunkbase,
+                                                                 const int *__restrict__ rowptr, int *__restrict__ colidx, VT *__restrict__ vals)
+{
+    __shared__ __attribute__((aligned(16))) uint4 s_rp[4 * 64];
+    __shared__ __attribute__((aligned(16))) uint4 s_ex[4 * 64 * 2];
+    __shared__ unsigned s_mw[4 * 8 * 64];
+    ex_chunkfill<VT, true>(chunkptr, chunk_row, mt, tile_rowptr, tile_colidx, masks, tile_nnz_ptr, t_vals, chunkbase, rowptr, colidx, vals, s_rp,
+                           s_ex, s_mw);
+}
+
 // per tile row of A: tile-level intermediate products (work estimate for the row-block split)
 __global__ void split_rowprod_kernel(const int *__restrict__ a_tile_rowptr, const int *__restrict__ a_tile_colidx,
                                      const int *__restrict__ b_tile_rowptr, int mt, long long *__restrict__ rowprod)
@@ -285,6 +340,60 @@ static bool export_type_ok(const pem_cplan *p, int value_bytes, const char *fn)
     set_error("%s: the plan holds %s values; use the %s export entry points", fn, p->A->value_bytes == 4 ? "fp32" : "fp64",
               p->A->value_bytes == 4 ? "_f32" : "fp64");
     return false;
+}
+
+// what the balanced export reads: a plan's C slice (mask in PEM_C_MASK's layout) or a whole tiling (TILED: PEM_T_MASKS' layout)
+struct ExSource {
+    int mt, nrows;
+    int64_t ntiles, nnz;
+    const int *tile_rowptr, *tile_colidx, *tile_nnz_ptr;
+    const uint32_t *mask;
+    const void *vals;
+};
+
+// the balanced chunk export (see above) into d_rowptr (zeroed by the caller), d_colidx, d_vals; mt > 0, nrows > 0
+template <typename VT, bool TILED>
+static pem_status export_balanced(pem_ctx *ctx, const ExSource &s, int32_t *d_rowptr, int32_t *d_colidx, VT *d_vals)
+{
+    hipStream_t st = ctx->stream;
+    const int mt = s.mt, nrows = s.nrows;
+    const size_t maxchunks = (size_t)s.ntiles / 64 + (size_t)mt + 1;   // every tile row adds at most one partial chunk
+    DevBuf &chunkptr = ctx->tmp[4], &chunkhist = ctx->tmp[5], &chunkrow = ctx->tmp[6], &rp16 = ctx->tmp[7];
+    PEM_TRY(arena_phase(ctx->arena, {{&chunkptr, sizeof(int) * ((size_t)mt + 4)}, {&chunkhist, sizeof(int) * 16 * (maxchunks + 1)},
+                                     {&chunkrow, sizeof(int) * (maxchunks + 4)}, {&rp16, sizeof(int) * (16 * (size_t)mt + 4)}}));
+    PEM_TRY(chunkptr.reserve(sizeof(int) * ((size_t)mt + 4)));
+    PEM_TRY(chunkhist.reserve(sizeof(int) * 16 * (maxchunks + 1)));
+    PEM_TRY(chunkrow.reserve(sizeof(int) * (maxchunks + 4)));
+    PEM_LAUNCH(ctx, ex_chunkcount_kernel, grid_for((size_t)mt, 256), 256, s.tile_rowptr, mt, chunkptr.as<int>());
+    PEM_TRY(exclusive_scan_i32(ctx, chunkptr.as<int>(), chunkptr.as<int>(), (size_t)mt, nullptr));
+    // (the number of chunks is only known on the device: the grids cover the bound, waves past the end leave at once)
+    if (s.ntiles > 0 && s.nnz > 0) {
+        // the row pointer is written in slots of sixteen per tile row; the caller's array ends at nrows + 1, which the last
+        // tile row may fall short of filling -- so a slice whose row count is no multiple of 16 goes through a padded copy
+        int *rp = d_rowptr;
+        const bool padded = nrows != 16 * mt;
+        if (padded) {
+            PEM_TRY(rp16.reserve(sizeof(int) * (16 * (size_t)mt + 4)));
+            rp = rp16.as<int>();
+        }
+        PEM_LAUNCH(ctx, ex_chunkrow_kernel, grid_for((size_t)mt * 64, 256), 256, chunkptr.as<int>(), mt, chunkrow.as<int>());
+        if constexpr (TILED)
+            PEM_LAUNCH(ctx, ex_chunkhist_tiled_kernel, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt, s.tile_rowptr,
+                       s.mask, chunkhist.as<int>());
+        else
+            PEM_LAUNCH(ctx, ex_chunkhist_kernel, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt, s.tile_rowptr, s.mask,
+                       chunkhist.as<int>());
+        PEM_LAUNCH(ctx, ex_chunkscan_kernel, grid_for((size_t)mt * 64, 256), 256, chunkptr.as<int>(), mt, padded ? 16 * mt : nrows, chunkhist.as<int>(),
+                   s.tile_rowptr, s.tile_nnz_ptr, rp);
+        if constexpr (TILED)
+            PEM_LAUNCH(ctx, ex_chunkfill_tiled_kernel<VT>, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt, s.tile_rowptr,
+                       s.tile_colidx, s.mask, s.tile_nnz_ptr, static_cast<const VT *>(s.vals), chunkhist.as<int>(), rp, d_colidx, d_vals);
+        else
+            PEM_LAUNCH(ctx, ex_chunkfill_kernel<VT>, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt, s.tile_rowptr,
+                       s.tile_colidx, s.mask, s.tile_nnz_ptr, static_cast<const VT *>(s.vals), chunkhist.as<int>(), rp, d_colidx, d_vals);
+        if (padded) PEM_HIP(hipMemcpyAsync(d_rowptr, rp, sizeof(int) * ((size_t)nrows + 1), hipMemcpyDeviceToDevice, st));
+    }
+    return PEM_OK;
 }
 
 template <typename VT>
@@ -315,35 +424,9 @@ static pem_status export_csr_device_impl(pem_ctx *ctx, const pem_cplan *p, int32
                        p->c_mask.as<uint16_t>(), p->c_tile_nnz_ptr.as<int>(), p->c_rowptr.as<uint8_t>(), p->c_vals.as<VT>(), mt, nrows,
                        d_rowptr, d_colidx, d_vals);
     } else if (mt > 0 && nrows > 0) {
-        const size_t maxchunks = (size_t)p->ntiles_c / 64 + (size_t)mt + 1;   // every tile row adds at most one partial chunk
-        DevBuf &chunkptr = ctx->tmp[4], &chunkhist = ctx->tmp[5], &chunkrow = ctx->tmp[6], &rp16 = ctx->tmp[7];
-        PEM_TRY(arena_phase(ctx->arena, {{&chunkptr, sizeof(int) * ((size_t)mt + 4)}, {&chunkhist, sizeof(int) * 16 * (maxchunks + 1)},
-                                         {&chunkrow, sizeof(int) * (maxchunks + 4)}, {&rp16, sizeof(int) * (16 * (size_t)mt + 4)}}));
-        PEM_TRY(chunkptr.reserve(sizeof(int) * ((size_t)mt + 4)));
-        PEM_TRY(chunkhist.reserve(sizeof(int) * 16 * (maxchunks + 1)));
-        PEM_TRY(chunkrow.reserve(sizeof(int) * (maxchunks + 4)));
-        PEM_LAUNCH(ctx, ex_chunkcount_kernel, grid_for((size_t)mt, 256), 256, p->c_tile_rowptr.as<int>(), mt, chunkptr.as<int>());
-        PEM_TRY(exclusive_scan_i32(ctx, chunkptr.as<int>(), chunkptr.as<int>(), (size_t)mt, nullptr));
-        // (the number of chunks is only known on the device: the grids cover the bound, waves past the end leave at once)
-        if (p->ntiles_c > 0 && p->nnz_c > 0) {
-            // the row pointer is written in slots of sixteen per tile row; the caller's array ends at nrows + 1, which the last
-            // tile row may fall short of filling -- so a slice whose row count is no multiple of 16 goes through a padded copy
-            int *rp = d_rowptr;
-            const bool padded = nrows != 16 * mt;
-            if (padded) {
-                PEM_TRY(rp16.reserve(sizeof(int) * (16 * (size_t)mt + 4)));
-                rp = rp16.as<int>();
-            }
-            PEM_LAUNCH(ctx, ex_chunkrow_kernel, grid_for((size_t)mt * 64, 256), 256, chunkptr.as<int>(), mt, chunkrow.as<int>());
-            PEM_LAUNCH(ctx, ex_chunkhist_kernel, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt,
-                       p->c_tile_rowptr.as<int>(), p->c_mask.as<uint32_t>(), chunkhist.as<int>());
-            PEM_LAUNCH(ctx, ex_chunkscan_kernel, grid_for((size_t)mt * 64, 256), 256, chunkptr.as<int>(), mt, padded ? 16 * mt : nrows, chunkhist.as<int>(),
-                       p->c_tile_rowptr.as<int>(), p->c_tile_nnz_ptr.as<int>(), rp);
-            PEM_LAUNCH(ctx, ex_chunkfill_kernel<VT>, grid_for(maxchunks * 64, 256), 256, chunkptr.as<int>(), chunkrow.as<int>(), mt,
-                       p->c_tile_rowptr.as<int>(), p->c_tile_colidx.as<int>(), p->c_mask.as<uint32_t>(), p->c_tile_nnz_ptr.as<int>(),
-                       p->c_vals.as<VT>(), chunkhist.as<int>(), rp, d_colidx, d_vals);
-            if (padded) PEM_HIP(hipMemcpyAsync(d_rowptr, rp, sizeof(int) * ((size_t)nrows + 1), hipMemcpyDeviceToDevice, st));
-        }
+        const ExSource src{mt, nrows, p->ntiles_c, p->nnz_c, p->c_tile_rowptr.as<int>(), p->c_tile_colidx.as<int>(), p->c_tile_nnz_ptr.as<int>(),
+                           p->c_mask.as<uint32_t>(), p->c_vals.p};
+        PEM_TRY((export_balanced<VT, false>(ctx, src, d_rowptr, d_colidx, d_vals)));
     }
     PEM_HIP(hipEventRecord(ctx->ev[7], st));
     return PEM_OK;
@@ -425,6 +508,66 @@ extern "C" pem_status pem_c_export_coo(pem_ctx *ctx, const pem_cplan *p, int64_t
 extern "C" pem_status pem_c_export_coo_f32(pem_ctx *ctx, const pem_cplan *p, int64_t *nnz, int32_t *rows, int32_t *cols, float *vals)
 {
     return export_coo_impl<float>(ctx, p, nnz, rows, cols, vals);
+}
+
+// ------------------------------------------------------------------------------------------
+// a tiling as CSR (pem_tiled_export_csr): the balanced export over the tiling's own arrays
+// ------------------------------------------------------------------------------------------
+template <typename VT>
+static pem_status tiled_export_csr_impl(pem_ctx *ctx, const pem_tiled *t, int64_t *nnz, int32_t *rowptr, int32_t *colidx, VT *vals)
+{
+    const char *fn = sizeof(VT) == 4 ? "pem_tiled_export_csr_f32" : "pem_tiled_export_csr";
+    if (!ctx || !t) {
+        set_error("%s: null context or tiling", fn);
+        return PEM_E_INVALID;
+    }
+    if (t->value_bytes != (int)sizeof(VT)) {
+        set_error("%s: the tiling holds %s values; use the %s export entry points", fn, t->value_bytes == 4 ? "fp32" : "fp64",
+                  t->value_bytes == 4 ? "_f32" : "fp64");
+        return PEM_E_INVALID;
+    }
+    if (nnz) *nnz = t->nnz;
+    if (!rowptr) return PEM_OK;   // size query
+    const size_t nrows = (size_t)t->rows, nz = (size_t)t->nnz;
+    if (nz && (!colidx || !vals)) {
+        set_error("%s: null column or value array for a tiling of %lld entries", fn, (long long)nz);
+        return PEM_E_INVALID;
+    }
+    PEM_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    PEM_TRY(zero_flags(ctx));
+    DevBuf dR, dC, dV;
+    PEM_TRY(dR.reserve(sizeof(int) * (nrows + 4)));
+    PEM_TRY(dC.reserve(sizeof(int) * (nz + 4)));
+    PEM_TRY(dV.reserve(sizeof(VT) * (nz + 1)));
+    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    PEM_HIP(hipMemsetAsync(dR.p, 0, sizeof(int) * (nrows + 1), st));
+    if (t->tile_rows > 0 && nrows > 0) {
+        const ExSource src{t->tile_rows, t->rows, t->ntiles, t->nnz, t->tile_rowptr.as<int>(), t->tile_colidx.as<int>(), t->tile_nnz_ptr.as<int>(),
+                           t->masks.as<uint32_t>(), t->vals.p};
+        PEM_TRY((export_balanced<VT, true>(ctx, src, dR.as<int>(), dC.as<int>(), dV.as<VT>())));
+    }
+    PEM_HIP(hipEventRecord(ctx->ev[7], st));
+    PEM_HIP(hipMemcpyAsync(rowptr, dR.p, sizeof(int) * (nrows + 1), hipMemcpyDeviceToHost, st));
+    if (nz) {
+        PEM_HIP(hipMemcpyAsync(colidx, dC.p, sizeof(int) * nz, hipMemcpyDeviceToHost, st));
+        PEM_HIP(hipMemcpyAsync(vals, dV.p, sizeof(VT) * nz, hipMemcpyDeviceToHost, st));
+    }
+    int hf[NUM_FLAGS];
+    PEM_TRY(read_flags(ctx, hf));    // (synchronises) -- the export's scan gave up: the row pointer just copied is not valid
+    PEM_TRY(check_internal(hf));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]) == hipSuccess) ctx->timings.export_ms = ms;
+    return PEM_OK;
+}
+
+extern "C" pem_status pem_tiled_export_csr(pem_ctx *ctx, const pem_tiled *t, int64_t *nnz, int32_t *rowptr, int32_t *colidx, double *vals)
+{
+    return tiled_export_csr_impl<double>(ctx, t, nnz, rowptr, colidx, vals);
+}
+extern "C" pem_status pem_tiled_export_csr_f32(pem_ctx *ctx, const pem_tiled *t, int64_t *nnz, int32_t *rowptr, int32_t *colidx, float *vals)
+{
+    return tiled_export_csr_impl<float>(ctx, t, nnz, rowptr, colidx, vals);
 }
 
 // weight of every tile row of A in C = A*B: its tile-level products + its tiles + 1 (so empty-product rows still spread out)

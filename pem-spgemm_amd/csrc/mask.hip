@@ -17,24 +17,9 @@
 //   mask_compact_kernel  one lane per pair: kept pairs to their new position (pair_col with its head bit, pairs_a, pairs_b), the
 //                        heads per 256 kept pairs (scanned afterwards), M's tile id per kept C tile, _C_rowPtr of the kept tiles
 #include "spgemm_internal.h"
+#include "tiled_internal.h"
 
 using namespace pem;
-
-// M's tile id at (i, j), -1 where M has none: binary search in M's tile row i (tile_colidx is sorted inside a row)
-__device__ __forceinline__ int mask_find_tile(const int *__restrict__ m_rowptr, const int *__restrict__ m_colidx, const int i, const int j)
-{
-    int lo = m_rowptr[i];
-    const int end = m_rowptr[i + 1];
-    int hi = end;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (m_colidx[mid] < j)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo < end && m_colidx[lo] == j ? lo : -1;
-}
 
 __device__ __forceinline__ bool mask_tile_full(const uint16_t *__restrict__ m_masks, const int mt)
 {

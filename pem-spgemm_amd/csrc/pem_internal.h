@@ -287,6 +287,9 @@ pem_status check_internal(const int *host_flags);   // PEM_E_HIP if a device pri
 // copy `count` int64 scalars from device to the pinned page and synchronise
 pem_status read_scalars(pem_ctx *ctx, const int64_t *d_src, int count, int64_t *host_dst);
 
+// process-wide, unique per tiling created (never 0): what a tiling made from other tilings records (convert.hip)
+uint64_t next_tiled_serial();
+
 }  // namespace pem
 
 struct pem_tiled {
@@ -315,6 +318,15 @@ struct pem_tiled {
     int src_transpose = 0;
     pem::DevBuf cmap;
     bool cmap_ready = false;
+    uint64_t serial = pem::next_tiled_serial();
+    // a tiling made by pem_tiled_ewise (ewise.hip): its operands' serials (0: not made so), the pattern, op and scales it was made
+    // with, A's and B's tile feeding every tile (int2[T], -1: none), and on its first pem_tiled_set_values_from_ewise the int2[nnz]
+    // slots of every entry's operand values in A's and B's vals (-1: none)
+    uint64_t ew_a_serial = 0, ew_b_serial = 0;
+    int ew_pattern = 0, ew_op = 0;
+    double ew_alpha = 1.0, ew_beta = 1.0;
+    pem::DevBuf ew_src, ew_map;
+    bool ew_map_ready = false;
 };
 
 struct pem_cplan {

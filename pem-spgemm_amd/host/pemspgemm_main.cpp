@@ -337,12 +337,17 @@ int main(int argc, char *argv[])
     // plus_pair or lor_land; C's structure, the flop count (the tile product's) and the CSV columns do not change.
     // `--power K` computes A^K = (...(A*A)*A...)*A as K-1 products, every C turned into the next left
     // operand on the device; with --semiring every product uses it.  The report and the CSV row describe the last product.
+    // `--add D.mtx [--alpha x] [--beta y]` computes C = alpha*(A*B) (+) beta*D on the device: the product's
+    // C becomes a tiling (pem_tiled_from_cplan) and is combined with D over the union of their patterns (pem_tiled_ewise), (+) being
+    // the semiring's additive op; --out then writes that sum.  D has C's shape and is read with --fp32 like A.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
     bool mask_complement = false;
     const char *semiring_name = nullptr;
     int power = 0;   // --power K: A^K as K-1 chained products (0: off)
+    const char *add_path = nullptr;   // --add D.mtx: C = alpha*(A*B) (+) beta*D
+    double add_alpha = 1.0, add_beta = 1.0;
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -362,6 +367,9 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--mask-complement")) mask_complement = true;
             else if (!strcmp(argv[r], "--semiring") && r + 1 < argc) semiring_name = argv[++r];
             else if (!strcmp(argv[r], "--power") && r + 1 < argc) power = atoi(argv[++r]);
+            else if (!strcmp(argv[r], "--add") && r + 1 < argc) add_path = argv[++r];
+            else if (!strcmp(argv[r], "--alpha") && r + 1 < argc) add_alpha = atof(argv[++r]);
+            else if (!strcmp(argv[r], "--beta") && r + 1 < argc) add_beta = atof(argv[++r]);
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -413,6 +421,23 @@ int main(int argc, char *argv[])
                 printf("--power does not combine with %s (A^K multiplies A by itself on one device). Exiting.\n", clash);
             return 1;
         }
+    }
+    // --add: the semiring's additive op (pem_binop) combines alpha*C and beta*D
+    static const int add_ops[] = {PEM_BINOP_PLUS, PEM_BINOP_MIN, PEM_BINOP_MAX, PEM_BINOP_MAX, PEM_BINOP_PLUS, PEM_BINOP_LOR};   // by pem_semiring
+    static const char *const add_op_names[] = {"plus", "times", "min", "max", "lor", "land"};                                  // by pem_binop
+    if (add_path) {
+        const char *clash = ngpu > 0 ? "--gpus" : mask_path ? "--mask" : power ? "--power" : nullptr;
+        if (clash) {
+            printf("--add does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        if ((add_alpha != 1.0 || add_beta != 1.0) && semiring != PEM_SEMIRING_PLUS_TIMES) {
+            printf("--add: --alpha / --beta other than 1 need the plus_times semiring, not %s. Exiting.\n", semiring_names[semiring]);
+            return 1;
+        }
+    } else if (add_alpha != 1.0 || add_beta != 1.0) {
+        printf("--alpha / --beta need --add <D.mtx>. Exiting.\n");
+        return 1;
     }
     if (ngpu > 0 && mask_path) {
         printf("--gpus does not combine with --mask (masked products run on one device). Exiting.\n");
@@ -610,6 +635,30 @@ int main(int argc, char *argv[])
             return 2;
         }
     }
+    pem_tiled *Dt = nullptr;   // --add: D, in the value type of A
+    pem_coo cd;
+    memset(&cd, 0, sizeof cd);
+    if (add_path) {
+        if (read_input(add_path, &cd) != 0) return 1;
+        if (cd.rows != ia.rows || cd.cols != ib.cols) {
+            printf("--add %s is %d x %d but C = A*B%s is %d x %d. Exiting.\n", add_path, cd.rows, cd.cols, aat ? "^T" : "", ia.rows, ib.cols);
+            pem_coo_free(&cd);
+            return 1;
+        }
+        pem_status ds;
+        if (fp32) {
+            std::vector<float> vf((size_t)cd.nnz);
+            for (int64_t e = 0; e < cd.nnz; ++e) vf[(size_t)e] = (float)cd.V[e];
+            ds = pem_tiled_from_coo_f32(ctx, cd.rows, cd.cols, cd.nnz, cd.I, cd.J, vf.data(), 0, &Dt);
+        } else {
+            ds = pem_tiled_from_coo(ctx, cd.rows, cd.cols, cd.nnz, cd.I, cd.J, cd.V, 0, &Dt);
+        }
+        if (ds != PEM_OK) {
+            fprintf(stderr, "pemspgemm: conversion of %s failed: %s\n", add_path, pem_last_error());
+            pem_coo_free(&cd);
+            return 2;
+        }
+    }
     if (fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", argv[1], ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
     printf("MATRIX B\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", b_path ? b_path : argv[1], ib.rows, ib.cols, (long long)ib.nnz);
@@ -728,6 +777,22 @@ int main(int argc, char *argv[])
     const char *csv = getenv("PEM_CSV") ? getenv("PEM_CSV") : "./pemspgemm_benchmark_result.csv";
     if (pem_csv_append(csv, &rec, extra) != 0) fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
 
+    pem_tiled *Sum = nullptr;   // --add: alpha*C (+) beta*D
+    if (Dt) {
+        auto a0 = std::chrono::high_resolution_clock::now();
+        pem_tiled *Ct = nullptr;
+        CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+        const int op = add_ops[semiring];
+        CHECK(pem_tiled_ewise(ctx, Ct, Dt, PEM_EWISE_UNION, op, add_alpha, add_beta, &Sum));
+        const double add_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - a0).count();
+        pem_tiled_info si, ct;
+        CHECK(pem_tiled_get_info(Sum, &si));
+        CHECK(pem_tiled_get_info(Ct, &ct));
+        printf("add: C = %g*(A*B) %s %g*D over the union: C -> tiling %.2fms, ewise %.2fms, total %.2fms, nnz %lld\n", add_alpha, add_op_names[op],
+               add_beta, ct.conv_ms, si.conv_ms, add_ms, (long long)si.nnz);
+        pem_tiled_destroy(ctx, Ct);
+    }
+
     int rc = 0;
     if (!save) {
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
@@ -752,7 +817,27 @@ int main(int argc, char *argv[])
             rc = 2;
         }
     }
-    if (out_path) {   // C as a Matrix-Market file (CSR export: rows ascending, columns ascending)
+    if (out_path && Sum) {   // the sum as a Matrix-Market file (the tiling's CSR export)
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Sum, &si));
+        std::vector<int32_t> rp((size_t)si.rows + 1), cidx((size_t)si.nnz);
+        std::vector<double> cv((size_t)si.nnz);
+        int64_t nnz = 0;
+        if (fp32) {
+            std::vector<float> vf((size_t)si.nnz);
+            CHECK(pem_tiled_export_csr_f32(ctx, Sum, &nnz, rp.data(), cidx.data(), vf.data()));
+            for (size_t e = 0; e < vf.size(); ++e) cv[e] = vf[e];
+        } else {
+            CHECK(pem_tiled_export_csr(ctx, Sum, &nnz, rp.data(), cidx.data(), cv.data()));
+        }
+        const std::string comment = std::string("C = alpha*A*B + beta*D (") + semiring_names[semiring] + ") by pemspgemm (pem-spgemm_amd)";
+        if (pem_write_mtx_csr(out_path, si.rows, si.cols, rp.data(), cidx.data(), cv.data(), comment.c_str()) != 0) {
+            fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
+            rc = 2;
+        } else {
+            printf("C written to %s\n", out_path);
+        }
+    } else if (out_path) {   // C as a Matrix-Market file (CSR export: rows ascending, columns ascending)
         std::vector<int32_t> rp((size_t)(ci.row_end - ci.row_begin) + 1), cidx((size_t)ci.nnz_c);
         std::vector<double> cv((size_t)ci.nnz_c);
         int64_t nnz = 0;
@@ -777,6 +862,9 @@ int main(int argc, char *argv[])
     if (L != A) pem_tiled_destroy(ctx, L);
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
+    if (Sum) pem_tiled_destroy(ctx, Sum);
+    if (Dt) pem_tiled_destroy(ctx, Dt);
+    pem_coo_free(&cd);
     if (B != A) pem_tiled_destroy(ctx, B);
     pem_tiled_destroy(ctx, A);
     pem_ctx_destroy(ctx);
