@@ -31,6 +31,9 @@ extern "C" {
 #define PEM_OPT_S2_TRANSPOSED  ((pem_option)16) /* step 2's boolean tile product: 0 from A's row masks (one trip per nonzero of the A tile), 1 from A's
                                                    transposed masks (one trip per inner index occupied on both sides), 2 (default): 1 on repeat
                                                    passes of plans with two or more pairs per C tile (cage15-class), else 0            */
+#define PEM_OPT_S3_POISON      ((pem_option)17) /* test hook: 1 fills C's values [0, nnz_c) with the NaN bit pattern 0x7FF4 per 16-bit half (fp64 and
+                                                   fp32 alike) on the context's stream before step 3's kernels, so that an entry no kernel writes
+                                                   keeps it; 2: the fill only, no step-3 kernel (a negative control for tests); 0 (default): off */
 
 /* a further value of pem_cplan_array: int32[T_C] of a masked plan (pem_cplan_create_masked), for every C tile M's tile id at its
  * (tile row, tile column), -1 where M has none (complement masks only); readable after step 1 */

@@ -357,6 +357,7 @@ struct pem_cplan {
     int opt_s3_xcd = 1;                                // step 3 (entry-per-lane kernels): XCD x takes the x-th contiguous eighth of C
     int opt_epw = 0;                                   // step 3: entries per wave / 256 (0: chosen from the C tiles' density)
     int opt_decode = 1;                                // shallow plans: step 3 reads (row, column) off the C masks, no Ctiles_rowColIdx on the pass
+    int opt_s3_poison = 0;                             // test hook: 1 fills c_vals with a NaN pattern before step 3's kernels, 2 the fill alone
     int64_t ntiles_c = 0, npairs = 0, nnz_c = 0;
     pem::DevBuf c_tile_rowptr, c_tile_colidx;
     mutable pem::DevBuf c_tile_rowidx; // _C_tileRowIdx: on demand from c_tile_rowptr on the row-local path (no reader there)

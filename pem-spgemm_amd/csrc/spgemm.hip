@@ -200,6 +200,7 @@ static int *plan_option_slot(pem_cplan *p, pem_option which)
     case PEM_OPT_S3_MARK: return &p->opt_mark;
     case PEM_OPT_S1_SEGMENTS: return &p->opt_s1_segments;
     case PEM_OPT_S2_TRANSPOSED: return &p->opt_s2_transposed;
+    case PEM_OPT_S3_POISON: return &p->opt_s3_poison;
     default: return nullptr;
     }
 }
@@ -217,7 +218,7 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
                   which == PEM_OPT_WIDE ? "PEM_OPT_WIDE" : "PEM_OPT_STEP1_GLOBAL_SORT", (long long)value);
         return PEM_E_INVALID;
     }
-    const int v = (which == PEM_OPT_S1_XLCAP || which == PEM_OPT_S3_EPW || which == PEM_OPT_S2_TRANSPOSED) ? (int)value : (value != 0);
+    const int v = (which == PEM_OPT_S1_XLCAP || which == PEM_OPT_S3_EPW || which == PEM_OPT_S2_TRANSPOSED || which == PEM_OPT_S3_POISON) ? (int)value : (value != 0);
     if (*slot == v) return PEM_OK;
     *slot = v;
     // a repeat pass re-uses the sizes (and possibly the captured graph) of the previous one: whatever changes the kernels
@@ -231,7 +232,8 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
     case PEM_OPT_PRUNE: case PEM_OPT_STEP1_GLOBAL_SORT: case PEM_OPT_S1_FORCE_KEY64: case PEM_OPT_S1_XLCAP: case PEM_OPT_S1_XL_GLOBAL:
     case PEM_OPT_S1_SEGMENTS: keep = 0; break;
     case PEM_OPT_WIDE: case PEM_OPT_S3_DECODE: case PEM_OPT_S2_TRANSPOSED: keep = 1; break;
-    case PEM_OPT_S3_BAND: case PEM_OPT_S3_EPW: case PEM_OPT_S3_IDX64: case PEM_OPT_S3_MARK: case PEM_OPT_S3_XCD: keep = 2; break;
+    case PEM_OPT_S3_BAND: case PEM_OPT_S3_EPW: case PEM_OPT_S3_IDX64: case PEM_OPT_S3_MARK: case PEM_OPT_S3_XCD:
+    case PEM_OPT_S3_POISON: keep = 2; break;
     default: break;                                    // warm passes, the export variant, serial bins: no step's result changes
     }
     if (plan->state > keep) plan->state = keep;

@@ -637,6 +637,14 @@ static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, 
 #undef PEM_S3_DECODE
 }
 
+// PEM_OPT_S3_POISON (pem_test.h): C's values become a NaN bit pattern before step 3 runs, so that a test can tell an entry no
+// kernel wrote from one an earlier pass left behind.  A kernel, not a memset, so that a captured pass holds it as an ordinary node.
+__global__ void __launch_bounds__(256) c_poison_fill_kernel(uint32_t *__restrict__ w, long long n)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) w[i] = 0x7FF47FF4u;
+}
+
 pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
 {
     if (p->state < 2) {
@@ -667,7 +675,11 @@ pem_status pem::step3_impl(pem_ctx *ctx, pem_cplan *p)
 #define PEM_S3_SR(SRT, SFX)                                                                                                                    \
     (f32 ? s3_launch<float, SRT>(ctx, p, PEM_S3_NAMES(float, SFX), deep, idx32, mark, s3_epw, s3_xcd)                                         \
          : s3_launch<double, SRT>(ctx, p, PEM_S3_NAMES(double, SFX), deep, idx32, mark, s3_epw, s3_xcd))
-    if (ntc > 0) {
+    if (p->opt_s3_poison && p->nnz_c > 0) {
+        const long long nw = (long long)p->nnz_c * A->value_bytes / 4;   // (4 or 8 bytes per value: whole words)
+        PEM_LAUNCH_NAMED(ctx, "c_poison_fill_kernel", c_poison_fill_kernel, grid_for((size_t)nw, 256), 256, p->c_vals.as<uint32_t>(), nw);
+    }
+    if (ntc > 0 && p->opt_s3_poison != 2) {
         switch (p->semiring) {
         case PEM_SEMIRING_MIN_PLUS: PEM_S3_SR(SrMinPlus, ",min_plus"); break;
         case PEM_SEMIRING_MAX_PLUS: PEM_S3_SR(SrMaxPlus, ",max_plus"); break;

@@ -12,6 +12,7 @@ import torch
 
 import maskref
 from matgen import _vals, cases
+from s3cases import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -215,7 +216,9 @@ def test_stepwise_repeat_and_graph_replay(pkg, oracle, ctx):
             ref.spgemm()
             want = _results(ref)
             want_arrays = {k: ref.array(k) for k in ARRAYS}
+            ref.set_option("s3_poison", 1)                     # from here C holds a NaN fill before every step 3
             sw = pkg.CPlan(ctx, A, B, mask=M, complement=comp)
+            sw.set_option("s3_poison", 1)
             sw.step1()
             for k in ("c_tile_rowptr", "c_tile_colidx", "pairs_offset", "c_mtile"):
                 assert _same(sw.array(k), want_arrays[k]), f"{name} step 1 {k}"
@@ -224,14 +227,17 @@ def test_stepwise_repeat_and_graph_replay(pkg, oracle, ctx):
                 assert _same(sw.array(k), want_arrays[k]), f"{name} step 2 {k}"
             sw.step3()
             assert all(_same(g, w) for g, w in zip(_results(sw), want)), f"{name} step-wise"
+            assert not poisoned(sw.array("c_vals")).any(), f"{name} step-wise"
             for _ in range(3):
                 ref.spgemm()
                 assert all(_same(g, w) for g, w in zip(_results(ref), want)), f"{name} repeat pass"
+                assert not poisoned(ref.array("c_vals")).any(), f"{name} repeat pass"
             ctx.set_graph_replay(True)
             try:
                 for _ in range(3):
                     ref.spgemm()
                     assert all(_same(g, w) for g, w in zip(_results(ref), want)), f"{name} graph replay"
+                    assert not poisoned(ref.array("c_vals")).any(), f"{name} graph replay"
                     for k in ARRAYS:
                         assert _same(ref.array(k), want_arrays[k]), f"{name} graph replay {k}"
             finally:

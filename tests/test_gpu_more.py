@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from s3cases import poisoned
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = sorted(glob.glob(os.path.join(GOLD, "spgemm_*.npz")))
@@ -312,6 +314,7 @@ def test_graph_replay_is_bit_identical_and_survives_reallocation(pkg, oracle, ct
         oA = oracle.Tiled(rows, cols, I, J, V)
         oB = oracle.Tiled(rows, cols, I, J, V, True) if tr else oA
         p = pkg.CPlan(ctx, A, B)
+        p.set_option("s3_poison", 1)                          # C holds a NaN fill before every step 3, replays included
         p.spgemm()
         plans.append((p, A, B))
         wants.append(expected(oracle.Plan(oA, oB), oA, oB)[0])
@@ -324,6 +327,7 @@ def test_graph_replay_is_bit_identical_and_survives_reallocation(pkg, oracle, ct
                 assert t["step1_ms"] == 0.0 and t["spgemm_wall_ms"] > 0.0     # replayed: no step split
                 for arr in ("pairs_a", "pairs_b", "c_mask", "c_tile_nnz_ptr", "c_rowcolidx", "c_vals", "c_tile_rowidx", "c_rowptr"):
                     assert np.array_equal(p.array(arr), want[arr]), (rnd, arr)
+                assert not poisoned(p.array("c_vals")).any()
                 if rnd == 1:
                     p.export_csr()                            # grows export scratch -> next replay must re-capture
         # a much larger plan on the same context grows the shared scan / sort scratch under the old graphs
@@ -335,6 +339,7 @@ def test_graph_replay_is_bit_identical_and_survives_reallocation(pkg, oracle, ct
         for (p, _, _), want in zip(plans, wants):
             p.spgemm()
             assert np.array_equal(p.array("c_vals"), want["c_vals"])
+            assert not poisoned(p.export_csr()[2]).any()
     finally:
         ctx.set_graph_replay(False)
     plans[0][0].spgemm()

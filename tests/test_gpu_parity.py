@@ -4,6 +4,7 @@ import pytest
 
 from matgen import cases
 from prune_ref import expected
+from s3cases import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -123,6 +124,7 @@ def test_repeat_passes_skip_readbacks_and_stay_identical(pkg, oracle, ctx, monke
     for name in ("powerlaw_600", "hub_row_4000", "empty_matrix", "blockrows_10000"):
         gA, gB, oA, oB = _tiled_pair(pkg, oracle, ctx, CASES[name])
         plan = pkg.CPlan(ctx, gA, gB)
+        plan.set_option("s3_poison", 1)    # C holds a NaN fill before every step 3: each pass must write all of it
         plan.spgemm()                      # cold
         cold = [plan.array(a) for a in C_NAMES]
         for _ in range(3):
@@ -136,6 +138,8 @@ def test_repeat_passes_skip_readbacks_and_stay_identical(pkg, oracle, ctx, monke
         for a, c, w, f in zip(C_NAMES, cold, warm, forced):
             want = want_arrays[a]
             assert np.array_equal(c, want) and np.array_equal(w, want) and np.array_equal(f, want), (name, a)
+        for got in (cold, warm, forced):
+            assert not poisoned(got[C_NAMES.index("c_vals")]).any(), name
 
 
 @pytest.mark.parametrize("name", ["powerlaw_600", "hub_row_4000", "ragged_37", "empty_rows"])

@@ -4,6 +4,7 @@ import pytest
 
 from matgen import cases
 from prune_ref import expected
+from s3cases import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -29,6 +30,7 @@ def test_stepwise_calls_after_warm_passes(pkg, oracle, ctx, name, graph):
     finding: c_tile_nnz_ptr / c_rowcolidx came out wrong and step 3 produced garbage, status PEM_OK)."""
     gA, gB, oA, oB = _pair(pkg, oracle, ctx, CASES[name])
     plan = pkg.CPlan(ctx, gA, gB)
+    plan.set_option("s3_poison", 1)   # C holds a NaN fill before every step 3: a pass that leaves an entry unwritten shows
     ctx.set_graph_replay(graph)
     try:
         for _ in range(3):
@@ -44,9 +46,11 @@ def test_stepwise_calls_after_warm_passes(pkg, oracle, ctx, name, graph):
     assert (info["ntiles_c"], info["npairs"], info["nnz_c"], info["npairs_all"]) == want_counts
     for arr in C_NAMES:
         assert np.array_equal(plan.array(arr), want_arrays[arr]), f"{name}: {arr} differs after step-wise calls on a warm plan"
+    assert not poisoned(plan.array("c_vals")).any()
     plan.spgemm()             # ... and the plan is still good for whole passes
     for arr in C_NAMES:
         assert np.array_equal(plan.array(arr), want_arrays[arr]), f"{name}: {arr} differs on the pass after"
+    assert not poisoned(plan.export_csr()[2]).any()
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 2048, 2049, 8192, 8193, 70001, 262144])
@@ -376,11 +380,14 @@ def test_plans_come_and_go_under_graph_replay(pkg, standins, ctx):
             cuts = [0] + [int(mt * (k + 0.13 * ((rnd + k) % 3)) / 4) for k in range(1, 4)] + [mt]
             for p in range(4):
                 plan = pkg.CPlan(ctx, A, A, cuts[p], cuts[p + 1])
+                plan.set_option("s3_poison", 1)            # (the arena hands this plan an earlier plan's C buffer)
                 for _ in range(5):
                     plan.spgemm()
                 info = plan.info()
                 key = (cuts[p], cuts[p + 1])
-                sig = (info["ntiles_c"], info["npairs"], info["nnz_c"], float(plan.array("c_vals").sum()))
+                cv = plan.array("c_vals")
+                assert not poisoned(cv).any()
+                sig = (info["ntiles_c"], info["npairs"], info["nnz_c"], float(cv.sum()))
                 assert seen.setdefault(key, sig) == sig
                 plan.close()
         whole = pkg.CPlan(ctx, A, A)

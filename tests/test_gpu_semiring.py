@@ -12,6 +12,7 @@ import torch
 
 import semiringref as sr
 from matgen import _vals, cases
+from s3cases import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -326,9 +327,11 @@ def test_warm_passes_and_graph_replay(pkg, ctx):
         base.spgemm()
         want_pt = base.export_csr()
         plan = pkg.CPlan(ctx, A, B, semiring="min_plus")
+        plan.set_option("s3_poison", 1)                            # C holds a NaN fill before every step 3, replays included
         for _ in range(3):                                         # warm repeat passes
             plan.spgemm()
             _check(plan.export_csr(), _expected(ref_ops, "min_plus", np.float64, cache), f"{name} warm")
+            assert not poisoned(plan.export_csr()[2]).any()
         ctx.set_graph_replay(True)
         try:
             for s in ("min_plus", "plus_pair", "plus_times", "max_plus", "lor_land"):
@@ -336,6 +339,7 @@ def test_warm_passes_and_graph_replay(pkg, ctx):
                 for _ in range(3):                                 # (the first pass after a change captures again)
                     plan.spgemm()
                     got = plan.export_csr()
+                    assert not poisoned(got[2]).any(), f"{name} replay {s}"
                     if s == "plus_times":
                         assert all(_same_bits(g, w) for g, w in zip(got, want_pt)), f"{name} replay plus_times"
                     else:
@@ -344,6 +348,7 @@ def test_warm_passes_and_graph_replay(pkg, ctx):
             ctx.set_graph_replay(False)
         plan.spgemm()
         _check(plan.export_csr(), _expected(ref_ops, "lor_land", np.float64, cache), f"{name} after replay")
+        assert not poisoned(plan.export_csr()[2]).any()
 
 
 def test_errors(pkg, ctx):
