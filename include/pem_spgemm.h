@@ -295,6 +295,45 @@ pem_status pem_tiled_ewise(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B,
                            pem_tiled **out);
 pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B);
 
+/* Select (GraphBLAS GrB_select): the stored entries of a tiling that satisfy a predicate, on the device.
+ *   pem_tiled_select  a new tiling R of A's shape and value type, owning its arrays, holding exactly the stored entries of A that
+ *       satisfy op with the thunk; values are copied bit for bit.  R works everywhere a tiling does (A, B, mask, save / load,
+ *       set_values*, flop count, split, ewise, export, select).  Tiles left without entries are not in R (1..256 entries per tile);
+ *       if nothing is kept, R is a valid tiling with nnz = 0.
+ *     Coordinates.  (i, j) are those of the matrix the tiling represents (the matrix pem_tiled_export_csr returns): a tiling built
+ *       with transpose = 1 is filtered as M^T.
+ *     Positional ops (PEM_SELECT_TRIL .. PEM_SELECT_COL_GT) read no values.  The thunk is an integer k: it must be integral with
+ *       |k| <= 2^31, else PEM_E_INVALID.  A k beyond the shape is legal and keeps everything or nothing.
+ *     Value ops compare the value x with y = the thunk rounded once to the tiling's value type ((float)thunk, to nearest, for fp32),
+ *       with IEEE comparisons in that type: -0.0 == 0.0; a NaN x fails every predicate but PEM_SELECT_VALUE_NE, and ABS_GT drops it;
+ *       a NaN thunk is allowed (VALUE_NE keeps everything, the other value ops nothing).  VALUE_NE with thunk 0 drops explicit zeros.
+ *     R equals the tiling pem_tiled_from_csr builds from the filtered pem_tiled_export_csr of A (every pem_tiled_info field but the
+ *       two timings, every pem_tiled_array).  PEM_E_INVALID: a null argument, an unknown op, a bad positional thunk.  A's values are
+ *       read as they are when the call is made (stream order); the call waits, and its allocations come from the context's arena (a
+ *       captured graph re-captures once).  Besides the tiling's own arrays R keeps 4 bytes per tile of R (its tile in A).
+ *   pem_tiled_set_values_from_select  positional ops only (their pattern does not depend on the values): rewrites t's vals and vals_t
+ *       in place from A's current values and bumps t's value version.  Stream-ordered, never waits, reads nothing back; only the
+ *       first call allocates (an int32 per entry: the slot of its value in A's vals).  PEM_E_INVALID unless t was made by
+ *       pem_tiled_select from exactly this A (the serial rule of pem_tiled_set_values_from_ewise), and for a t made by a value op:
+ *       its pattern depends on the values, so select again. */
+typedef enum {
+    /* position of entry (i, j) of the tiled matrix; k = thunk, an integer */
+    PEM_SELECT_TRIL = 0,     /* j <= i + k */
+    PEM_SELECT_TRIU = 1,     /* j >= i + k */
+    PEM_SELECT_DIAG = 2,     /* j == i + k */
+    PEM_SELECT_OFFDIAG = 3,  /* j != i + k */
+    PEM_SELECT_ROW_LE = 4,   /* i <= k */
+    PEM_SELECT_ROW_GT = 5,   /* i >  k */
+    PEM_SELECT_COL_LE = 6,   /* j <= k */
+    PEM_SELECT_COL_GT = 7,   /* j >  k */
+    /* value x of the entry; y = thunk rounded once to the tiling's value type */
+    PEM_SELECT_VALUE_EQ = 8, PEM_SELECT_VALUE_NE = 9, PEM_SELECT_VALUE_LT = 10,
+    PEM_SELECT_VALUE_LE = 11, PEM_SELECT_VALUE_GT = 12, PEM_SELECT_VALUE_GE = 13,
+    PEM_SELECT_ABS_GT = 14   /* fabs(x) > y: drop tolerance */
+} pem_select_op;
+pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out);
+pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

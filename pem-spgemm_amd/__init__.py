@@ -49,12 +49,17 @@ ABI_SYMBOLS = [
     "pem_debug_refused_launch", "pem_tiled_set_values", "pem_tiled_set_values_device", "pem_tiled_set_values_f32",
     "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
     "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan", "pem_tiled_ewise", "pem_tiled_set_values_from_ewise",
-    "pem_tiled_export_csr", "pem_tiled_export_csr_f32",
+    "pem_tiled_export_csr", "pem_tiled_export_csr_f32", "pem_tiled_select", "pem_tiled_set_values_from_select",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
 EWISE_PATTERNS = dict(union=0, intersect=1)
 BINOPS = dict(plus=0, times=1, min=2, max=3, lor=4, land=5)
+
+# enum pem_select_op (include/pem_spgemm.h): Tiled.select's ops, by value; the first eight are positional
+SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
+              "value_gt", "value_ge", "abs_gt")
+POSITIONAL_SELECT_OPS = SELECT_OPS[:8]
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
 VALUE_ORDERS = dict(row=0, col=1)
@@ -317,6 +322,21 @@ class Tiled:
         """Refresh a tiling made by ewise(A, B, ...) from A's and B's current values, in place.  Ordered on the context's stream;
         returns without waiting."""
         _check(lib().pem_tiled_set_values_from_ewise(self.ctx._h, self._h, A._h, B._h))
+
+    def select(self, op, thunk=0):
+        """Select: a new tiling of this one's shape and dtype holding exactly the stored entries that satisfy
+        op (one of SELECT_OPS) with the thunk -- an integer k for the positional ops, a value (rounded to the dtype) for the value ops.
+        Values are copied bit for bit.  Waits."""
+        if op not in SELECT_OPS:
+            raise ValueError(f"unknown select op {op!r}; one of {SELECT_OPS}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_select(self.ctx._h, self._h, SELECT_OPS.index(op), C.c_double(float(thunk)), C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_select(self, A):
+        """Refresh a tiling made by A.select(op, k) with a positional op from A's current values, in place.  Ordered on the context's
+        stream; returns without waiting."""
+        _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
 
     def export_csr(self):
         """(rowptr int32[rows + 1], colidx int32[nnz], vals[nnz] in the tiling's dtype): the tiled matrix as canonical CSR."""

@@ -327,6 +327,13 @@ struct pem_tiled {
     double ew_alpha = 1.0, ew_beta = 1.0;
     pem::DevBuf ew_src, ew_map;
     bool ew_map_ready = false;
+    // a tiling made by pem_tiled_select (select.hip): its source's serial (0: not made so), the op and thunk, A's tile feeding every
+    // tile (int[T]), and on its first pem_tiled_set_values_from_select the int32[nnz] slot of every entry's value in A's vals
+    uint64_t sel_a_serial = 0;
+    int sel_op = 0;
+    double sel_thunk = 0.0;
+    pem::DevBuf sel_src, sel_map;
+    bool sel_map_ready = false;
 };
 
 struct pem_cplan {

@@ -1,0 +1,426 @@
+// select.hip -- entries of a tiling kept by position or by value (include/pem_spgemm.h, pem_tiled_select /
+// pem_tiled_set_values_from_select): R holds exactly the stored entries of A that satisfy the predicate, values copied bit for bit.
+//
+// R's tiles are a subsequence of A's and R's entries a subsequence of A's, both in A's order, so the route needs no sort and no
+// search outside a wave.  It ends, like chain.hip and ewise.hip, at the sorted tile payload derive_tiled (convert.hip) starts from:
+//   new row masks   positional ops: one lane per A tile ANDs A's 16 row masks with the band rows of the predicate, computed from the
+//                   tile's key, the row and k (a tile wholly inside or outside the band gets full or empty band rows; no per-bit
+//                   work anywhere).  Value ops: one wave per 64 A tiles, one ENTRY per lane over A's rowcolidx and vals; the keep
+//                   bits are ORed into the tiles' masks in LDS.  Either kernel also writes every tile's kept count and a non-empty
+//                   flag (one lane per tile popcounts the new masks).
+//   scans           one pair scan: the counts give every A tile's entry offset in R, the flags its tile id in R.
+//   payload         one wave per 64 A tiles, one ENTRY of A per lane (ew_fill_kernel's shape): the tiles' new masks and row
+//                   prefixes in LDS; a kept entry's slot in R is its R tile's offset + the new row prefix + the popcount of the new
+//                   row mask below c.  It writes R's tile_keys, tile_nnz_ptr, rowcolidx, tile-head scan and vals, and the A tile
+//                   of every R tile (kept with R for the refresh).
+//   derive_tiled    everything else.
+// Refresh (positional ops only: their pattern does not depend on A's values): the first call fills an int32 per entry of R, the
+// slot of its value in A's vals (one wave per 64 R tiles, the source tile's tile_rec word of the entry's row, as ewise decodes an
+// operand slot); every call is then one entry-parallel gather into vals and vals_t (through the tiling's vmap_t).
+#include "spgemm_internal.h"
+#include "tiled_internal.h"
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <memory>
+
+using namespace pem;
+
+// ------------------------------------------------------------------------------------------
+// the predicates (header comment of pem_tiled_select)
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned sel_cols_le(long long d)   // columns c <= d of a row, as a 16-bit mask
+{
+    return d < 0 ? 0u : d >= 15 ? 0xFFFFu : (2u << d) - 1u;
+}
+
+__device__ __forceinline__ unsigned sel_cols_ge(long long d)   // columns c >= d
+{
+    return d <= 0 ? 0xFFFFu : d > 15 ? 0u : (0xFFFFu << d) & 0xFFFFu;
+}
+
+// the columns of matrix row i that the positional op keeps in the tile whose first column is j0 (j = j0 + c)
+__device__ __forceinline__ unsigned sel_band_row(int op, long long i, long long j0, long long k)
+{
+    const long long d = i + k - j0;   // j == i + k  <=>  c == d
+    switch (op) {
+    case PEM_SELECT_TRIL: return sel_cols_le(d);
+    case PEM_SELECT_TRIU: return sel_cols_ge(d);
+    case PEM_SELECT_DIAG: return d >= 0 && d <= 15 ? 1u << d : 0u;
+    case PEM_SELECT_OFFDIAG: return d >= 0 && d <= 15 ? 0xFFFFu & ~(1u << d) : 0xFFFFu;
+    case PEM_SELECT_ROW_LE: return i <= k ? 0xFFFFu : 0u;
+    case PEM_SELECT_ROW_GT: return i > k ? 0xFFFFu : 0u;
+    case PEM_SELECT_COL_LE: return sel_cols_le(k - j0);
+    default: return 0xFFFFu & ~sel_cols_le(k - j0);   // PEM_SELECT_COL_GT
+    }
+}
+
+// IEEE comparisons in the value type: a NaN x fails all but VALUE_NE; -0.0 == 0.0
+template <typename VT>
+__device__ __forceinline__ bool sel_keep_value(int op, VT x, VT y)
+{
+    switch (op) {
+    case PEM_SELECT_VALUE_EQ: return x == y;
+    case PEM_SELECT_VALUE_NE: return x != y;
+    case PEM_SELECT_VALUE_LT: return x < y;
+    case PEM_SELECT_VALUE_LE: return x <= y;
+    case PEM_SELECT_VALUE_GT: return x > y;
+    case PEM_SELECT_VALUE_GE: return x >= y;
+    default: return (x < VT(0) ? -x : x) > y;   // PEM_SELECT_ABS_GT (a NaN x stays NaN and fails)
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// new row masks and counts
+// ------------------------------------------------------------------------------------------
+// positional ops, one lane per A tile: nm (uint32[8T], word q = row 2q | row 2q+1 << 16, the tiling's layout) = A's masks AND the
+// band; cnt[t] its popcount, flag[t] = cnt[t] != 0
+__global__ void sel_band_kernel(const long long *__restrict__ keys, const uint16_t *__restrict__ masks, long long ta, int op, long long k,
+                                uint32_t *__restrict__ nm, int *__restrict__ cnt, int *__restrict__ flag)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ta) return;
+    const long long key = keys[t];
+    const long long i0 = 16 * (key >> 32), j0 = 16 * (key & 0xFFFFFFFFll);
+    const uint4 *pm = reinterpret_cast<const uint4 *>(masks + 16 * t);
+    const uint4 m0 = pm[0], m1 = pm[1];
+    unsigned w[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        w[q] &= sel_band_row(op, i0 + 2 * q, j0, k) | sel_band_row(op, i0 + 2 * q + 1, j0, k) << 16;
+        n += __popc(w[q]);
+    }
+    uint4 *po = reinterpret_cast<uint4 *>(nm + 8 * t);
+    po[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    po[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    cnt[t] = n;
+    flag[t] = n != 0;
+}
+
+// value ops: one wave per chunk of 64 consecutive A tiles, one ENTRY per lane.  Lane = tile first: its entry offset stays in the
+// lane's register; then every lane takes one entry of the chunk (its tile by a shuffle search over the offsets), tests its value and
+// ORs the keep bit into the tile's mask word in LDS.  Lane = tile again: nm, cnt and flag as sel_band_kernel writes them.
+template <typename VT>
+__global__ void __launch_bounds__(256) sel_value_kernel(const int *__restrict__ a_ptr, const uint8_t *__restrict__ a_rci,
+                                                        const VT *__restrict__ a_vals, long long ta, int op, VT y, uint32_t *__restrict__ nm,
+                                                        int *__restrict__ cnt, int *__restrict__ flag)
+{
+    __shared__ unsigned s_mw[4 * 8 * 64];   // [wave][word q][tile]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
+    if (t0 >= ta) return;   // (wave-uniform)
+    unsigned *const my_mw = s_mw + wv * 512;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) my_mw[q * 64 + lane] = 0u;
+    const int ntl = ta - t0 < 64 ? (int)(ta - t0) : 64;
+    const bool live = lane < ntl;
+    const long long o = t0 + (live ? lane : 0);
+    const int my_off = live ? a_ptr[o] : INT_MAX;
+    const int e_end = a_ptr[t0 + ntl];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int e_begin = __shfl(my_off, 0, 64);
+    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
+        const int e = ebase + lane;
+        int ti = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {
+            const int probe = __shfl(my_off, ti + step, 64);
+            if (probe <= e) ti += step;
+        }
+        if (e >= e_end) continue;
+        const unsigned rc = a_rci[e];
+        if (sel_keep_value<VT>(op, a_vals[e], y)) atomicOr(&my_mw[(rc >> 5) * 64 + ti], 1u << ((rc & 15u) + 16u * ((rc >> 4) & 1u)));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!live) return;
+    unsigned w[8];
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        w[q] = my_mw[q * 64 + lane];
+        n += __popc(w[q]);
+    }
+    uint4 *po = reinterpret_cast<uint4 *>(nm + 8 * o);
+    po[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    po[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    cnt[o] = n;
+    flag[o] = n != 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// payload
+// ------------------------------------------------------------------------------------------
+// One wave per chunk of 64 consecutive A tiles, one ENTRY of A per lane.  Lane = tile first: the tile's new masks and their row
+// prefixes go to LDS; its A entry offset, R entry offset (roff, the scanned counts) and R tile id (rid, the scanned flags) stay in
+// registers, and a tile that keeps entries writes R's tile_keys, tile_nnz_ptr and sel_src there.  Then every lane takes one entry of
+// the chunk: its tile by a shuffle search, its (r, c) from A's rowcolidx; if the new mask holds it, its slot in R is the R tile's
+// offset + the new prefix of row r + the popcount of the new row mask below c (the order of A is kept).  roff and rid have ta + 1
+// entries (roff[ta] = R's nnz, rid[ta] = R's tiles).
+template <typename VT>
+__global__ void __launch_bounds__(256) sel_fill_kernel(const long long *__restrict__ a_keys, const int *__restrict__ a_ptr,
+                                                       const uint8_t *__restrict__ a_rci, const VT *__restrict__ a_vals, long long ta,
+                                                       const uint32_t *__restrict__ nm, const int *__restrict__ roff, const int *__restrict__ rid,
+                                                       long long *__restrict__ tile_keys, int *__restrict__ tile_nnz_ptr, int *__restrict__ src,
+                                                       uint8_t *__restrict__ rowcolidx, int *__restrict__ headx, VT *__restrict__ vals)
+{
+    __shared__ __attribute__((aligned(16))) uint4 s_rp[4 * 64];   // [wave][tile] prefix counts of the tile's new rows, a byte each
+    __shared__ unsigned s_mw[4 * 8 * 64];                         // [wave][word q][tile]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
+    if (t0 == 0 && lane == 0) {   // closing offsets: tile_nnz_ptr[T] = nnz, headx[nnz] = T
+        const int nnz = roff[ta], nt = rid[ta];
+        tile_nnz_ptr[nt] = nnz;
+        headx[nnz] = nt;
+    }
+    if (t0 >= ta) return;   // (wave-uniform)
+    uint4 *const my_rp = s_rp + wv * 64;
+    unsigned *const my_mw = s_mw + wv * 512;
+    const int ntl = ta - t0 < 64 ? (int)(ta - t0) : 64;
+    const bool live = lane < ntl;
+    const long long o = t0 + (live ? lane : 0);
+    unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (live) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(nm + 8 * o);
+        const uint4 n0 = p[0], n1 = p[1];
+        w[0] = n0.x, w[1] = n0.y, w[2] = n0.z, w[3] = n0.w, w[4] = n1.x, w[5] = n1.y, w[6] = n1.z, w[7] = n1.w;
+    }
+    const int my_off = live ? a_ptr[o] : INT_MAX;
+    const int e_end = a_ptr[t0 + ntl];
+    const int r_off = live ? roff[o] : 0, r_id = live ? rid[o] : 0;
+    unsigned rp[4] = {0, 0, 0, 0};   // row r's prefix in byte r & 3 of rp[r >> 2]
+    {
+        int run = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            rp[q >> 1] |= (unsigned)run << (16 * (q & 1));
+            run += __popc(w[q] & 0xFFFFu);
+            rp[q >> 1] |= (unsigned)run << (16 * (q & 1) + 8);
+            run += __popc(w[q] >> 16);
+        }
+        if (live && run != 0) {
+            tile_keys[r_id] = a_keys[o];
+            tile_nnz_ptr[r_id] = r_off;
+            src[r_id] = (int)o;
+        }
+    }
+    my_rp[lane] = make_uint4(rp[0], rp[1], rp[2], rp[3]);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) my_mw[q * 64 + lane] = w[q];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int e_begin = __shfl(my_off, 0, 64);
+    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
+        const int e = ebase + lane;
+        int ti = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {
+            const int probe = __shfl(my_off, ti + step, 64);
+            if (probe <= e) ti += step;
+        }
+        const int ro = __shfl(r_off, ti, 64), rd = __shfl(r_id, ti, 64);
+        if (e >= e_end) continue;
+        const unsigned rc = a_rci[e];
+        const unsigned r = rc >> 4, c = rc & 15u;
+        const unsigned word = my_mw[(r >> 1) * 64 + ti];
+        const unsigned m = (r & 1u) ? word >> 16 : word & 0xFFFFu;
+        if (!((m >> c) & 1u)) continue;
+        const uint4 rp4 = my_rp[ti];
+        const unsigned d = (r >> 2) == 0 ? rp4.x : (r >> 2) == 1 ? rp4.y : (r >> 2) == 2 ? rp4.z : rp4.w;
+        const int n = (int)((d >> (8 * (r & 3u))) & 0xFFu) + __popc(m & ((1u << c) - 1u));
+        const int slot = ro + n;
+        rowcolidx[slot] = (uint8_t)rc;
+        headx[slot] = n == 0 ? rd : rd + 1;
+        vals[slot] = a_vals[e];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// refresh
+// ------------------------------------------------------------------------------------------
+// the refresh map, once: one wave per chunk of 64 consecutive R tiles, one entry of R per lane; the entry's (r, c) from R's
+// rowcolidx, its slot in A's vals from the source tile's tile_rec word of row r (intra-tile row pointer + popcount below c)
+__global__ void __launch_bounds__(256) sel_map_kernel(const int *__restrict__ src, long long nt, const int *__restrict__ r_ptr,
+                                                      const uint8_t *__restrict__ r_rci, const int *__restrict__ a_ptr,
+                                                      const uint32_t *__restrict__ a_rec, int *__restrict__ map)
+{
+    const int lane = threadIdx.x & 63;
+    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
+    if (t0 >= nt) return;   // (wave-uniform)
+    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
+    const bool live = lane < ntl;
+    const long long o = t0 + (live ? lane : 0);
+    const int my_off = live ? r_ptr[o] : INT_MAX;
+    const int e_end = r_ptr[t0 + ntl];
+    const int s = live ? src[o] : 0;
+    const int a_off = live ? a_ptr[s] : 0;
+    const int e_begin = __shfl(my_off, 0, 64);
+    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
+        const int e = ebase + lane;
+        int ti = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {
+            const int probe = __shfl(my_off, ti + step, 64);
+            if (probe <= e) ti += step;
+        }
+        const int sx = __shfl(s, ti, 64), ao = __shfl(a_off, ti, 64);
+        if (e >= e_end) continue;
+        const unsigned rc = r_rci[e];
+        const uint32_t wa = a_rec[16 * (size_t)sx + (rc >> 4)];
+        map[e] = ao + (int)(wa >> 16) + __popc(wa & ((1u << (rc & 15u)) - 1u));
+    }
+}
+
+// one entry per lane: A's value through the map into vals[e] and vals_t[map_t[e]]
+template <typename VT>
+__global__ void __launch_bounds__(256) sel_refresh_kernel(const int *__restrict__ map, const int *__restrict__ map_t, size_t nnz,
+                                                          const VT *__restrict__ a_vals, VT *__restrict__ vals, VT *__restrict__ vals_t)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nnz) return;
+    const VT v = a_vals[map[e]];
+    vals[e] = v;
+    vals_t[map_t[e]] = v;
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+static bool sel_positional(int op) { return op >= PEM_SELECT_TRIL && op <= PEM_SELECT_COL_GT; }
+
+template <typename VT>
+static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled *R)
+{
+    hipStream_t st = ctx->stream;
+    R->value_bytes = A->value_bytes;
+    R->rows = A->rows;
+    R->cols = A->cols;
+    R->tile_rows = A->tile_rows;
+    R->tile_cols = A->tile_cols;
+    const size_t ta = (size_t)A->ntiles;
+    PEM_TRY(zero_flags(ctx));
+    DevBuf nm, roff, rid;   // per A tile: new masks (uint32[8]); kept count -> R entry offset; non-empty flag -> R tile id
+    PEM_TRY(nm.reserve(sizeof(uint32_t) * 8 * (ta + 1)));
+    PEM_TRY(roff.reserve(sizeof(int) * (ta + 4)));
+    PEM_TRY(rid.reserve(sizeof(int) * (ta + 4)));
+    if (ta) {
+        if (sel_positional(op))
+            PEM_LAUNCH(ctx, sel_band_kernel, grid_for(ta, 256), 256, A->tile_keys.as<long long>(), A->masks.as<uint16_t>(), (long long)ta, op,
+                       (long long)thunk, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>());
+        else
+            PEM_LAUNCH(ctx, sel_value_kernel<VT>, grid_for((ta + 63) / 64 * 64, 256), 256, A->tile_nnz_ptr.as<int>(), A->rowcolidx.as<uint8_t>(),
+                       A->vals.as<VT>(), (long long)ta, op, (VT)thunk, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>());
+    }
+    PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ta, ctx->d_scalars, ctx->d_scalars + 1));
+    int64_t tot[2] = {0, 0};
+    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
+    int hf[NUM_FLAGS];
+    PEM_TRY(read_flags(ctx, hf));
+    if (hf[FLAG_OVERFLOW] || tot[0] > 0x7FFFFFFFll) {
+        set_error("pem_tiled_select: the result's entries exceed the int32 index range");
+        return PEM_E_OVERFLOW;
+    }
+    PEM_TRY(check_internal(hf));
+    const size_t nnz = (size_t)tot[0], nt = (size_t)tot[1];
+    R->nnz = (int64_t)nnz;
+    R->ntiles = (int64_t)nt;
+    const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
+    PEM_TRY(reserve_tile_arrays(ctx, R));
+    PEM_TRY(R->tile_keys.reserve(sizeof(long long) * (nt + 1)));
+    PEM_TRY(R->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
+    PEM_TRY(R->vals.reserve(sizeof(VT) * (nnz + 1)));
+    PEM_TRY(R->rowcolidx.reserve(nnz + 16));
+    PEM_TRY(R->sel_src.reserve(sizeof(int) * (nt + 1)));
+    PEM_TRY(ctx->tmp[0].reserve(sizeof(int) * (nnz + 4)));
+    int *headx = ctx->tmp[0].as<int>();
+    PEM_HIP(hipMemsetAsync(R->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
+    PEM_HIP(hipMemsetAsync(headx, 0, sizeof(int), st));
+    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    if (ta)
+        PEM_LAUNCH(ctx, sel_fill_kernel<VT>, grid_for((ta + 63) / 64 * 64, 256), 256, A->tile_keys.as<long long>(), A->tile_nnz_ptr.as<int>(),
+                   A->rowcolidx.as<uint8_t>(), A->vals.as<VT>(), (long long)ta, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>(),
+                   R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->sel_src.as<int>(), R->rowcolidx.as<uint8_t>(), headx,
+                   R->vals.as<VT>());
+    return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
+}
+
+static bool select_args_ok(int op, double thunk, const char *fn)
+{
+    if (op < PEM_SELECT_TRIL || op > PEM_SELECT_ABS_GT) {
+        set_error("%s: unknown op %d (PEM_SELECT_TRIL .. PEM_SELECT_ABS_GT = 0 .. 14)", fn, op);
+        return false;
+    }
+    if (sel_positional(op) && !(std::floor(thunk) == thunk && std::fabs(thunk) <= 2147483648.0)) {
+        set_error("%s: the thunk of a positional op must be an integer k with |k| <= 2^31, not %g", fn, thunk);
+        return false;
+    }
+    return true;
+}
+
+extern "C" pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out)
+{
+    const char *fn = "pem_tiled_select";
+    if (!ctx || !A || !out) {
+        set_error("%s: null context, operand or output", fn);
+        return PEM_E_INVALID;
+    }
+    *out = nullptr;
+    if (!select_args_ok(op, thunk, fn)) return PEM_E_INVALID;
+    PEM_ENTER(ctx);
+    auto t0 = std::chrono::high_resolution_clock::now();
+    std::unique_ptr<pem_tiled> R(new pem_tiled());
+    pem_status s = A->value_bytes == 4 ? select_build<float>(ctx, A, op, thunk, R.get()) : select_build<double>(ctx, A, op, thunk, R.get());
+    (void)hipStreamSynchronize(ctx->stream);
+    if (s != PEM_OK) return s;
+    R->sel_a_serial = A->serial;
+    R->sel_op = op;
+    R->sel_thunk = thunk;
+    R->conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    *out = R.release();
+    return PEM_OK;
+}
+
+template <typename VT>
+static pem_status select_refresh(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A)
+{
+    const size_t nnz = (size_t)t->nnz, nt = (size_t)t->ntiles;
+    PEM_TRY(ensure_vmap_t(ctx, t));
+    if (!t->sel_map_ready) {   // once: every entry's slot in A's vals
+        PEM_TRY(t->sel_map.reserve(sizeof(int) * (nnz + 1)));
+        PEM_LAUNCH(ctx, sel_map_kernel, grid_for((nt + 63) / 64 * 64, 256), 256, t->sel_src.as<int>(), (long long)nt, t->tile_nnz_ptr.as<int>(),
+                   t->rowcolidx.as<uint8_t>(), A->tile_nnz_ptr.as<int>(), A->tile_rec.as<uint32_t>(), t->sel_map.as<int>());
+        t->sel_map_ready = true;
+    }
+    PEM_LAUNCH(ctx, sel_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->sel_map.as<int>(), t->vmap_t.as<int>(), nnz, A->vals.as<VT>(),
+               t->vals.as<VT>(), t->vals_t.as<VT>());
+    return PEM_OK;
+}
+
+extern "C" pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A)
+{
+    const char *fn = "pem_tiled_set_values_from_select";
+    if (!ctx || !t || !A) {
+        set_error("%s: null context, tiling or source", fn);
+        return PEM_E_INVALID;
+    }
+    if (t->sel_a_serial == 0 || t->sel_a_serial != A->serial) {
+        set_error("%s: the tiling was not made by pem_tiled_select from this A", fn);
+        return PEM_E_INVALID;
+    }
+    if (!sel_positional(t->sel_op)) {
+        set_error("%s: the tiling was made by a value predicate (op %d), whose pattern depends on A's values: select again instead", fn,
+                  t->sel_op);
+        return PEM_E_INVALID;
+    }
+    if (t->nnz) {
+        PEM_ENTER(ctx);
+        PEM_TRY(t->value_bytes == 4 ? select_refresh<float>(ctx, t, A) : select_refresh<double>(ctx, t, A));
+    }
+    ++t->value_version;
+    return PEM_OK;
+}

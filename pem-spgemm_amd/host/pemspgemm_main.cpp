@@ -340,6 +340,10 @@ int main(int argc, char *argv[])
     // `--add D.mtx [--alpha x] [--beta y]` computes C = alpha*(A*B) (+) beta*D on the device: the product's
     // C becomes a tiling (pem_tiled_from_cplan) and is combined with D over the union of their patterns (pem_tiled_ewise), (+) being
     // the semiring's additive op; --out then writes that sum.  D has C's shape and is read with --fp32 like A.
+    // `--select OP[:THUNK]` keeps the entries of the final result (C, or the sum of --add) that satisfy
+    // OP, one of tril triu diag offdiag row_le row_gt col_le col_gt (THUNK an integer k) or value_eq value_ne value_lt value_le
+    // value_gt value_ge abs_gt (THUNK a value); THUNK defaults to 0.  The result becomes a tiling (pem_tiled_from_cplan, or the
+    // ewise sum) and is filtered on the device (pem_tiled_select); --out then writes what is kept.  The CSV row describes the product.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
@@ -348,6 +352,7 @@ int main(int argc, char *argv[])
     int power = 0;   // --power K: A^K as K-1 chained products (0: off)
     const char *add_path = nullptr;   // --add D.mtx: C = alpha*(A*B) (+) beta*D
     double add_alpha = 1.0, add_beta = 1.0;
+    const char *select_spec = nullptr;   // --select OP[:THUNK]
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -370,6 +375,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--add") && r + 1 < argc) add_path = argv[++r];
             else if (!strcmp(argv[r], "--alpha") && r + 1 < argc) add_alpha = atof(argv[++r]);
             else if (!strcmp(argv[r], "--beta") && r + 1 < argc) add_beta = atof(argv[++r]);
+            else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -438,6 +444,39 @@ int main(int argc, char *argv[])
     } else if (add_alpha != 1.0 || add_beta != 1.0) {
         printf("--alpha / --beta need --add <D.mtx>. Exiting.\n");
         return 1;
+    }
+    // --select: the op by name (pem_select_op) and its thunk
+    static const char *const select_names[] = {"tril",     "triu",     "diag",     "offdiag",  "row_le",   "row_gt",   "col_le", "col_gt",
+                                               "value_eq", "value_ne", "value_lt", "value_le", "value_gt", "value_ge", "abs_gt"};
+    int select_op = -1;
+    double select_thunk = 0.0;
+    if (select_spec) {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : nullptr;
+        if (clash) {
+            printf("--select does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        const char *colon = strchr(select_spec, ':');
+        const std::string name = colon ? std::string(select_spec, (size_t)(colon - select_spec)) : std::string(select_spec);
+        for (int i = 0; i < 15; ++i)
+            if (name == select_names[i]) select_op = i;
+        if (select_op < 0) {
+            printf("--select %s: unknown op %s (tril, triu, diag, offdiag, row_le, row_gt, col_le, col_gt, value_eq, value_ne, value_lt, "
+                   "value_le, value_gt, value_ge, abs_gt). Exiting.\n", select_spec, name.c_str());
+            return 1;
+        }
+        if (colon) {
+            char *end = nullptr;
+            select_thunk = strtod(colon + 1, &end);
+            if (end == colon + 1 || *end != '\0') {
+                printf("--select %s: the thunk %s does not parse as a number. Exiting.\n", select_spec, colon + 1);
+                return 1;
+            }
+        }
+        if (select_op <= PEM_SELECT_COL_GT && !(std::floor(select_thunk) == select_thunk && std::fabs(select_thunk) <= 2147483648.0)) {
+            printf("--select %s: the positional op %s needs an integral thunk k with |k| <= 2^31. Exiting.\n", select_spec, name.c_str());
+            return 1;
+        }
     }
     if (ngpu > 0 && mask_path) {
         printf("--gpus does not combine with --mask (masked products run on one device). Exiting.\n");
@@ -792,6 +831,23 @@ int main(int argc, char *argv[])
                add_beta, ct.conv_ms, si.conv_ms, add_ms, (long long)si.nnz);
         pem_tiled_destroy(ctx, Ct);
     }
+    pem_tiled *Sel = nullptr;   // --select: the entries of C (or of the sum) that satisfy the op
+    if (select_op >= 0) {
+        auto s0 = std::chrono::high_resolution_clock::now();
+        pem_tiled *Src = Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        CHECK(pem_tiled_select(ctx, Src, select_op, select_thunk, &Sel));
+        const double sel_total_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - s0).count();
+        pem_tiled_info si, src;
+        CHECK(pem_tiled_get_info(Sel, &si));
+        CHECK(pem_tiled_get_info(Src, &src));
+        printf("select: %s:%g of %s: select %.2fms, total %.2fms, nnz %lld of %lld kept\n", select_names[select_op], select_thunk,
+               Sum ? "the sum" : "C", si.conv_ms, sel_total_ms, (long long)si.nnz, (long long)src.nnz);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
 
     int rc = 0;
     if (!save) {
@@ -817,20 +873,23 @@ int main(int argc, char *argv[])
             rc = 2;
         }
     }
-    if (out_path && Sum) {   // the sum as a Matrix-Market file (the tiling's CSR export)
+    pem_tiled *Res = Sel ? Sel : Sum;   // the final result when it is a tiling
+    if (out_path && Res) {   // the sum and / or the selection as a Matrix-Market file (the tiling's CSR export)
         pem_tiled_info si;
-        CHECK(pem_tiled_get_info(Sum, &si));
+        CHECK(pem_tiled_get_info(Res, &si));
         std::vector<int32_t> rp((size_t)si.rows + 1), cidx((size_t)si.nnz);
         std::vector<double> cv((size_t)si.nnz);
         int64_t nnz = 0;
         if (fp32) {
             std::vector<float> vf((size_t)si.nnz);
-            CHECK(pem_tiled_export_csr_f32(ctx, Sum, &nnz, rp.data(), cidx.data(), vf.data()));
+            CHECK(pem_tiled_export_csr_f32(ctx, Res, &nnz, rp.data(), cidx.data(), vf.data()));
             for (size_t e = 0; e < vf.size(); ++e) cv[e] = vf[e];
         } else {
-            CHECK(pem_tiled_export_csr(ctx, Sum, &nnz, rp.data(), cidx.data(), cv.data()));
+            CHECK(pem_tiled_export_csr(ctx, Res, &nnz, rp.data(), cidx.data(), cv.data()));
         }
-        const std::string comment = std::string("C = alpha*A*B + beta*D (") + semiring_names[semiring] + ") by pemspgemm (pem-spgemm_amd)";
+        std::string comment = Sum ? std::string("C = alpha*A*B + beta*D (") + semiring_names[semiring] + ")" : std::string("C = A*B (") + semiring_names[semiring] + ")";
+        if (Sel) comment += std::string(", select ") + select_spec;
+        comment += " by pemspgemm (pem-spgemm_amd)";
         if (pem_write_mtx_csr(out_path, si.rows, si.cols, rp.data(), cidx.data(), cv.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
             rc = 2;
@@ -862,6 +921,7 @@ int main(int argc, char *argv[])
     if (L != A) pem_tiled_destroy(ctx, L);
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
+    if (Sel) pem_tiled_destroy(ctx, Sel);
     if (Sum) pem_tiled_destroy(ctx, Sum);
     if (Dt) pem_tiled_destroy(ctx, Dt);
     pem_coo_free(&cd);
