@@ -334,6 +334,41 @@ typedef enum {
 pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out);
 pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
 
+/* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
+ * the fold of every row or column, on the device.
+ *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)
+ *                  y = A^T (+).(x) x  (transpose = 1: x has A.rows entries, y has A.cols)
+ *     dx and dy are device arrays of the tiling's value type on the context's device; their lengths cannot be checked, so the caller
+ *       provides them as above.  Coordinates are those of the matrix the tiling represents (what pem_tiled_export_csr returns): a
+ *       tiling built with transpose = 1 acts as M^T.  Any tiling works (converted, loaded, from_cplan, ewise, select).
+ *     Order.  Under plus-times y_i is the fma chain over row i's stored entries in ascending column, acc = fma(a_ij, x_j, acc), from 0
+ *       -- or from the old y_i with accumulate = 1; for transpose = 1 y_j is the same chain over column j's entries in ascending row.
+ *       The result equals, bit for bit, the plan product A*X (X: the A.cols x 1 tiling storing every x_j, zeros included) resp.
+ *       X^T*A, under every semiring (section 3g's rules: each a + x and a * x rounded once in the value type, fmin / fmax skip NaN,
+ *       plus_pair counts entries -- acc + 1 per entry -- reading neither x nor A's values, lor_land gives 1.0 / 0.0 with NaN != 0);
+ *       min / max results do not depend on order and the sign of a zero there is not specified.  fp32 tilings compute in fp32 (fmaf).
+ *       No atomics: two calls give identical bits.
+ *     Empty rows (columns).  accumulate = 0: the semiring's start value (0, +inf, -inf, -inf, 0, 0).  accumulate = 1: y is left
+ *       untouched there, and every other fold starts from the old y (lor_land: from y != 0).
+ *   pem_tiled_reduce  y_i = the (+)-fold of row i's (dim = PEM_REDUCE_ROWS: y has A.rows entries) or column j's (PEM_REDUCE_COLS:
+ *       A.cols entries) stored values, op a pem_binop: PLUS, TIMES, MIN, MAX, LOR, LAND.  A left fold in ascending index from the
+ *       identity (0, 1, +inf, -inf, 0, 1), or from the old y with accumulate = 1 (LOR / LAND: from y != 0), each step rounded once;
+ *       LOR / LAND give 1.0 / 0.0 (NaN != 0).  Empty rows get the identity (accumulate = 0) or stay untouched (accumulate = 1).
+ *       reduce(PLUS) equals mxv(plus_times, x = 1) bit for bit; MIN / MAX equal mxv(min_plus / max_plus, x = 0) up to the sign of a
+ *       zero; LOR equals mxv(lor_land, x = 1).
+ *   PEM_E_INVALID: a null context or tiling; a null dx (dy) where x (y) has entries; an unknown semiring, op or dim; transpose or
+ *     accumulate not 0 or 1; the fp64 form on an fp32 tiling or the reverse; x and y overlapping.  An empty tiling or a 0-length y is
+ *     legal.  Stream-ordered on the context's stream; never waits and reads nothing back (a launch failure surfaces at the next
+ *     synchronising call).  A's current values are read, so pem_tiled_set_values_device followed by an mxv needs no sync.  The first
+ *     column-orientation call (transpose = 1, PEM_REDUCE_COLS) on a tiling builds its column schedule -- 8 bytes per tile and 1 per
+ *     entry, carved from the context's arena and kept with the tiling (a captured graph re-captures once, as after the first
+ *     pem_tiled_set_values); every later call allocates nothing. */
+typedef enum { PEM_REDUCE_ROWS = 0, PEM_REDUCE_COLS = 1 } pem_reduce_dim;
+pem_status pem_tiled_mxv(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, const double *dx, double *dy, int accumulate);
+pem_status pem_tiled_mxv_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, const float *dx, float *dy, int accumulate);
+pem_status pem_tiled_reduce(pem_ctx *ctx, const pem_tiled *A, int op, int dim, double *dy, int accumulate);
+pem_status pem_tiled_reduce_f32(pem_ctx *ctx, const pem_tiled *A, int op, int dim, float *dy, int accumulate);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
     "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan", "pem_tiled_ewise", "pem_tiled_set_values_from_ewise",
     "pem_tiled_export_csr", "pem_tiled_export_csr_f32", "pem_tiled_select", "pem_tiled_set_values_from_select",
+    "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -60,6 +61,9 @@ BINOPS = dict(plus=0, times=1, min=2, max=3, lor=4, land=5)
 SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
               "value_gt", "value_ge", "abs_gt")
 POSITIONAL_SELECT_OPS = SELECT_OPS[:8]
+
+# enum pem_reduce_dim (include/pem_spgemm.h): Tiled.reduce folds every row or every column
+REDUCE_DIMS = dict(rows=0, cols=1)
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
 VALUE_ORDERS = dict(row=0, col=1)
@@ -337,6 +341,52 @@ class Tiled:
         """Refresh a tiling made by A.select(op, k) with a positional op from A's current values, in place.  Ordered on the context's
         stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
+
+    def _vector(self, fn, name, v, n):
+        """the device pointer of a torch tensor of n values of this tiling's dtype (the check of set_values_device)"""
+        if not hasattr(v, "data_ptr") or not v.is_cuda or v.numel() != n or not v.is_contiguous() or str(v.dtype) != f"torch.{self.dtype.name}":
+            got = f"{v.dtype} x {v.numel()} on {v.device}" if hasattr(v, "data_ptr") else type(v).__name__
+            raise ValueError(f"{fn}: want a contiguous device tensor of {n} {self.dtype.name} values for {name}, got {got}")
+        return C.c_void_p(v.data_ptr())
+
+    def _out(self, fn, out, n, like=None):
+        if out is None:
+            import torch
+            dev = like.device if like is not None else torch.device("cuda", self.ctx.device)
+            out = torch.empty(n, dtype=getattr(torch, self.dtype.name), device=dev)
+        return out, self._vector(fn, "out", out, n)
+
+    def mxv(self, x, semiring="plus_times", transpose=False, out=None, accumulate=False):
+        """Matrix-vector product: out = A (+).(x) x, or A^T (+).(x) x with transpose=True, under a
+        semiring of SEMIRINGS.  x: a contiguous device torch tensor of the tiling's dtype with cols (transpose: rows) entries; out: one
+        with rows (transpose: cols) entries, allocated when None.  Every output is the fold of its row's (column's) entries in
+        ascending index -- under plus_times the fma chain, bit for bit what CPlan(A, X) computes -- from the semiring's start value, or
+        from out's old value with accumulate=True (empty rows then stay as they are).  x and out must not overlap.  Ordered on the
+        context's stream and never waits: on a context created on the torch stream torch works on (s = torch.cuda.Stream(), Context(dev,
+        stream=s.cuda_stream), torch.cuda.set_stream(s) -- torch's default stream is the null stream, and stream=None gives the context
+        a stream of its own) torch reads out, and may write x, with no extra sync.  Returns out."""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        nx, ny = (self.rows, self.cols) if transpose else (self.cols, self.rows)
+        px = self._vector("mxv", "x", x, nx)
+        out, py = self._out("mxv", out, ny, like=x)
+        fn = lib().pem_tiled_mxv_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv
+        _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, py, int(bool(accumulate))))
+        return out
+
+    def reduce(self, op="plus", dim="rows", out=None, accumulate=False):
+        """Row or column reduction: out[i] = the left fold, in ascending index, of row i's (dim="cols":
+        column i's) stored values under op (one of BINOPS), from the op's identity -- or from out's old value with accumulate=True.
+        out: a contiguous device torch tensor of the tiling's dtype with rows (cols) entries, allocated when None.  Ordered on the
+        context's stream and never waits (a context on the torch stream torch works on needs no extra sync; see mxv).  Returns out."""
+        if op not in BINOPS:
+            raise ValueError(f"unknown op {op!r}; one of {sorted(BINOPS)}")
+        if dim not in REDUCE_DIMS:
+            raise ValueError(f"unknown dim {dim!r}; one of {sorted(REDUCE_DIMS)}")
+        out, py = self._out("reduce", out, self.cols if dim == "cols" else self.rows)
+        fn = lib().pem_tiled_reduce_f32 if self.value_bytes == 4 else lib().pem_tiled_reduce
+        _check(fn(self.ctx._h, self._h, BINOPS[op], REDUCE_DIMS[dim], py, int(bool(accumulate))))
+        return out
 
     def export_csr(self):
         """(rowptr int32[rows + 1], colidx int32[nnz], vals[nnz] in the tiling's dtype): the tiled matrix as canonical CSR."""

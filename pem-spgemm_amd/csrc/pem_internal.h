@@ -334,6 +334,11 @@ struct pem_tiled {
     double sel_thunk = 0.0;
     pem::DevBuf sel_src, sel_map;
     bool sel_map_ready = false;
+    // matrix-vector products and reductions (mxv.hip): the column walk's schedule, built on the first column-orientation call and
+    // then kept -- per CSC position the entry offset in column-walk order (int[T+1]) and its tile's first slot in vals_t (int[T]),
+    // and per slot of vals_t the entry's (c << 4) | r (uint8[nnz]).  The row walk reads the tiling's own arrays.
+    mutable pem::DevBuf mx_csc_off, mx_csc_base, mx_rci_t;
+    mutable bool mx_cols_ready = false;
 };
 
 struct pem_cplan {

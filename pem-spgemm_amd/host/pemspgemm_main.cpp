@@ -21,6 +21,7 @@
 #include "../../include/pem_host.h"
 #include "../../include/pem_mgpu.h"
 #include "../../include/pem_spgemm.h"
+#include <hip/hip_runtime_api.h>
 
 static int env_int(const char *name, int dflt)
 {
@@ -344,6 +345,9 @@ int main(int argc, char *argv[])
     // OP, one of tril triu diag offdiag row_le row_gt col_le col_gt (THUNK an integer k) or value_eq value_ne value_lt value_le
     // value_gt value_ge abs_gt (THUNK a value); THUNK defaults to 0.  The result becomes a tiling (pem_tiled_from_cplan, or the
     // ewise sum) and is filtered on the device (pem_tiled_select); --out then writes what is kept.  The CSV row describes the product.
+    // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
+    // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
+    // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
@@ -353,6 +357,7 @@ int main(int argc, char *argv[])
     const char *add_path = nullptr;   // --add D.mtx: C = alpha*(A*B) (+) beta*D
     double add_alpha = 1.0, add_beta = 1.0;
     const char *select_spec = nullptr;   // --select OP[:THUNK]
+    const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -376,6 +381,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--alpha") && r + 1 < argc) add_alpha = atof(argv[++r]);
             else if (!strcmp(argv[r], "--beta") && r + 1 < argc) add_beta = atof(argv[++r]);
             else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
+            else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -476,6 +482,31 @@ int main(int argc, char *argv[])
         if (select_op <= PEM_SELECT_COL_GT && !(std::floor(select_thunk) == select_thunk && std::fabs(select_thunk) <= 2147483648.0)) {
             printf("--select %s: the positional op %s needs an integral thunk k with |k| <= 2^31. Exiting.\n", select_spec, name.c_str());
             return 1;
+        }
+    }
+    // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op)
+    int reduce_dim = -1, reduce_op = add_ops[semiring];
+    if (reduce_spec) {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : nullptr;
+        if (clash) {
+            printf("--reduce does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        const char *colon = strchr(reduce_spec, ':');
+        const std::string dim = colon ? std::string(reduce_spec, (size_t)(colon - reduce_spec)) : std::string(reduce_spec);
+        reduce_dim = dim == "rows" ? PEM_REDUCE_ROWS : dim == "cols" ? PEM_REDUCE_COLS : -1;
+        if (reduce_dim < 0) {
+            printf("--reduce %s: unknown dimension %s (rows, cols). Exiting.\n", reduce_spec, dim.c_str());
+            return 1;
+        }
+        if (colon) {
+            reduce_op = -1;
+            for (int i = 0; i < 6; ++i)
+                if (!strcmp(colon + 1, add_op_names[i])) reduce_op = i;
+            if (reduce_op < 0) {
+                printf("--reduce %s: unknown op %s (plus, times, min, max, lor, land). Exiting.\n", reduce_spec, colon + 1);
+                return 1;
+            }
         }
     }
     if (ngpu > 0 && mask_path) {
@@ -849,6 +880,43 @@ int main(int argc, char *argv[])
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
 
+    std::vector<double> red;   // --reduce: the vector, on the host
+    if (reduce_dim >= 0) {
+        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Src, &si));
+        const size_t n = (size_t)(reduce_dim == PEM_REDUCE_COLS ? si.cols : si.rows);
+        const size_t vb = fp32 ? 4 : 8;
+        void *dy = nullptr;
+        if (hipMalloc(&dy, vb * n + 8) != hipSuccess) {
+            fprintf(stderr, "pemspgemm: --reduce: device allocation of %zu values failed\n", n);
+            return 2;
+        }
+        CHECK(pem_ctx_synchronize(ctx));
+        auto r0 = std::chrono::high_resolution_clock::now();
+        CHECK(fp32 ? pem_tiled_reduce_f32(ctx, Src, reduce_op, reduce_dim, (float *)dy, 0) : pem_tiled_reduce(ctx, Src, reduce_op, reduce_dim, (double *)dy, 0));
+        CHECK(pem_ctx_synchronize(ctx));
+        const double red_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - r0).count();
+        red.resize(n);
+        if (fp32) {
+            std::vector<float> f(n);
+            if (n && hipMemcpy(f.data(), dy, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+            for (size_t i = 0; i < n; ++i) red[i] = f[i];
+        } else if (n && hipMemcpy(red.data(), dy, 8 * n, hipMemcpyDeviceToHost) != hipSuccess) {
+            return 2;
+        }
+        (void)hipFree(dy);
+        double sum = 0.0;
+        for (double v : red) sum += v;
+        printf("reduce: %s %s of %s: reduce %.3fms, %zu values, host sum %.17g\n", reduce_dim == PEM_REDUCE_COLS ? "cols" : "rows",
+               add_op_names[reduce_op], Sel ? "the selection" : Sum ? "the sum" : "C", red_ms, n, sum);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+
     int rc = 0;
     if (!save) {
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
@@ -874,7 +942,22 @@ int main(int argc, char *argv[])
         }
     }
     pem_tiled *Res = Sel ? Sel : Sum;   // the final result when it is a tiling
-    if (out_path && Res) {   // the sum and / or the selection as a Matrix-Market file (the tiling's CSR export)
+    if (out_path && reduce_dim >= 0) {   // the reduced vector as a Matrix-Market dense array (n x 1)
+        FILE *f = fopen(out_path, "w");
+        bool ok = f != nullptr;
+        if (ok) {
+            ok = fprintf(f, "%%%%MatrixMarket matrix array real general\n%% reduce %s of C = A*B (%s) by pemspgemm (pem-spgemm_amd)\n%zu 1\n",
+                         reduce_spec, semiring_names[semiring], red.size()) > 0;
+            for (size_t i = 0; ok && i < red.size(); ++i) ok = fprintf(f, fp32 ? "%.9g\n" : "%.17g\n", red[i]) > 0;
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) {
+            fprintf(stderr, "pemspgemm: --out %s: cannot write the vector\n", out_path);
+            rc = 2;
+        } else {
+            printf("vector written to %s\n", out_path);
+        }
+    } else if (out_path && Res) {   // the sum and / or the selection as a Matrix-Market file (the tiling's CSR export)
         pem_tiled_info si;
         CHECK(pem_tiled_get_info(Res, &si));
         std::vector<int32_t> rp((size_t)si.rows + 1), cidx((size_t)si.nnz);
