@@ -15,12 +15,11 @@
 // then chain_count_t_kernel + scan give C^T's entry offsets and chain_gather_t_kernel writes C^T's payload: tiles in C's CSC
 // order, (c<<4|r) in (c, r) order, values from vals_t.  derive_tiled once more.
 //
-// Refresh: for C, vals = c_vals; for C^T, vals = c_vals gathered through cmap (the position of every entry's value in c_vals,
-// built on the first refresh).  vals_t through the tiling's vmap_t (values.hip).  One kernel, stream-ordered, no read-back.
+// Refresh: for C, vals = c_vals; for C^T, vals = c_vals gathered through the derivation's map (the position of every entry's value
+// in c_vals, built on the first refresh by chain_cmap_kernel).  vals_t through the tiling's vmap_t.  One kernel, values.hip's
+// refresh_gather (vals_refresh_kernel, identity or mapped form), stream-ordered, no read-back.
 #include "spgemm_internal.h"
 #include "tiled_internal.h"
-#include <chrono>
-#include <memory>
 
 using namespace pem;
 
@@ -150,43 +149,6 @@ __global__ void __launch_bounds__(256) chain_cmap_kernel(const int *__restrict__
     }
 }
 
-// refresh: v = c_vals[e] (C) or c_vals[cmap[e]] (C^T); vals[e] = vals_t[map_t[e]] = v.  Four entries per lane, like
-// vals_refresh_kernel; a plain copy through registers, so every bit pattern arrives unchanged.
-template <typename VT, bool MAPPED>
-__global__ void __launch_bounds__(256) chain_refresh_kernel(const VT *__restrict__ c_vals, const int *__restrict__ cmap, const int *__restrict__ map_t,
-                                                            size_t nnz, VT *__restrict__ vals, VT *__restrict__ vals_t)
-{
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t e = 4 * q;
-    if (e + 4 <= nnz) {
-        const int4 d = reinterpret_cast<const int4 *>(map_t)[q];
-        VT v0, v1, v2, v3;
-        if constexpr (MAPPED) {
-            const int4 s = reinterpret_cast<const int4 *>(cmap)[q];
-            v0 = c_vals[s.x], v1 = c_vals[s.y], v2 = c_vals[s.z], v3 = c_vals[s.w];
-        } else {
-            v0 = c_vals[e], v1 = c_vals[e + 1], v2 = c_vals[e + 2], v3 = c_vals[e + 3];
-        }
-        if constexpr (sizeof(VT) == 8) {
-            double2 *o = reinterpret_cast<double2 *>(vals + e);
-            o[0] = make_double2(v0, v1);
-            o[1] = make_double2(v2, v3);
-        } else {
-            reinterpret_cast<float4 *>(vals + e)[0] = make_float4(v0, v1, v2, v3);
-        }
-        vals_t[d.x] = v0;
-        vals_t[d.y] = v1;
-        vals_t[d.z] = v2;
-        vals_t[d.w] = v3;
-    } else {
-        for (size_t i = e; i < nnz; ++i) {
-            const VT v = MAPPED ? c_vals[cmap[i]] : c_vals[i];
-            vals[i] = v;
-            vals_t[map_t[i]] = v;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -197,30 +159,6 @@ static pem_status c_current(const pem_cplan *p, const char *fn)
         return PEM_E_STATE;
     }
     return c_values_current(p, fn);
-}
-
-static void set_shape(pem_tiled *T, int value_bytes, int rows, int cols, int64_t nnz, int64_t ntiles)
-{
-    T->value_bytes = value_bytes;
-    T->rows = rows;
-    T->cols = cols;
-    T->nnz = nnz;
-    T->ntiles = ntiles;
-    T->tile_rows = (rows + 15) / 16;
-    T->tile_cols = (cols + 15) / 16;
-}
-
-// the payload arrays derive_tiled starts from, and the tile-head scan in ctx->tmp[0]
-static pem_status reserve_payload(pem_ctx *ctx, pem_tiled *T)
-{
-    const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
-    PEM_TRY(reserve_tile_arrays(ctx, T));
-    PEM_TRY(T->tile_keys.reserve(sizeof(long long) * (nt + 1)));
-    PEM_TRY(T->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
-    PEM_TRY(T->vals.reserve((size_t)T->value_bytes * (nnz + 1)));
-    PEM_TRY(T->rowcolidx.reserve(nnz + 16));
-    PEM_TRY(ctx->tmp[0].reserve(sizeof(int) * (nnz + 4)));
-    return PEM_OK;
 }
 
 // C's tiling (the plan's full shape A.rows x B.cols) into T
@@ -242,13 +180,13 @@ static pem_status c_tiling(pem_ctx *ctx, const pem_cplan *p, pem_tiled *T)
         PEM_TRY(read_flags(ctx, hf));
         PEM_TRY(check_internal(hf));
     }
-    set_shape(T, p->A->value_bytes, p->A->rows, p->B->cols, (int64_t)nnz, nt);
+    set_tiled_shape(T, p->A->value_bytes, p->A->rows, p->B->cols);
+    T->nnz = (int64_t)nnz;
+    T->ntiles = nt;
     const int bits_tr = bits_for((uint64_t)T->tile_rows), bits_tc = bits_for((uint64_t)T->tile_cols);
     PEM_TRY(reserve_payload(ctx, T));
-    int *headx = ctx->tmp[0].as<int>();
-    PEM_HIP(hipMemsetAsync(T->tile_nnz_ptr.p, 0, sizeof(int) * ((size_t)nt + 1), st));
-    PEM_HIP(hipMemsetAsync(headx, 0, sizeof(int), st));
-    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    int *headx;
+    PEM_TRY(begin_payload(ctx, T, &headx));
     if (ntc)
         PEM_LAUNCH(ctx, chain_scatter_kernel, grid_for(16 * ntc, 256), 256, p->c_tile_nnz_ptr.as<int>(), p->c_tile_rowidx.as<int>(),
                    p->c_tile_colidx.as<int>(), p->c_mask.as<uint16_t>(), idx.as<int>(), (long long)ntc, T->tile_keys.as<long long>(),
@@ -261,17 +199,16 @@ static pem_status c_tiling(pem_ctx *ctx, const pem_cplan *p, pem_tiled *T)
 template <typename VT>
 static pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled *T)
 {
-    hipStream_t st = ctx->stream;
     const size_t nt = (size_t)Tc->ntiles;
-    set_shape(T, Tc->value_bytes, Tc->cols, Tc->rows, Tc->nnz, Tc->ntiles);
+    set_tiled_shape(T, Tc->value_bytes, Tc->cols, Tc->rows);
+    T->nnz = Tc->nnz;
+    T->ntiles = Tc->ntiles;
     const int bits_tr = bits_for((uint64_t)T->tile_rows), bits_tc = bits_for((uint64_t)T->tile_cols);
     PEM_TRY(reserve_payload(ctx, T));
     DevBuf cnt;
     PEM_TRY(cnt.reserve(sizeof(int) * (nt + 4)));
-    int *headx = ctx->tmp[0].as<int>();   // (Tc's head scan there is no longer read: derive_tiled synchronised)
-    PEM_HIP(hipMemsetAsync(T->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
-    PEM_HIP(hipMemsetAsync(headx, 0, sizeof(int), st));
-    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    int *headx;   // (ctx->tmp[0]: Tc's head scan there is no longer read, derive_tiled synchronised)
+    PEM_TRY(begin_payload(ctx, T, &headx));
     if (nt) {
         PEM_LAUNCH(ctx, chain_count_t_kernel, grid_for(nt, 256), 256, Tc->tile_offsets.as<int>(), Tc->tile_nnz_ptr.as<int>(), (long long)nt,
                    cnt.as<int>());
@@ -284,6 +221,20 @@ static pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled
     int hf[NUM_FLAGS];
     PEM_TRY(read_flags(ctx, hf));   // (the scan of the entry offsets gave up: nothing behind it is valid)
     return check_internal(hf);
+}
+
+// C's tiling into T, or C^T's from a C tiling of its own (freed once C^T is built)
+static pem_status cplan_build(pem_ctx *ctx, const pem_cplan *plan, int transpose, pem_tiled *T)
+{
+    T->derived.kind = Derivation::CPLAN;
+    T->derived.src[0] = plan->serial;
+    T->derived.op = transpose;
+    if (!transpose) return c_tiling(ctx, plan, T);
+    std::unique_ptr<pem_tiled> Tc(new pem_tiled());
+    pem_status s = c_tiling(ctx, plan, Tc.get());
+    if (s == PEM_OK) s = Tc->value_bytes == 4 ? transposed_tiling<float>(ctx, Tc.get(), T) : transposed_tiling<double>(ctx, Tc.get(), T);
+    (void)hipStreamSynchronize(ctx->stream);   // (C's tiling goes back to the arena)
+    return s;
 }
 
 extern "C" pem_status pem_tiled_from_cplan(pem_ctx *ctx, const pem_cplan *plan, int transpose, pem_tiled **out)
@@ -299,55 +250,25 @@ extern "C" pem_status pem_tiled_from_cplan(pem_ctx *ctx, const pem_cplan *plan, 
         return PEM_E_INVALID;
     }
     PEM_TRY(c_current(plan, fn));
-    PEM_ENTER(ctx);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    std::unique_ptr<pem_tiled> T(new pem_tiled());
-    pem_status s = c_tiling(ctx, plan, T.get());
-    if (s == PEM_OK && transpose) {
-        std::unique_ptr<pem_tiled> Tt(new pem_tiled());
-        s = T->value_bytes == 4 ? transposed_tiling<float>(ctx, T.get(), Tt.get()) : transposed_tiling<double>(ctx, T.get(), Tt.get());
-        (void)hipStreamSynchronize(ctx->stream);   // (C's tiling goes back to the arena)
-        T.swap(Tt);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (s != PEM_OK) return s;
-    T->src_plan_serial = plan->serial;
-    T->src_transpose = transpose;
-    T->conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    *out = T.release();
-    return PEM_OK;
+    return build_derived(ctx, out, [&](pem_tiled *T) { return cplan_build(ctx, plan, transpose, T); });
 }
 
-// cmap of a C^T tiling on its first refresh: counts in CSC order, scan, fill.  Stream-ordered, no read-back.
-static pem_status ensure_cmap(pem_ctx *ctx, pem_tiled *T)
+// the map of a C^T tiling on its first refresh: counts in CSC order, scan, fill.  Stream-ordered, no read-back.
+static pem_status build_cmap(pem_ctx *ctx, pem_tiled *T)
 {
-    if (T->cmap_ready) return PEM_OK;
     const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
-    DevBuf cbase;
-    PEM_TRY(arena_phase(ctx->arena, {{&T->cmap, sizeof(int) * (nnz + 4)}, {&cbase, sizeof(int) * (nt + 4)}}));
-    PEM_TRY(T->cmap.reserve(sizeof(int) * (nnz + 4)));
+    DevBuf &cmap = T->derived.map, cbase;
+    PEM_TRY(arena_phase(ctx->arena, {{&cmap, sizeof(int) * (nnz + 4)}, {&cbase, sizeof(int) * (nt + 4)}}));
+    PEM_TRY(cmap.reserve(sizeof(int) * (nnz + 4)));
     PEM_TRY(cbase.reserve(sizeof(int) * (nt + 4)));
     if (nt) {
         PEM_LAUNCH(ctx, chain_count_t_kernel, grid_for(nt, 256), 256, T->tile_offsets.as<int>(), T->tile_nnz_ptr.as<int>(), (long long)nt,
                    cbase.as<int>());
         PEM_TRY(exclusive_scan_i32(ctx, cbase.as<int>(), cbase.as<int>(), nt, nullptr));
         PEM_LAUNCH(ctx, chain_cmap_kernel, grid_for(16 * nt, 256), 256, T->tile_offsets.as<int>(), T->tile_nnz_ptr.as<int>(),
-                   T->tile_rec.as<uint32_t>(), T->tile_rec_t.as<uint32_t>(), cbase.as<int>(), (long long)nt, T->cmap.as<int>());
+                   T->tile_rec.as<uint32_t>(), T->tile_rec_t.as<uint32_t>(), cbase.as<int>(), (long long)nt, cmap.as<int>());
     }
-    T->cmap_ready = true;
     return PEM_OK;
-}
-
-template <typename VT>
-static void launch_refresh(pem_ctx *ctx, pem_tiled *t, const pem_cplan *plan, size_t nnz)
-{
-    const unsigned grid = grid_for((nnz + 3) / 4, 256);
-    if (t->src_transpose)
-        PEM_LAUNCH_NAMED(ctx, "chain_refresh_kernel<mapped>", (chain_refresh_kernel<VT, true>), grid, 256, plan->c_vals.as<VT>(), t->cmap.as<int>(),
-                         t->vmap_t.as<int>(), nnz, t->vals.as<VT>(), t->vals_t.as<VT>());
-    else
-        PEM_LAUNCH_NAMED(ctx, "chain_refresh_kernel", (chain_refresh_kernel<VT, false>), grid, 256, plan->c_vals.as<VT>(), nullptr,
-                         t->vmap_t.as<int>(), nnz, t->vals.as<VT>(), t->vals_t.as<VT>());
 }
 
 extern "C" pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t, const pem_cplan *plan)
@@ -357,7 +278,7 @@ extern "C" pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t
         set_error("%s: null context, tiling or plan", fn);
         return PEM_E_INVALID;
     }
-    if (t->src_plan_serial == 0 || t->src_plan_serial != plan->serial) {
+    if (t->derived.kind != Derivation::CPLAN || t->derived.src[0] != plan->serial) {
         set_error("%s: the tiling was not made from this plan by pem_tiled_from_cplan", fn);
         return PEM_E_INVALID;
     }
@@ -366,16 +287,8 @@ extern "C" pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t
         set_error("%s: the plan's C has %lld entries, the tiling %lld", fn, (long long)plan->nnz_c, (long long)t->nnz);
         return PEM_E_INVALID;
     }
-    const size_t nnz = (size_t)t->nnz;
-    if (nnz) {
-        PEM_ENTER(ctx);
-        PEM_TRY(ensure_vmap_t(ctx, t));
-        if (t->src_transpose) PEM_TRY(ensure_cmap(ctx, t));
-        if (t->value_bytes == 4)
-            launch_refresh<float>(ctx, t, plan, nnz);
-        else
-            launch_refresh<double>(ctx, t, plan, nnz);
-    }
-    ++t->value_version;
-    return PEM_OK;
+    const bool tr = t->derived.op != 0;   // C^T: through the map; C: c_vals as it is
+    return refresh_derived(
+        ctx, t, [&] { return tr ? build_cmap(ctx, t) : PEM_OK; },
+        [&] { refresh_gather(ctx, t, plan->c_vals.p, tr ? t->derived.map.as<int>() : nullptr); });
 }

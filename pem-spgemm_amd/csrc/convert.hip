@@ -467,6 +467,47 @@ pem_status pem::reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T)
                         {&T->vals, (size_t)T->value_bytes * (nnz + 1)}, {&T->rowcolidx, nnz + 16}, {&ctx->tmp[0], 4 * (nnz + 4)}});
 }
 
+void pem::set_tiled_shape(pem_tiled *T, int value_bytes, int rows, int cols)
+{
+    T->value_bytes = value_bytes;
+    T->rows = rows;
+    T->cols = cols;
+    T->tile_rows = (rows + 15) / 16;
+    T->tile_cols = (cols + 15) / 16;
+}
+
+pem_status pem::reserve_payload(pem_ctx *ctx, pem_tiled *T)
+{
+    const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
+    PEM_TRY(reserve_tile_arrays(ctx, T));
+    PEM_TRY(T->tile_keys.reserve(sizeof(long long) * (nt + 1)));
+    PEM_TRY(T->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
+    PEM_TRY(T->vals.reserve((size_t)T->value_bytes * (nnz + 1)));
+    PEM_TRY(T->rowcolidx.reserve(nnz + 16));
+    PEM_TRY(ctx->tmp[0].reserve(sizeof(int) * (nnz + 4)));
+    return PEM_OK;
+}
+
+pem_status pem::begin_payload(pem_ctx *ctx, pem_tiled *T, int **headx)
+{
+    *headx = ctx->tmp[0].as<int>();
+    PEM_HIP(hipMemsetAsync(T->tile_nnz_ptr.p, 0, sizeof(int) * ((size_t)T->ntiles + 1), ctx->stream));
+    PEM_HIP(hipMemsetAsync(*headx, 0, sizeof(int), ctx->stream));
+    PEM_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
+    return PEM_OK;
+}
+
+pem_status pem::check_result_entries(pem_ctx *ctx, int64_t nnz, const char *fn)
+{
+    int hf[NUM_FLAGS];
+    PEM_TRY(read_flags(ctx, hf));
+    if (hf[FLAG_OVERFLOW] || nnz > 0x7FFFFFFFll) {
+        set_error("%s: the result's entries exceed the int32 index range", fn);
+        return PEM_E_OVERFLOW;
+    }
+    return check_internal(hf);
+}
+
 // Everything that follows from the sorted tile payload (tile_keys, tile_nnz_ptr, rowcolidx, vals): masks, intra-tile
 // row pointers, transposed masks (a5/a6), the step-3 records, the column-major values and the tile-level CSR/CSC
 // indices (a7).  Shared by the conversion, the cache loader and the tilings made from a plan's C (chain.hip).  headx = exclusive scan of the tile-head flags;
@@ -562,11 +603,7 @@ static pem_status build_tiled(pem_ctx *ctx, pem_tiled *T, DevBuf &k0, DevBuf &k1
     }
     T->ntiles = ntiles;
     const size_t nt = (size_t)ntiles;
-    PEM_TRY(reserve_tile_arrays(ctx, T));
-    PEM_TRY(T->tile_keys.reserve(sizeof(long long) * (nt + 1)));
-    PEM_TRY(T->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
-    PEM_TRY(T->vals.reserve((size_t)T->value_bytes * (nnz + 1)));
-    PEM_TRY(T->rowcolidx.reserve(nnz + 16));
+    PEM_TRY(reserve_payload(ctx, T));   // (head is ctx->tmp[0], already this size)
     PEM_HIP(hipMemsetAsync(T->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
     PEM_HIP(hipEventRecord(ctx->ev[6], st));
     if (nnz && T->value_bytes == 4)
@@ -593,12 +630,8 @@ static pem_status tiled_from_device(pem_ctx *ctx, int rows, int cols, int64_t nn
     PEM_ENTER(ctx);
     auto t0 = std::chrono::high_resolution_clock::now();
     pem_tiled *T = new pem_tiled();
-    T->value_bytes = value_bytes;
-    T->rows = transpose ? cols : rows;
-    T->cols = transpose ? rows : cols;
+    set_tiled_shape(T, value_bytes, transpose ? cols : rows, transpose ? rows : cols);
     T->nnz = nnz;
-    T->tile_rows = (T->rows + 15) / 16;
-    T->tile_cols = (T->cols + 15) / 16;
     const int bits_tr = bits_for((uint64_t)T->tile_rows), bits_tc = bits_for((uint64_t)T->tile_cols);
     pem_status s = PEM_OK;
     {
@@ -936,24 +969,15 @@ extern "C" pem_status pem_tiled_load(pem_ctx *ctx, const char *path, const pem_c
     PEM_ENTER(ctx);
     hipStream_t st = ctx->stream;
     pem_tiled *T = new pem_tiled();
-    T->value_bytes = (int)h.value_bytes;
-    T->rows = h.rows;
-    T->cols = h.cols;
+    set_tiled_shape(T, (int)h.value_bytes, h.rows, h.cols);
     T->nnz = h.nnz;
     T->ntiles = h.ntiles;
-    T->tile_rows = (T->rows + 15) / 16;
-    T->tile_cols = (T->cols + 15) / 16;
     const int bits_tr = bits_for((uint64_t)T->tile_rows), bits_tc = bits_for((uint64_t)T->tile_cols);
     const size_t nt = (size_t)h.ntiles, nnz = (size_t)h.nnz;
     auto body = [&]() -> pem_status {
         PEM_TRY(zero_flags(ctx));
-        PEM_TRY(reserve_tile_arrays(ctx, T));
-        PEM_TRY(T->tile_keys.reserve(sizeof(long long) * (nt + 1)));
-        PEM_TRY(T->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
-        PEM_TRY(T->vals.reserve((size_t)T->value_bytes * (nnz + 1)));
-        PEM_TRY(T->rowcolidx.reserve(nnz + 16));
+        PEM_TRY(reserve_payload(ctx, T));
         DevBuf &head = ctx->tmp[0];
-        PEM_TRY(head.reserve(sizeof(int) * (nnz + 4)));
         PEM_HIP(hipMemsetAsync(T->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
         if (nt) {
             PEM_HIP(hipMemcpyAsync(T->tile_keys.p, payload.data() + L.off_keys, sizeof(long long) * nt, hipMemcpyHostToDevice, st));

@@ -11,7 +11,8 @@
 //                       in B]; B's unmatched tile j at its lower bound in A + uscan[j].  (a tile's place in the merge is the
 //                       number of tiles of either list with a smaller key.)
 //                     INTERSECT: A's tiles whose B tile exists and whose ANDed masks are not empty are flagged and scanned.
-//                   Every R tile records its A and B source tiles (int2, -1: none) -- kept with R for the refresh.
+//                   Every R tile records its A and B source tiles (int2, -1: none) -- kept with R (derived.src_tiles) for the
+//                   refresh.
 //   counts          one lane per R tile: the 16 row masks ORed or ANDed, popcounted; a scan gives R's entry offsets.
 //   payload         one wave per 64 R tiles, one ENTRY per lane (ex_chunkfill_kernel's shape): the tiles' combined masks and row
 //                   prefixes in LDS; every entry decodes its tile, row and column and writes its (r<<4|c) byte, the tile-head scan
@@ -19,12 +20,10 @@
 //                   pointer (tile_rec >> 16) plus the popcount of the row-mask bits below c.  (A first form ran 16 lanes per tile,
 //                   lane = row: on webbase-1M's A^2 (+) A it took 1.14 ms, most lanes idle on tiles of a few entries.)
 //   derive_tiled    everything else.
-// Refresh: the same decode fills an int2 per entry (A slot, B slot, -1: none) on the first call; later calls are one
-// entry-parallel kernel that gathers both values, applies the op and writes vals and vals_t (through the tiling's vmap_t).
+// Refresh: the same decode fills an int2 per entry (A slot, B slot, -1: none; derived.map) on the first call; every call is then
+// one entry-parallel kernel that gathers both values, applies the op and writes vals and vals_t (through the tiling's vmap_t).
 #include "spgemm_internal.h"
 #include "tiled_internal.h"
-#include <chrono>
-#include <memory>
 
 using namespace pem;
 
@@ -209,37 +208,19 @@ __global__ void __launch_bounds__(256) ew_fill_kernel(const int2 *__restrict__ s
     const int my_off = live ? ptr[o] : 0x7FFFFFFF;
     const int e_end = ptr[t0 + ntl];
     const int a_off = s.x >= 0 ? A.nnz_ptr[s.x] : 0, b_off = s.y >= 0 ? B.nnz_ptr[s.y] : 0;
-    unsigned rp[4] = {0, 0, 0, 0};   // row r's prefix in byte r & 3 of rp[r >> 2]
-    {
-        int run = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            rp[q >> 1] |= (unsigned)run << (16 * (q & 1));
-            run += __popc(w[q] & 0xFFFFu);
-            rp[q >> 1] |= (unsigned)run << (16 * (q & 1) + 8);
-            run += __popc(w[q] >> 16);
-        }
-    }
-    my_rp[lane] = make_uint4(rp[0], rp[1], rp[2], rp[3]);
+    my_rp[lane] = row_prefixes(w);
 #pragma unroll
     for (int q = 0; q < 8; ++q) my_mw[q * 64 + lane] = w[q];
     if (!MAP && live) {
         tile_keys[o] = s.x >= 0 ? A.keys[s.x] : B.keys[s.y];
         tile_nnz_ptr[o] = my_off;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int e_begin = __shfl(my_off, 0, 64);
     for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
         const int e = ebase + lane;
         const bool valid = e < e_end;
-        int ti = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1) {
-            const int probe = __shfl(my_off, ti + step, 64);
-            if (probe <= e) ti += step;
-        }
+        const int ti = chunk_tile_of(my_off, e);
         const int toff = __shfl(my_off, ti, 64);
         const int sx = __shfl(s.x, ti, 64), sy = __shfl(s.y, ti, 64);
         const int ao = __shfl(a_off, ti, 64), bo = __shfl(b_off, ti, 64);
@@ -271,11 +252,10 @@ __global__ void __launch_bounds__(256) ew_fill_kernel(const int2 *__restrict__ s
         m = g2 ? m >> 2 : m;
         const bool g1 = k >= (m & 1u);
         const int c = (g8 ? 8 : 0) + (g4 ? 4 : 0) + (g2 ? 2 : 0) + (g1 ? 1 : 0);
-        const unsigned below = (1u << c) - 1u;
         const uint32_t wa = sx >= 0 ? A.rec[16 * (size_t)sx + r] : 0u, wb = sy >= 0 ? B.rec[16 * (size_t)sy + r] : 0u;
         const bool ha = (wa >> c) & 1u, hb = (wb >> c) & 1u;
-        const int sa = ha ? ao + (int)(wa >> 16) + __popc(wa & below) : -1;
-        const int sb = hb ? bo + (int)(wb >> 16) + __popc(wb & below) : -1;
+        const int sa = ha ? src_slot(ao, wa, c) : -1;
+        const int sb = hb ? src_slot(bo, wb, c) : -1;
         if constexpr (MAP) {
             map[e] = make_int2(sa, sb);
         } else {
@@ -322,7 +302,7 @@ static pem_status check_operands(const pem_tiled *A, const pem_tiled *B, const c
     return PEM_OK;
 }
 
-// R's sources per tile into R->ew_src (int2 per R tile); R->ntiles set
+// R's sources per tile into R->derived.src_tiles (int2 per R tile); R->ntiles set
 static pem_status match_tiles(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int pattern, pem_tiled *R)
 {
     const size_t ta = (size_t)A->ntiles, tb = (size_t)B->ntiles;
@@ -360,8 +340,8 @@ static pem_status match_tiles(pem_ctx *ctx, const pem_tiled *A, const pem_tiled 
     PEM_TRY(read_flags(ctx, hf));
     PEM_TRY(check_internal(hf));
     R->ntiles = nt;
-    PEM_TRY(R->ew_src.reserve(sizeof(int2) * ((size_t)nt + 1)));
-    if (nt) PEM_HIP(hipMemcpyAsync(R->ew_src.p, src.p, sizeof(int2) * (size_t)nt, hipMemcpyDeviceToDevice, ctx->stream));
+    PEM_TRY(R->derived.src_tiles.reserve(sizeof(int2) * ((size_t)nt + 1)));
+    if (nt) PEM_HIP(hipMemcpyAsync(R->derived.src_tiles.p, src.p, sizeof(int2) * (size_t)nt, hipMemcpyDeviceToDevice, ctx->stream));
     return PEM_OK;   // (src goes back to the arena: the copy was enqueued before anything that can reuse it)
 }
 
@@ -369,11 +349,15 @@ template <typename VT>
 static pem_status ewise_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const EwParams &prm, pem_tiled *R)
 {
     hipStream_t st = ctx->stream;
-    R->value_bytes = A->value_bytes;
-    R->rows = A->rows;
-    R->cols = A->cols;
-    R->tile_rows = A->tile_rows;
-    R->tile_cols = A->tile_cols;
+    set_tiled_shape(R, A->value_bytes, A->rows, A->cols);
+    Derivation &d = R->derived;
+    d.kind = Derivation::EWISE;
+    d.src[0] = A->serial;
+    d.src[1] = B->serial;
+    d.pattern = prm.pattern;
+    d.op = prm.op;
+    d.p0 = prm.alpha;
+    d.p1 = prm.beta;
     PEM_TRY(zero_flags(ctx));
     PEM_TRY(match_tiles(ctx, A, B, prm.pattern, R));
     const size_t nt = (size_t)R->ntiles;
@@ -381,32 +365,19 @@ static pem_status ewise_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled 
     PEM_TRY(ptr.reserve(sizeof(int) * (nt + 4)));
     PEM_HIP(hipMemsetAsync(ptr.p, 0, sizeof(int) * (nt + 1), st));
     if (nt)
-        PEM_LAUNCH(ctx, ew_count_kernel, grid_for(nt, 256), 256, R->ew_src.as<int2>(), (long long)nt, A->masks.as<uint16_t>(), B->masks.as<uint16_t>(),
+        PEM_LAUNCH(ctx, ew_count_kernel, grid_for(nt, 256), 256, d.src_tiles.as<int2>(), (long long)nt, A->masks.as<uint16_t>(), B->masks.as<uint16_t>(),
                    prm.pattern == PEM_EWISE_INTERSECT ? 1 : 0, ptr.as<int>());
     PEM_TRY(exclusive_scan_i32(ctx, ptr.as<int>(), ptr.as<int>(), nt, ctx->d_scalars));
     int64_t nnz = 0;
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 1, &nnz));
-    int hf[NUM_FLAGS];
-    PEM_TRY(read_flags(ctx, hf));
-    if (hf[FLAG_OVERFLOW] || nnz > 0x7FFFFFFFll) {
-        set_error("pem_tiled_ewise: the result's entries exceed the int32 index range");
-        return PEM_E_OVERFLOW;
-    }
-    PEM_TRY(check_internal(hf));
+    PEM_TRY(check_result_entries(ctx, nnz, "pem_tiled_ewise"));
     R->nnz = nnz;
     const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
-    PEM_TRY(reserve_tile_arrays(ctx, R));
-    PEM_TRY(R->tile_keys.reserve(sizeof(long long) * (nt + 1)));
-    PEM_TRY(R->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
-    PEM_TRY(R->vals.reserve(sizeof(VT) * ((size_t)nnz + 1)));
-    PEM_TRY(R->rowcolidx.reserve((size_t)nnz + 16));
-    PEM_TRY(ctx->tmp[0].reserve(sizeof(int) * ((size_t)nnz + 4)));
-    int *headx = ctx->tmp[0].as<int>();
-    PEM_HIP(hipMemsetAsync(R->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
-    PEM_HIP(hipMemsetAsync(headx, 0, sizeof(int), st));
-    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    PEM_TRY(reserve_payload(ctx, R));
+    int *headx;
+    PEM_TRY(begin_payload(ctx, R, &headx));
     if (nt)
-        PEM_LAUNCH(ctx, (ew_fill_kernel<VT, false>), grid_for((nt + 63) / 64 * 64, 256), 256, R->ew_src.as<int2>(), (long long)nt, ptr.as<int>(), side_of(A),
+        PEM_LAUNCH(ctx, (ew_fill_kernel<VT, false>), grid_for((nt + 63) / 64 * 64, 256), 256, d.src_tiles.as<int2>(), (long long)nt, ptr.as<int>(), side_of(A),
                    side_of(B), A->vals.as<VT>(), B->vals.as<VT>(), prm, R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(),
                    R->rowcolidx.as<uint8_t>(), headx, R->vals.as<VT>(), nullptr);
     return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
@@ -436,40 +407,35 @@ extern "C" pem_status pem_tiled_ewise(pem_ctx *ctx, const pem_tiled *A, const pe
     *out = nullptr;
     if (!params_ok(pattern, op, fn)) return PEM_E_INVALID;
     PEM_TRY(check_operands(A, B, fn));
-    PEM_ENTER(ctx);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    std::unique_ptr<pem_tiled> R(new pem_tiled());
     const EwParams prm{pattern, op, alpha, beta};
-    pem_status s = A->value_bytes == 4 ? ewise_build<float>(ctx, A, B, prm, R.get()) : ewise_build<double>(ctx, A, B, prm, R.get());
-    (void)hipStreamSynchronize(ctx->stream);
-    if (s != PEM_OK) return s;
-    R->ew_a_serial = A->serial;
-    R->ew_b_serial = B->serial;
-    R->ew_pattern = pattern;
-    R->ew_op = op;
-    R->ew_alpha = alpha;
-    R->ew_beta = beta;
-    R->conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    *out = R.release();
+    return build_derived(ctx, out, [&](pem_tiled *R) {
+        return A->value_bytes == 4 ? ewise_build<float>(ctx, A, B, prm, R) : ewise_build<double>(ctx, A, B, prm, R);
+    });
+}
+
+static EwParams params_of(const pem_tiled *t)
+{
+    return EwParams{t->derived.pattern, t->derived.op, t->derived.p0, t->derived.p1};
+}
+
+// the decode of the build, once: every entry's operand slots
+template <typename VT>
+static pem_status ewise_map(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
+{
+    const size_t nnz = (size_t)t->nnz, nt = (size_t)t->ntiles;
+    PEM_TRY(t->derived.map.reserve(sizeof(int2) * (nnz + 1)));
+    PEM_LAUNCH(ctx, (ew_fill_kernel<VT, true>), grid_for((nt + 63) / 64 * 64, 256), 256, t->derived.src_tiles.as<int2>(), (long long)nt,
+               t->tile_nnz_ptr.as<int>(), side_of(A), side_of(B), A->vals.as<VT>(), B->vals.as<VT>(), params_of(t), nullptr, nullptr, nullptr,
+               nullptr, nullptr, t->derived.map.as<int2>());
     return PEM_OK;
 }
 
 template <typename VT>
-static pem_status ewise_refresh(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
+static void ewise_refresh(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
 {
-    const size_t nnz = (size_t)t->nnz, nt = (size_t)t->ntiles;
-    const EwParams prm{t->ew_pattern, t->ew_op, t->ew_alpha, t->ew_beta};
-    PEM_TRY(ensure_vmap_t(ctx, t));
-    if (!t->ew_map_ready) {   // the decode of the build, once: every entry's operand slots
-        PEM_TRY(t->ew_map.reserve(sizeof(int2) * (nnz + 1)));
-        PEM_LAUNCH(ctx, (ew_fill_kernel<VT, true>), grid_for((nt + 63) / 64 * 64, 256), 256, t->ew_src.as<int2>(), (long long)nt, t->tile_nnz_ptr.as<int>(),
-                   side_of(A), side_of(B), A->vals.as<VT>(), B->vals.as<VT>(), prm, nullptr, nullptr, nullptr, nullptr, nullptr,
-                   t->ew_map.as<int2>());
-        t->ew_map_ready = true;
-    }
-    PEM_LAUNCH(ctx, ew_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->ew_map.as<int2>(), t->vmap_t.as<int>(), nnz, A->vals.as<VT>(),
-               B->vals.as<VT>(), prm, t->vals.as<VT>(), t->vals_t.as<VT>());
-    return PEM_OK;
+    const size_t nnz = (size_t)t->nnz;
+    PEM_LAUNCH(ctx, ew_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->derived.map.as<int2>(), t->vmap_t.as<int>(), nnz, A->vals.as<VT>(),
+               B->vals.as<VT>(), params_of(t), t->vals.as<VT>(), t->vals_t.as<VT>());
 }
 
 extern "C" pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
@@ -479,14 +445,12 @@ extern "C" pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t
         set_error("%s: null context, tiling or operand", fn);
         return PEM_E_INVALID;
     }
-    if (t->ew_a_serial == 0 || t->ew_a_serial != A->serial || t->ew_b_serial != B->serial) {
+    if (t->derived.kind != Derivation::EWISE || t->derived.src[0] != A->serial || t->derived.src[1] != B->serial) {
         set_error("%s: the tiling was not made by pem_tiled_ewise from this A and this B (in this order)", fn);
         return PEM_E_INVALID;
     }
-    if (t->nnz) {
-        PEM_ENTER(ctx);
-        PEM_TRY(t->value_bytes == 4 ? ewise_refresh<float>(ctx, t, A, B) : ewise_refresh<double>(ctx, t, A, B));
-    }
-    ++t->value_version;
-    return PEM_OK;
+    const bool f32 = t->value_bytes == 4;
+    return refresh_derived(
+        ctx, t, [&] { return f32 ? ewise_map<float>(ctx, t, A, B) : ewise_map<double>(ctx, t, A, B); },
+        [&] { f32 ? ewise_refresh<float>(ctx, t, A, B) : ewise_refresh<double>(ctx, t, A, B); });
 }

@@ -290,6 +290,24 @@ pem_status read_scalars(pem_ctx *ctx, const int64_t *d_src, int count, int64_t *
 // process-wide, unique per tiling created (never 0): what a tiling made from other tilings records (convert.hip)
 uint64_t next_tiled_serial();
 
+// The provenance of a derived tiling, which its pem_tiled_set_values_from_* checks and refreshes from:
+//   CPLAN   pem_tiled_from_cplan (chain.hip)   src[0] = the plan's serial; op = transpose.  map (C^T only): int32[nnz + 4], every
+//                                              entry's value position in the plan's c_vals.  C itself needs no map.
+//   EWISE   pem_tiled_ewise (ewise.hip)        src = A's and B's serials; op, pattern; p0, p1 = alpha, beta.  src_tiles: int2[T],
+//                                              A's and B's tile feeding every tile (-1: none).  map: int2[nnz], every entry's
+//                                              operand slots in A's and B's vals (-1: none).
+//   SELECT  pem_tiled_select (select.hip)      src[0] = A's serial; op; p0 = thunk.  src_tiles: int[T], A's tile feeding every tile.
+//                                              map: int32[nnz + 4], every entry's value slot in A's vals.
+// map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
+struct Derivation {
+    enum Kind { NONE, CPLAN, EWISE, SELECT } kind = NONE;
+    uint64_t src[2] = {0, 0};
+    int op = 0, pattern = 0;
+    double p0 = 0.0, p1 = 0.0;
+    DevBuf src_tiles, map;
+    bool map_ready = false;
+};
+
 }  // namespace pem
 
 struct pem_tiled {
@@ -312,28 +330,8 @@ struct pem_tiled {
     pem::DevBuf vmap_t;               // int32[nnz]: for every entry in tile order, its slot in vals_t
     bool vmap_ready[2] = {false, false}, vmap_t_ready = false;
     uint64_t value_version = 0;       // bumped by every refresh; a plan's C is current while it equals what step 3 read
-    // a tiling made from a plan's C (chain.hip, pem_tiled_from_cplan): the plan's serial (0: not made from a plan), whether it
-    // holds C^T, and for C^T the int32[nnz] map from every entry to its value's position in the plan's c_vals (first refresh)
-    uint64_t src_plan_serial = 0;
-    int src_transpose = 0;
-    pem::DevBuf cmap;
-    bool cmap_ready = false;
     uint64_t serial = pem::next_tiled_serial();
-    // a tiling made by pem_tiled_ewise (ewise.hip): its operands' serials (0: not made so), the pattern, op and scales it was made
-    // with, A's and B's tile feeding every tile (int2[T], -1: none), and on its first pem_tiled_set_values_from_ewise the int2[nnz]
-    // slots of every entry's operand values in A's and B's vals (-1: none)
-    uint64_t ew_a_serial = 0, ew_b_serial = 0;
-    int ew_pattern = 0, ew_op = 0;
-    double ew_alpha = 1.0, ew_beta = 1.0;
-    pem::DevBuf ew_src, ew_map;
-    bool ew_map_ready = false;
-    // a tiling made by pem_tiled_select (select.hip): its source's serial (0: not made so), the op and thunk, A's tile feeding every
-    // tile (int[T]), and on its first pem_tiled_set_values_from_select the int32[nnz] slot of every entry's value in A's vals
-    uint64_t sel_a_serial = 0;
-    int sel_op = 0;
-    double sel_thunk = 0.0;
-    pem::DevBuf sel_src, sel_map;
-    bool sel_map_ready = false;
+    pem::Derivation derived;          // what the tiling was made from, if it was made from a plan or from other tilings
     // matrix-vector products and reductions (mxv.hip): the column walk's schedule, built on the first column-orientation call and
     // then kept -- per CSC position the entry offset in column-walk order (int[T+1]) and its tile's first slot in vals_t (int[T]),
     // and per slot of vals_t the entry's (c << 4) | r (uint8[nnz]).  The row walk reads the tiling's own arrays.

@@ -12,17 +12,15 @@
 //   payload         one wave per 64 A tiles, one ENTRY of A per lane (ew_fill_kernel's shape): the tiles' new masks and row
 //                   prefixes in LDS; a kept entry's slot in R is its R tile's offset + the new row prefix + the popcount of the new
 //                   row mask below c.  It writes R's tile_keys, tile_nnz_ptr, rowcolidx, tile-head scan and vals, and the A tile
-//                   of every R tile (kept with R for the refresh).
+//                   of every R tile (kept with R, derived.src_tiles, for the refresh).
 //   derive_tiled    everything else.
 // Refresh (positional ops only: their pattern does not depend on A's values): the first call fills an int32 per entry of R, the
 // slot of its value in A's vals (one wave per 64 R tiles, the source tile's tile_rec word of the entry's row, as ewise decodes an
-// operand slot); every call is then one entry-parallel gather into vals and vals_t (through the tiling's vmap_t).
+// operand slot; derived.map); every call is then values.hip's refresh_gather, four entries per lane, into vals and vals_t.
 #include "spgemm_internal.h"
 #include "tiled_internal.h"
-#include <chrono>
 #include <climits>
 #include <cmath>
-#include <memory>
 
 using namespace pem;
 
@@ -118,25 +116,16 @@ __global__ void __launch_bounds__(256) sel_value_kernel(const int *__restrict__ 
     const long long o = t0 + (live ? lane : 0);
     const int my_off = live ? a_ptr[o] : INT_MAX;
     const int e_end = a_ptr[t0 + ntl];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int e_begin = __shfl(my_off, 0, 64);
     for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
         const int e = ebase + lane;
-        int ti = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1) {
-            const int probe = __shfl(my_off, ti + step, 64);
-            if (probe <= e) ti += step;
-        }
+        const int ti = chunk_tile_of(my_off, e);
         if (e >= e_end) continue;
         const unsigned rc = a_rci[e];
         if (sel_keep_value<VT>(op, a_vals[e], y)) atomicOr(&my_mw[(rc >> 5) * 64 + ti], 1u << ((rc & 15u) + 16u * ((rc >> 4) & 1u)));
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (!live) return;
     unsigned w[8];
     int n = 0;
@@ -157,7 +146,7 @@ __global__ void __launch_bounds__(256) sel_value_kernel(const int *__restrict__ 
 // ------------------------------------------------------------------------------------------
 // One wave per chunk of 64 consecutive A tiles, one ENTRY of A per lane.  Lane = tile first: the tile's new masks and their row
 // prefixes go to LDS; its A entry offset, R entry offset (roff, the scanned counts) and R tile id (rid, the scanned flags) stay in
-// registers, and a tile that keeps entries writes R's tile_keys, tile_nnz_ptr and sel_src there.  Then every lane takes one entry of
+// registers, and a tile that keeps entries writes R's tile_keys, tile_nnz_ptr and src there.  Then every lane takes one entry of
 // the chunk: its tile by a shuffle search, its (r, c) from A's rowcolidx; if the new mask holds it, its slot in R is the R tile's
 // offset + the new prefix of row r + the popcount of the new row mask below c (the order of A is kept).  roff and rid have ta + 1
 // entries (roff[ta] = R's nnz, rid[ta] = R's tiles).
@@ -192,37 +181,20 @@ __global__ void __launch_bounds__(256) sel_fill_kernel(const long long *__restri
     const int my_off = live ? a_ptr[o] : INT_MAX;
     const int e_end = a_ptr[t0 + ntl];
     const int r_off = live ? roff[o] : 0, r_id = live ? rid[o] : 0;
-    unsigned rp[4] = {0, 0, 0, 0};   // row r's prefix in byte r & 3 of rp[r >> 2]
-    {
-        int run = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            rp[q >> 1] |= (unsigned)run << (16 * (q & 1));
-            run += __popc(w[q] & 0xFFFFu);
-            rp[q >> 1] |= (unsigned)run << (16 * (q & 1) + 8);
-            run += __popc(w[q] >> 16);
-        }
-        if (live && run != 0) {
-            tile_keys[r_id] = a_keys[o];
-            tile_nnz_ptr[r_id] = r_off;
-            src[r_id] = (int)o;
-        }
+    const uint4 rp = row_prefixes(w);
+    if (live && (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0u) {   // (the tile keeps entries)
+        tile_keys[r_id] = a_keys[o];
+        tile_nnz_ptr[r_id] = r_off;
+        src[r_id] = (int)o;
     }
-    my_rp[lane] = make_uint4(rp[0], rp[1], rp[2], rp[3]);
+    my_rp[lane] = rp;
 #pragma unroll
     for (int q = 0; q < 8; ++q) my_mw[q * 64 + lane] = w[q];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int e_begin = __shfl(my_off, 0, 64);
     for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
         const int e = ebase + lane;
-        int ti = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1) {
-            const int probe = __shfl(my_off, ti + step, 64);
-            if (probe <= e) ti += step;
-        }
+        const int ti = chunk_tile_of(my_off, e);
         const int ro = __shfl(r_off, ti, 64), rd = __shfl(r_id, ti, 64);
         if (e >= e_end) continue;
         const unsigned rc = a_rci[e];
@@ -262,30 +234,12 @@ __global__ void __launch_bounds__(256) sel_map_kernel(const int *__restrict__ sr
     const int e_begin = __shfl(my_off, 0, 64);
     for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
         const int e = ebase + lane;
-        int ti = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1) {
-            const int probe = __shfl(my_off, ti + step, 64);
-            if (probe <= e) ti += step;
-        }
+        const int ti = chunk_tile_of(my_off, e);
         const int sx = __shfl(s, ti, 64), ao = __shfl(a_off, ti, 64);
         if (e >= e_end) continue;
         const unsigned rc = r_rci[e];
-        const uint32_t wa = a_rec[16 * (size_t)sx + (rc >> 4)];
-        map[e] = ao + (int)(wa >> 16) + __popc(wa & ((1u << (rc & 15u)) - 1u));
+        map[e] = src_slot(ao, a_rec[16 * (size_t)sx + (rc >> 4)], rc & 15u);
     }
-}
-
-// one entry per lane: A's value through the map into vals[e] and vals_t[map_t[e]]
-template <typename VT>
-__global__ void __launch_bounds__(256) sel_refresh_kernel(const int *__restrict__ map, const int *__restrict__ map_t, size_t nnz,
-                                                          const VT *__restrict__ a_vals, VT *__restrict__ vals, VT *__restrict__ vals_t)
-{
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nnz) return;
-    const VT v = a_vals[map[e]];
-    vals[e] = v;
-    vals_t[map_t[e]] = v;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -296,12 +250,11 @@ static bool sel_positional(int op) { return op >= PEM_SELECT_TRIL && op <= PEM_S
 template <typename VT>
 static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled *R)
 {
-    hipStream_t st = ctx->stream;
-    R->value_bytes = A->value_bytes;
-    R->rows = A->rows;
-    R->cols = A->cols;
-    R->tile_rows = A->tile_rows;
-    R->tile_cols = A->tile_cols;
+    set_tiled_shape(R, A->value_bytes, A->rows, A->cols);
+    R->derived.kind = Derivation::SELECT;
+    R->derived.src[0] = A->serial;
+    R->derived.op = op;
+    R->derived.p0 = thunk;
     const size_t ta = (size_t)A->ntiles;
     PEM_TRY(zero_flags(ctx));
     DevBuf nm, roff, rid;   // per A tile: new masks (uint32[8]); kept count -> R entry offset; non-empty flag -> R tile id
@@ -319,32 +272,19 @@ static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double 
     PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ta, ctx->d_scalars, ctx->d_scalars + 1));
     int64_t tot[2] = {0, 0};
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
-    int hf[NUM_FLAGS];
-    PEM_TRY(read_flags(ctx, hf));
-    if (hf[FLAG_OVERFLOW] || tot[0] > 0x7FFFFFFFll) {
-        set_error("pem_tiled_select: the result's entries exceed the int32 index range");
-        return PEM_E_OVERFLOW;
-    }
-    PEM_TRY(check_internal(hf));
+    PEM_TRY(check_result_entries(ctx, tot[0], "pem_tiled_select"));
     const size_t nnz = (size_t)tot[0], nt = (size_t)tot[1];
     R->nnz = (int64_t)nnz;
     R->ntiles = (int64_t)nt;
     const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
-    PEM_TRY(reserve_tile_arrays(ctx, R));
-    PEM_TRY(R->tile_keys.reserve(sizeof(long long) * (nt + 1)));
-    PEM_TRY(R->tile_nnz_ptr.reserve(sizeof(int) * (nt + 4)));
-    PEM_TRY(R->vals.reserve(sizeof(VT) * (nnz + 1)));
-    PEM_TRY(R->rowcolidx.reserve(nnz + 16));
-    PEM_TRY(R->sel_src.reserve(sizeof(int) * (nt + 1)));
-    PEM_TRY(ctx->tmp[0].reserve(sizeof(int) * (nnz + 4)));
-    int *headx = ctx->tmp[0].as<int>();
-    PEM_HIP(hipMemsetAsync(R->tile_nnz_ptr.p, 0, sizeof(int) * (nt + 1), st));
-    PEM_HIP(hipMemsetAsync(headx, 0, sizeof(int), st));
-    PEM_HIP(hipEventRecord(ctx->ev[6], st));
+    PEM_TRY(reserve_payload(ctx, R));
+    PEM_TRY(R->derived.src_tiles.reserve(sizeof(int) * (nt + 1)));
+    int *headx;
+    PEM_TRY(begin_payload(ctx, R, &headx));
     if (ta)
         PEM_LAUNCH(ctx, sel_fill_kernel<VT>, grid_for((ta + 63) / 64 * 64, 256), 256, A->tile_keys.as<long long>(), A->tile_nnz_ptr.as<int>(),
                    A->rowcolidx.as<uint8_t>(), A->vals.as<VT>(), (long long)ta, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>(),
-                   R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->sel_src.as<int>(), R->rowcolidx.as<uint8_t>(), headx,
+                   R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->derived.src_tiles.as<int>(), R->rowcolidx.as<uint8_t>(), headx,
                    R->vals.as<VT>());
     return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
 }
@@ -371,33 +311,18 @@ extern "C" pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op,
     }
     *out = nullptr;
     if (!select_args_ok(op, thunk, fn)) return PEM_E_INVALID;
-    PEM_ENTER(ctx);
-    auto t0 = std::chrono::high_resolution_clock::now();
-    std::unique_ptr<pem_tiled> R(new pem_tiled());
-    pem_status s = A->value_bytes == 4 ? select_build<float>(ctx, A, op, thunk, R.get()) : select_build<double>(ctx, A, op, thunk, R.get());
-    (void)hipStreamSynchronize(ctx->stream);
-    if (s != PEM_OK) return s;
-    R->sel_a_serial = A->serial;
-    R->sel_op = op;
-    R->sel_thunk = thunk;
-    R->conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
-    *out = R.release();
-    return PEM_OK;
+    return build_derived(ctx, out, [&](pem_tiled *R) {
+        return A->value_bytes == 4 ? select_build<float>(ctx, A, op, thunk, R) : select_build<double>(ctx, A, op, thunk, R);
+    });
 }
 
-template <typename VT>
-static pem_status select_refresh(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A)
+// once: every entry's slot in A's vals (nnz + 4 ints, as refresh_gather's four-entry loads want)
+static pem_status select_map(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A)
 {
     const size_t nnz = (size_t)t->nnz, nt = (size_t)t->ntiles;
-    PEM_TRY(ensure_vmap_t(ctx, t));
-    if (!t->sel_map_ready) {   // once: every entry's slot in A's vals
-        PEM_TRY(t->sel_map.reserve(sizeof(int) * (nnz + 1)));
-        PEM_LAUNCH(ctx, sel_map_kernel, grid_for((nt + 63) / 64 * 64, 256), 256, t->sel_src.as<int>(), (long long)nt, t->tile_nnz_ptr.as<int>(),
-                   t->rowcolidx.as<uint8_t>(), A->tile_nnz_ptr.as<int>(), A->tile_rec.as<uint32_t>(), t->sel_map.as<int>());
-        t->sel_map_ready = true;
-    }
-    PEM_LAUNCH(ctx, sel_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->sel_map.as<int>(), t->vmap_t.as<int>(), nnz, A->vals.as<VT>(),
-               t->vals.as<VT>(), t->vals_t.as<VT>());
+    PEM_TRY(t->derived.map.reserve(sizeof(int) * (nnz + 4)));
+    PEM_LAUNCH(ctx, sel_map_kernel, grid_for((nt + 63) / 64 * 64, 256), 256, t->derived.src_tiles.as<int>(), (long long)nt, t->tile_nnz_ptr.as<int>(),
+               t->rowcolidx.as<uint8_t>(), A->tile_nnz_ptr.as<int>(), A->tile_rec.as<uint32_t>(), t->derived.map.as<int>());
     return PEM_OK;
 }
 
@@ -408,19 +333,15 @@ extern "C" pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *
         set_error("%s: null context, tiling or source", fn);
         return PEM_E_INVALID;
     }
-    if (t->sel_a_serial == 0 || t->sel_a_serial != A->serial) {
+    if (t->derived.kind != Derivation::SELECT || t->derived.src[0] != A->serial) {
         set_error("%s: the tiling was not made by pem_tiled_select from this A", fn);
         return PEM_E_INVALID;
     }
-    if (!sel_positional(t->sel_op)) {
+    if (!sel_positional(t->derived.op)) {
         set_error("%s: the tiling was made by a value predicate (op %d), whose pattern depends on A's values: select again instead", fn,
-                  t->sel_op);
+                  t->derived.op);
         return PEM_E_INVALID;
     }
-    if (t->nnz) {
-        PEM_ENTER(ctx);
-        PEM_TRY(t->value_bytes == 4 ? select_refresh<float>(ctx, t, A) : select_refresh<double>(ctx, t, A));
-    }
-    ++t->value_version;
-    return PEM_OK;
+    return refresh_derived(
+        ctx, t, [&] { return select_map(ctx, t, A); }, [&] { refresh_gather(ctx, t, A->vals.p, t->derived.map.as<int>()); });
 }

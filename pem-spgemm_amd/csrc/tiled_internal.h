@@ -1,18 +1,70 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip).
+// ewise.hip, select.hip).  A derived tiling (chain.hip, ewise.hip, select.hip) is built by build_derived around its route: the shape
+// (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
+// provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.
 #pragma once
 #include "pem_internal.h"
+#include <chrono>
+#include <memory>
 
 namespace pem {
 
+// value_bytes, rows, cols and the tile grid (tile_rows, tile_cols); nnz and ntiles are the caller's (convert.hip)
+void set_tiled_shape(pem_tiled *T, int value_bytes, int rows, int cols);
 // sizing phase "tiles" of a tiling whose rows, cols, nnz, ntiles and value_bytes are set: every per-tile array (and the
 // nnz-sized payload) in one driver allocation
 pem_status reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T);
+// reserve_tile_arrays, then the payload derive_tiled starts from (tile_keys, tile_nnz_ptr, vals, rowcolidx) and the tile-head
+// scan in ctx->tmp[0], sized by T's nnz and ntiles
+pem_status reserve_payload(pem_ctx *ctx, pem_tiled *T);
+// where a derived route's payload kernels start: tile_nnz_ptr[0..ntiles] and headx[0] zeroed, ctx->ev[6] recorded;
+// *headx = ctx->tmp[0]
+pem_status begin_payload(pem_ctx *ctx, pem_tiled *T, int **headx);
 // everything that follows from the sorted tile payload (tile_keys, tile_nnz_ptr, rowcolidx, vals); headx[0..nnz] = exclusive
 // scan of the tile-head flags.  ctx->ev[6] must have been recorded where the caller's payload kernels start.  Synchronises.
 pem_status derive_tiled(pem_ctx *ctx, pem_tiled *T, const int *headx, int bits_tr, int bits_tc);
+// a derived route's size read-back: the flags (synchronises), then "<fn>: the result's entries exceed the int32 index range"
+// where the scan of the counts overflowed or nnz does not fit an int32, then check_internal
+pem_status check_result_entries(pem_ctx *ctx, int64_t nnz, const char *fn);
 // vmap_t (every entry's slot in vals_t) on first use (values.hip)
 pem_status ensure_vmap_t(pem_ctx *ctx, pem_tiled *T);
+// vals[e] = vals_t[vmap_t[e]] = src[map[e]], or src[e] where map is null (values.hip).  src holds T's value type; map is
+// 16-byte aligned with at least nnz + 4 ints.  vmap_t must be ready.
+void refresh_gather(pem_ctx *ctx, pem_tiled *T, const void *src, const int *map);
+
+// The shell of pem_tiled_from_cplan, pem_tiled_ewise and pem_tiled_select (their arguments checked, *out cleared): build(T) into
+// a fresh tiling, the time into conv_ms, synchronised; the tiling goes to *out on success and is freed otherwise.
+template <typename Build>
+pem_status build_derived(pem_ctx *ctx, pem_tiled **out, Build build)
+{
+    PEM_ENTER(ctx);
+    auto t0 = std::chrono::high_resolution_clock::now();
+    std::unique_ptr<pem_tiled> T(new pem_tiled());
+    pem_status s = build(T.get());
+    (void)hipStreamSynchronize(ctx->stream);
+    if (s != PEM_OK) return s;
+    T->conv_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    *out = T.release();
+    return PEM_OK;
+}
+
+// The tail of every pem_tiled_set_values_from_* (arguments and provenance checked): on a tiling with entries, vmap_t and the
+// derivation's map on the first call (build_map), then the refresh (launch); value_version bumped.  Stream-ordered, no read-back.
+template <typename BuildMap, typename Launch>
+pem_status refresh_derived(pem_ctx *ctx, pem_tiled *t, BuildMap build_map, Launch launch)
+{
+    if (t->nnz) {
+        PEM_ENTER(ctx);
+        PEM_TRY(ensure_vmap_t(ctx, t));
+        if (!t->derived.map_ready) {
+            PEM_TRY(build_map());
+            t->derived.map_ready = true;
+        }
+        launch();
+    }
+    ++t->value_version;
+    return PEM_OK;
+}
 
 // ---- device: tile lookups in a tiling's tile CSR (mask.hip, ewise.hip) ----
 // M's tile id at (i, j), -1 where M has none: binary search in M's tile row i (tile_colidx is sorted inside a row)
@@ -45,6 +97,51 @@ __device__ __forceinline__ int tile_lower_bound(const int *__restrict__ m_rowptr
             hi = mid;
     }
     return lo;
+}
+
+// ---- device: one wave per chunk of 64 consecutive tiles, one entry per lane (ewise.hip, select.hip) ----
+// the wave's LDS writes visible to the whole wave (each wave keeps its own LDS rows: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the chunk tile (lane) that holds entry e: my_off = the lane's tile's first entry, ascending over the lanes, INT_MAX past the
+// chunk's tiles.  A 6-step shuffle search.
+__device__ __forceinline__ int chunk_tile_of(const int my_off, const int e)
+{
+    int ti = 0;
+#pragma unroll
+    for (int step = 32; step > 0; step >>= 1) {
+        const int probe = __shfl(my_off, ti + step, 64);
+        if (probe <= e) ti += step;
+    }
+    return ti;
+}
+
+// a tile's row prefixes (entries of the rows above) from its 8 mask words (word q = row 2q | row 2q+1 << 16): row r's prefix in
+// byte r & 3 of component r >> 2
+__device__ __forceinline__ uint4 row_prefixes(const unsigned w[8])
+{
+    unsigned rp[4] = {0, 0, 0, 0};
+    int run = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        rp[q >> 1] |= (unsigned)run << (16 * (q & 1));
+        run += __popc(w[q] & 0xFFFFu);
+        rp[q >> 1] |= (unsigned)run << (16 * (q & 1) + 8);
+        run += __popc(w[q] >> 16);
+    }
+    return make_uint4(rp[0], rp[1], rp[2], rp[3]);
+}
+
+// the slot in a source tiling's vals of the entry in column c of a row whose tile_rec word is rec (row mask | entries of the
+// rows above << 16), in a tile whose first entry is off
+__device__ __forceinline__ int src_slot(const int off, const uint32_t rec, const unsigned c)
+{
+    return off + (int)(rec >> 16) + __popc(rec & ((1u << c) - 1u));
 }
 
 }  // namespace pem

@@ -104,19 +104,25 @@ __global__ void __launch_bounds__(256) vmap_t_kernel(const uint32_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// refresh: vals[e] = vals_t[map_t[e]] = V[map[e]], four entries per lane (16-byte map loads, 16/32-byte vals stores).
-// A plain copy through registers: every bit pattern (NaN payloads, -0.0, subnormals) arrives unchanged.
+// refresh: vals[e] = vals_t[map_t[e]] = V[map[e]] (MAPPED) or V[e], four entries per lane (16-byte map loads, 16/32-byte vals
+// stores).  A plain copy through registers: every bit pattern (NaN payloads, -0.0, subnormals) arrives unchanged.  Serves
+// pem_tiled_set_values* and the refresh of the tilings made from a plan's C (chain.hip) or by select (select.hip).
 // ------------------------------------------------------------------------------------------
-template <typename VT>
+template <typename VT, bool MAPPED>
 __global__ void __launch_bounds__(256) vals_refresh_kernel(const VT *__restrict__ V, const int *__restrict__ map, const int *__restrict__ map_t,
                                                            size_t nnz, VT *__restrict__ vals, VT *__restrict__ vals_t)
 {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t e = 4 * q;
     if (e + 4 <= nnz) {
-        const int4 s = reinterpret_cast<const int4 *>(map)[q];
         const int4 d = reinterpret_cast<const int4 *>(map_t)[q];
-        const VT v0 = V[s.x], v1 = V[s.y], v2 = V[s.z], v3 = V[s.w];
+        VT v0, v1, v2, v3;
+        if constexpr (MAPPED) {
+            const int4 s = reinterpret_cast<const int4 *>(map)[q];
+            v0 = V[s.x], v1 = V[s.y], v2 = V[s.z], v3 = V[s.w];
+        } else {
+            v0 = V[e], v1 = V[e + 1], v2 = V[e + 2], v3 = V[e + 3];
+        }
         if constexpr (sizeof(VT) == 8) {
             double2 *o = reinterpret_cast<double2 *>(vals + e);
             o[0] = make_double2(v0, v1);
@@ -130,7 +136,7 @@ __global__ void __launch_bounds__(256) vals_refresh_kernel(const VT *__restrict_
         vals_t[d.w] = v3;
     } else {
         for (size_t i = e; i < nnz; ++i) {
-            const VT v = V[map[i]];
+            const VT v = MAPPED ? V[map[i]] : V[i];
             vals[i] = v;
             vals_t[map_t[i]] = v;
         }
@@ -150,6 +156,29 @@ pem_status pem::ensure_vmap_t(pem_ctx *ctx, pem_tiled *T)
                (long long)nt, T->vmap_t.as<int>());
     T->vmap_t_ready = true;
     return PEM_OK;
+}
+
+// The mapped form keeps the name tools/numeric_pass.py looks its time up by
+template <typename VT>
+static void launch_gather(pem_ctx *ctx, pem_tiled *T, const VT *src, const int *map)
+{
+    const size_t nnz = (size_t)T->nnz;
+    const unsigned grid = grid_for((nnz + 3) / 4, 256);
+    const bool f32 = sizeof(VT) == 4;
+    if (map)
+        PEM_LAUNCH_NAMED(ctx, f32 ? "vals_refresh_kernel<float>" : "vals_refresh_kernel<double>", (vals_refresh_kernel<VT, true>), grid, 256, src,
+                         map, T->vmap_t.as<int>(), nnz, T->vals.as<VT>(), T->vals_t.as<VT>());
+    else
+        PEM_LAUNCH_NAMED(ctx, f32 ? "vals_refresh_kernel<float, identity>" : "vals_refresh_kernel<double, identity>", (vals_refresh_kernel<VT, false>),
+                         grid, 256, src, nullptr, T->vmap_t.as<int>(), nnz, T->vals.as<VT>(), T->vals_t.as<VT>());
+}
+
+void pem::refresh_gather(pem_ctx *ctx, pem_tiled *T, const void *src, const int *map)
+{
+    if (T->value_bytes == 4)
+        launch_gather(ctx, T, static_cast<const float *>(src), map);
+    else
+        launch_gather(ctx, T, static_cast<const double *>(src), map);
 }
 
 static pem_status ensure_maps(pem_ctx *ctx, pem_tiled *T, int order)
@@ -211,12 +240,7 @@ static pem_status set_values(pem_ctx *ctx, pem_tiled *T, const void *host, const
         dV = stage.p;
     }
     PEM_TRY(ensure_maps(ctx, T, order));
-    if (value_bytes == 4)
-        PEM_LAUNCH(ctx, vals_refresh_kernel<float>, grid_for((nnz + 3) / 4, 256), 256, static_cast<const float *>(dV), T->vmap[order].as<int>(),
-                   T->vmap_t.as<int>(), nnz, T->vals.as<float>(), T->vals_t.as<float>());
-    else
-        PEM_LAUNCH(ctx, vals_refresh_kernel<double>, grid_for((nnz + 3) / 4, 256), 256, static_cast<const double *>(dV), T->vmap[order].as<int>(),
-                   T->vmap_t.as<int>(), nnz, T->vals.as<double>(), T->vals_t.as<double>());
+    refresh_gather(ctx, T, dV, T->vmap[order].as<int>());
     ++T->value_version;
     if (!host) return PEM_OK;   // device form: a failure surfaces at pem_ctx_synchronize
     int hf[NUM_FLAGS];
