@@ -369,6 +369,28 @@ pem_status pem_tiled_mxv_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int
 pem_status pem_tiled_reduce(pem_ctx *ctx, const pem_tiled *A, int op, int dim, double *dy, int accumulate);
 pem_status pem_tiled_reduce_f32(pem_ctx *ctx, const pem_tiled *A, int op, int dim, float *dy, int accumulate);
 
+/* Sparse times dense block: a tiling times k dense device vectors at once under a semiring.
+ *   pem_tiled_spmm  Y = A (+).(x) X  (transpose = 0: X is A.cols x k, Y is A.rows x k)
+ *                   Y = A^T (+).(x) X  (transpose = 1: X is A.rows x k, Y is A.cols x k)
+ *     X and Y are row-major device arrays of the tiling's value type: element (j, c) of X is dX[j * ldx + c], and likewise for Y.
+ *       They need only the value type's alignment; any ld >= max(k, 1) works.  Coordinates are those of the matrix the tiling
+ *       represents, as for pem_tiled_mxv; any tiling works.
+ *     Contract.  For every c, column c of Y is bit for bit what pem_tiled_mxv(A, semiring, transpose, X[:, c], y, accumulate) writes
+ *       into y (with the same old y under accumulate = 1); the sign of a zero under min / max is not specified, NaN payloads are not
+ *       compared.  Under plus-times each Y[i, c] is the fma chain over row i's entries in ascending column.  Empty rows: the start
+ *       value (accumulate = 0) or untouched (accumulate = 1).  No atomics: two calls give identical bits.  Columns [k, ldy) of Y are
+ *       never written.
+ *   PEM_E_INVALID: a null context or tiling; an unknown semiring; transpose or accumulate not 0 or 1; k < 0; ldx or ldy below
+ *     max(k, 1); a null dX (dY) where X (Y) has entries; the fp64 form on an fp32 tiling or the reverse; X's and Y's byte spans
+ *     overlapping (a span runs from p to p + ((n - 1) * ld + k) * value_bytes); n * ld overflowing int64.  k = 0, a 0-row Y and an
+ *     empty tiling are legal.  Stream-ordered on the context's stream; never waits and reads nothing back.  A's current values are
+ *     read.  Allocates nothing, except that the first column-orientation call on a tiling builds the column schedule pem_tiled_mxv
+ *     keeps with it (see above). */
+pem_status pem_tiled_spmm(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, int64_t k, const double *dX, int64_t ldx,
+                          double *dY, int64_t ldy, int accumulate);
+pem_status pem_tiled_spmm_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, int64_t k, const float *dX, int64_t ldx,
+                              float *dY, int64_t ldy, int accumulate);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

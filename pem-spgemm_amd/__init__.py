@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_device_f32", "pem_cplan_create_masked", "pem_cplan_set_semiring", "pem_cplan_get_semiring",
     "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan", "pem_tiled_ewise", "pem_tiled_set_values_from_ewise",
     "pem_tiled_export_csr", "pem_tiled_export_csr_f32", "pem_tiled_select", "pem_tiled_set_values_from_select",
-    "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32",
+    "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32", "pem_tiled_spmm", "pem_tiled_spmm_f32",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -372,6 +372,44 @@ class Tiled:
         out, py = self._out("mxv", out, ny, like=x)
         fn = lib().pem_tiled_mxv_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, py, int(bool(accumulate))))
+        return out
+
+    def _block(self, fn, name, v, n, k=None):
+        """(k, ld) of a 2-D row-major device torch tensor of this tiling's dtype with n rows (and k columns): stride(1) == 1 and
+        stride(0) >= k, so a column slice of a wider row-major tensor is accepted"""
+        want = (f"a 2-D device tensor on cuda:{self.ctx.device} of {self.dtype.name} values, {n} x {'k' if k is None else k}, row-major "
+                "(stride(1) == 1, stride(0) >= k)")
+        if not hasattr(v, "data_ptr"):
+            raise ValueError(f"{fn}: want {want} for {name}, got {type(v).__name__}")
+        got = f"{v.dtype} of shape {tuple(v.shape)}, strides {tuple(v.stride())} on {v.device}"
+        if (v.dim() != 2 or not v.is_cuda or v.device.index != self.ctx.device or str(v.dtype) != f"torch.{self.dtype.name}" or v.shape[0] != n
+                or (k is not None and v.shape[1] != k)):
+            raise ValueError(f"{fn}: want {want} for {name}, got {got}")
+        kk = v.shape[1]
+        if kk == 0:   # (no element: the strides say nothing)
+            return 0, 1
+        if (v.stride(1) != 1 and kk > 1) or (v.shape[0] > 1 and v.stride(0) < kk):
+            raise ValueError(f"{fn}: want {want} for {name}, got {got}")
+        return kk, v.stride(0) if v.shape[0] > 1 else kk
+
+    def spmm(self, X, semiring="plus_times", transpose=False, out=None, accumulate=False):
+        """Sparse times dense block: out = A (+).(x) X, or A^T (+).(x) X with transpose=True, under a
+        semiring of SEMIRINGS.  X: a 2-D device torch tensor of the tiling's dtype, cols x k (transpose: rows x k), row-major with
+        stride(1) == 1 and stride(0) >= k (a column slice of a wider tensor is fine); out: rows x k (transpose: cols x k) under the
+        same rule, allocated contiguous when None.  Column c of out is bit for bit A.mxv(X[:, c], ...) with the same accumulate;
+        columns past k of out's rows are never written.  X and out must not overlap.  Ordered on the context's stream and never waits
+        (see mxv).  Returns out."""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        nx, ny = (self.rows, self.cols) if transpose else (self.cols, self.rows)
+        k, ldx = self._block("spmm", "X", X, nx)
+        if out is None:
+            import torch
+            out = torch.empty((ny, k), dtype=getattr(torch, self.dtype.name), device=X.device)
+        _, ldy = self._block("spmm", "out", out, ny, k)
+        fn = lib().pem_tiled_spmm_f32 if self.value_bytes == 4 else lib().pem_tiled_spmm
+        _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), C.c_int64(k), C.c_void_p(X.data_ptr()), C.c_int64(ldx),
+                  C.c_void_p(out.data_ptr()), C.c_int64(ldy), int(bool(accumulate))))
         return out
 
     def reduce(self, op="plus", dim="rows", out=None, accumulate=False):

@@ -1,0 +1,80 @@
+// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip): the folds of the matrix-vector
+// products and reductions, and the column-walk schedule.  SpMM folds with the very functions mxv folds with, so column c of
+// A (+).(x) X is bit for bit mxv of X's column c.
+#pragma once
+#include "spgemm_internal.h"
+
+namespace pem {
+
+// ------------------------------------------------------------------------------------------
+// the folds: K < 6 is a pem_semiring (mxv, spmm), K = 6 + op a pem_binop (reduce)
+// ------------------------------------------------------------------------------------------
+enum { MX_REDUCE = 6, MX_KINDS = 12 };
+
+template <int K>
+struct MxOp {
+    static constexpr bool reads_vals = K != PEM_SEMIRING_PLUS_PAIR;
+    static constexpr bool reads_x = K < MX_REDUCE && K != PEM_SEMIRING_PLUS_PAIR;
+    static constexpr bool pair = K == PEM_SEMIRING_PLUS_TIMES;   // stages (a, x): the fma needs both unrounded
+    template <typename VT> static __device__ __forceinline__ VT start()
+    {
+        switch (K) {
+        case PEM_SEMIRING_MIN_PLUS:
+        case MX_REDUCE + PEM_BINOP_MIN: return pem_inf<VT>();
+        case PEM_SEMIRING_MAX_PLUS:
+        case PEM_SEMIRING_MAX_TIMES:
+        case MX_REDUCE + PEM_BINOP_MAX: return -pem_inf<VT>();
+        case MX_REDUCE + PEM_BINOP_TIMES:
+        case MX_REDUCE + PEM_BINOP_LAND: return VT(1);
+        default: return VT(0);
+        }
+    }
+    // the start taken from the old y (accumulate): the boolean folds start from y != 0
+    template <typename VT> static __device__ __forceinline__ VT from_y(VT y)
+    {
+        if constexpr (K == PEM_SEMIRING_LOR_LAND || K == MX_REDUCE + PEM_BINOP_LOR || K == MX_REDUCE + PEM_BINOP_LAND)
+            return y != VT(0) ? VT(1) : VT(0);
+        else
+            return y;
+    }
+    // what one entry contributes (every + and * rounded once in VT; -ffp-contract=off)
+    template <typename VT> static __device__ __forceinline__ VT term(VT a, VT x)
+    {
+        switch (K) {
+        case PEM_SEMIRING_MIN_PLUS:
+        case PEM_SEMIRING_MAX_PLUS: return a + x;
+        case PEM_SEMIRING_MAX_TIMES: return a * x;
+        case PEM_SEMIRING_LOR_LAND: return (a != VT(0) && x != VT(0)) ? VT(1) : VT(0);
+        default: return a;   // plus_times stages a and x apart; plus_pair's term is not read
+        }
+    }
+    template <typename VT> static __device__ __forceinline__ VT step(VT acc, VT t, VT x)
+    {
+        switch (K) {
+        case PEM_SEMIRING_PLUS_TIMES: return pem_fma(t, x, acc);
+        case PEM_SEMIRING_MIN_PLUS:
+        case MX_REDUCE + PEM_BINOP_MIN: return pem_fmin(acc, t);
+        case PEM_SEMIRING_MAX_PLUS:
+        case PEM_SEMIRING_MAX_TIMES:
+        case MX_REDUCE + PEM_BINOP_MAX: return pem_fmax(acc, t);
+        case PEM_SEMIRING_PLUS_PAIR: return acc + VT(1);
+        case PEM_SEMIRING_LOR_LAND: return t != VT(0) ? VT(1) : acc;
+        case MX_REDUCE + PEM_BINOP_PLUS: return acc + t;
+        case MX_REDUCE + PEM_BINOP_TIMES: return acc * t;
+        case MX_REDUCE + PEM_BINOP_LOR: return (acc != VT(0) || t != VT(0)) ? VT(1) : VT(0);
+        default: return (acc != VT(0) && t != VT(0)) ? VT(1) : VT(0);   // reduce LAND
+        }
+    }
+};
+
+// The column walk's schedule, built on the first column-orientation call and kept with the tiling (mxv.hip): per CSC position the
+// entry offset in column-walk order (mx_csc_off) and the tile's first slot in vals_t (mx_csc_base), per vals_t slot the entry's
+// (c << 4) | r (mx_rci_t).  Allocates from the context's arena the first time only; stream-ordered.
+pem_status ensure_mx_cols(pem_ctx *ctx, const pem_tiled *A);
+
+// pem_tiled_mxv's launch for checked arguments (mxv.hip): y = A (+).(x) x under semiring K < 6, col the orientation; x and y hold
+// the tiling's value type.  Builds the column schedule on first use; stream-ordered.
+pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const float *x, float *y, int accumulate);
+pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const double *x, double *y, int accumulate);
+
+}  // namespace pem

@@ -22,70 +22,12 @@
 // lane that folded it.
 #include "spgemm_internal.h"
 #include "tiled_internal.h"
+#include "mx_internal.h"
 #include <climits>
 
 using namespace pem;
 
-// ------------------------------------------------------------------------------------------
-// the folds: K < 6 is a pem_semiring (mxv), K = 6 + op a pem_binop (reduce)
-// ------------------------------------------------------------------------------------------
-enum { MX_REDUCE = 6, MX_KINDS = 12 };
-
-template <int K>
-struct MxOp {
-    static constexpr bool reads_vals = K != PEM_SEMIRING_PLUS_PAIR;
-    static constexpr bool reads_x = K < MX_REDUCE && K != PEM_SEMIRING_PLUS_PAIR;
-    static constexpr bool pair = K == PEM_SEMIRING_PLUS_TIMES;   // stages (a, x): the fma needs both unrounded
-    template <typename VT> static __device__ __forceinline__ VT start()
-    {
-        switch (K) {
-        case PEM_SEMIRING_MIN_PLUS:
-        case MX_REDUCE + PEM_BINOP_MIN: return pem_inf<VT>();
-        case PEM_SEMIRING_MAX_PLUS:
-        case PEM_SEMIRING_MAX_TIMES:
-        case MX_REDUCE + PEM_BINOP_MAX: return -pem_inf<VT>();
-        case MX_REDUCE + PEM_BINOP_TIMES:
-        case MX_REDUCE + PEM_BINOP_LAND: return VT(1);
-        default: return VT(0);
-        }
-    }
-    // the start taken from the old y (accumulate): the boolean folds start from y != 0
-    template <typename VT> static __device__ __forceinline__ VT from_y(VT y)
-    {
-        if constexpr (K == PEM_SEMIRING_LOR_LAND || K == MX_REDUCE + PEM_BINOP_LOR || K == MX_REDUCE + PEM_BINOP_LAND)
-            return y != VT(0) ? VT(1) : VT(0);
-        else
-            return y;
-    }
-    // what one entry contributes (every + and * rounded once in VT; -ffp-contract=off)
-    template <typename VT> static __device__ __forceinline__ VT term(VT a, VT x)
-    {
-        switch (K) {
-        case PEM_SEMIRING_MIN_PLUS:
-        case PEM_SEMIRING_MAX_PLUS: return a + x;
-        case PEM_SEMIRING_MAX_TIMES: return a * x;
-        case PEM_SEMIRING_LOR_LAND: return (a != VT(0) && x != VT(0)) ? VT(1) : VT(0);
-        default: return a;   // plus_times stages a and x apart; plus_pair's term is not read
-        }
-    }
-    template <typename VT> static __device__ __forceinline__ VT step(VT acc, VT t, VT x)
-    {
-        switch (K) {
-        case PEM_SEMIRING_PLUS_TIMES: return pem_fma(t, x, acc);
-        case PEM_SEMIRING_MIN_PLUS:
-        case MX_REDUCE + PEM_BINOP_MIN: return pem_fmin(acc, t);
-        case PEM_SEMIRING_MAX_PLUS:
-        case PEM_SEMIRING_MAX_TIMES:
-        case MX_REDUCE + PEM_BINOP_MAX: return pem_fmax(acc, t);
-        case PEM_SEMIRING_PLUS_PAIR: return acc + VT(1);
-        case PEM_SEMIRING_LOR_LAND: return t != VT(0) ? VT(1) : acc;
-        case MX_REDUCE + PEM_BINOP_PLUS: return acc + t;
-        case MX_REDUCE + PEM_BINOP_TIMES: return acc * t;
-        case MX_REDUCE + PEM_BINOP_LOR: return (acc != VT(0) || t != VT(0)) ? VT(1) : VT(0);
-        default: return (acc != VT(0) && t != VT(0)) ? VT(1) : VT(0);   // reduce LAND
-        }
-    }
-};
+// the folds (MxOp, mx_internal.h): K < 6 is a pem_semiring (mxv), K = 6 + op a pem_binop (reduce)
 
 __device__ __forceinline__ void mx_wave_sync()
 {
@@ -227,7 +169,7 @@ __global__ void mx_rci_t_kernel(const uint16_t *__restrict__ masks_t, const int 
     }
 }
 
-static pem_status ensure_mx_cols(pem_ctx *ctx, const pem_tiled *A)
+pem_status pem::ensure_mx_cols(pem_ctx *ctx, const pem_tiled *A)
 {
     if (A->mx_cols_ready) return PEM_OK;
     const size_t nt = (size_t)A->ntiles, nnz = (size_t)A->nnz;
@@ -293,6 +235,16 @@ static pem_status mx_run(pem_ctx *ctx, const pem_tiled *A, int kind, bool col, c
     case 10: return mx_launch<VT, 10>(ctx, A, col, x, y, accumulate);
     default: return mx_launch<VT, 11>(ctx, A, col, x, y, accumulate);
     }
+}
+
+pem_status pem::mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const float *x, float *y, int accumulate)
+{
+    return mx_run<float>(ctx, A, semiring, col, x, y, accumulate);
+}
+
+pem_status pem::mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const double *x, double *y, int accumulate)
+{
+    return mx_run<double>(ctx, A, semiring, col, x, y, accumulate);
 }
 
 static bool mx_flag_ok(int v) { return v == 0 || v == 1; }

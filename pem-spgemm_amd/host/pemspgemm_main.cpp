@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cctype>
 #include <cmath>
 #include <condition_variable>
 #include <mutex>
@@ -322,6 +323,50 @@ static int read_input(const char *path, pem_coo *out)
     return rc;
 }
 
+// --spmm: X as a Matrix-Market `array real general` file (values column by column), returned row-major (x[j * k + c]).  Returns an
+// empty string on success, else what is wrong.  (pem_mm_read reads coordinate files only.)
+static std::string read_dense_array(const char *path, int64_t *rows, int64_t *k, std::vector<double> *x)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return "cannot open the file";
+    char line[4096];
+    std::string err;
+    if (!fgets(line, sizeof line, f)) err = "empty file";
+    char banner[64] = "", object[64] = "", format[64] = "", field[64] = "", symmetry[64] = "";
+    if (err.empty() && sscanf(line, "%63s %63s %63s %63s %63s", banner, object, format, field, symmetry) != 5) err = "no Matrix-Market header";
+    auto lower = [](char *t) { for (; *t; ++t) *t = (char)tolower((unsigned char)*t); };
+    lower(banner), lower(object), lower(format), lower(field), lower(symmetry);
+    if (err.empty() && (strcmp(banner, "%%matrixmarket") || strcmp(object, "matrix"))) err = "no Matrix-Market header";
+    if (err.empty() && strcmp(format, "array")) err = std::string("a ") + format + " file, not an array (dense) file";
+    if (err.empty() && strcmp(field, "real")) err = std::string("a ") + field + " file, not a real one";
+    if (err.empty() && strcmp(symmetry, "general")) err = std::string("a ") + symmetry + " array, not a general one";
+    long long m = -1, n = -1;
+    while (err.empty()) {
+        if (!fgets(line, sizeof line, f)) {
+            err = "no size line";
+            break;
+        }
+        if (line[0] == '%') continue;
+        if (sscanf(line, "%lld %lld", &m, &n) != 2 || m < 0 || n < 0) err = "bad size line";
+        break;
+    }
+    if (err.empty()) {
+        x->assign((size_t)m * (size_t)n, 0.0);
+        for (long long c = 0; c < n && err.empty(); ++c)
+            for (long long j = 0; j < m; ++j) {
+                double v;
+                if (fscanf(f, "%lf", &v) != 1) {
+                    err = "fewer values than rows x cols";
+                    break;
+                }
+                (*x)[(size_t)j * (size_t)n + (size_t)c] = v;
+            }
+    }
+    fclose(f);
+    *rows = m, *k = n;
+    return err;
+}
+
 int main(int argc, char *argv[])
 {
     // Beyond the reference: `--B <file.mtx>` multiplies by a second matrix instead of A itself,
@@ -348,6 +393,9 @@ int main(int argc, char *argv[])
     // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
     // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
     // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
+    // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
+    // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
+    // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
@@ -358,6 +406,7 @@ int main(int argc, char *argv[])
     double add_alpha = 1.0, add_beta = 1.0;
     const char *select_spec = nullptr;   // --select OP[:THUNK]
     const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
+    const char *spmm_path = nullptr;     // --spmm X.mtx
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -382,6 +431,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--beta") && r + 1 < argc) add_beta = atof(argv[++r]);
             else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
             else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
+            else if (!strcmp(argv[r], "--spmm") && r + 1 < argc) spmm_path = argv[++r];
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -481,6 +531,21 @@ int main(int argc, char *argv[])
         }
         if (select_op <= PEM_SELECT_COL_GT && !(std::floor(select_thunk) == select_thunk && std::fabs(select_thunk) <= 2147483648.0)) {
             printf("--select %s: the positional op %s needs an integral thunk k with |k| <= 2^31. Exiting.\n", select_spec, name.c_str());
+            return 1;
+        }
+    }
+    // --spmm: X read up front, so that a bad file is refused before any work
+    int64_t spmm_rows = 0, spmm_k = 0;
+    std::vector<double> spmm_x;
+    if (spmm_path) {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : reduce_spec ? "--reduce" : nullptr;
+        if (clash) {
+            printf("--spmm does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        const std::string err = read_dense_array(spmm_path, &spmm_rows, &spmm_k, &spmm_x);
+        if (!err.empty()) {
+            printf("--spmm %s: %s (want a Matrix-Market array real general file). Exiting.\n", spmm_path, err.c_str());
             return 1;
         }
     }
@@ -917,6 +982,58 @@ int main(int argc, char *argv[])
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
 
+    std::vector<double> spmm_y;   // --spmm: Y, row-major, on the host
+    int64_t spmm_ny = 0;
+    if (spmm_path) {
+        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Src, &si));
+        if (spmm_rows != si.cols) {
+            printf("--spmm %s: X has %lld rows; the result has %d columns. Exiting.\n", spmm_path, (long long)spmm_rows, si.cols);
+            if (Ct) pem_tiled_destroy(ctx, Ct);
+            return 1;
+        }
+        const int64_t k = spmm_k, ld = k > 1 ? k : 1;
+        spmm_ny = si.rows;
+        const size_t vb = fp32 ? 4 : 8, nxv = (size_t)spmm_rows * (size_t)ld, nyv = (size_t)spmm_ny * (size_t)ld;
+        void *dx = nullptr, *dy = nullptr;
+        if (hipMalloc(&dx, vb * nxv + 8) != hipSuccess || hipMalloc(&dy, vb * nyv + 8) != hipSuccess) {
+            fprintf(stderr, "pemspgemm: --spmm: device allocation failed\n");
+            return 2;
+        }
+        if (fp32) {
+            std::vector<float> xf(spmm_x.begin(), spmm_x.end());
+            if (nxv && hipMemcpy(dx, xf.data(), 4 * nxv, hipMemcpyHostToDevice) != hipSuccess) return 2;
+        } else if (nxv && hipMemcpy(dx, spmm_x.data(), 8 * nxv, hipMemcpyHostToDevice) != hipSuccess) {
+            return 2;
+        }
+        CHECK(pem_ctx_synchronize(ctx));
+        auto m0 = std::chrono::high_resolution_clock::now();
+        CHECK(fp32 ? pem_tiled_spmm_f32(ctx, Src, semiring, 0, k, (const float *)dx, ld, (float *)dy, ld, 0)
+                   : pem_tiled_spmm(ctx, Src, semiring, 0, k, (const double *)dx, ld, (double *)dy, ld, 0));
+        CHECK(pem_ctx_synchronize(ctx));
+        const double spmm_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - m0).count();
+        spmm_y.resize(nyv);
+        if (fp32) {
+            std::vector<float> f(nyv);
+            if (nyv && hipMemcpy(f.data(), dy, 4 * nyv, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+            for (size_t i = 0; i < nyv; ++i) spmm_y[i] = f[i];
+        } else if (nyv && hipMemcpy(spmm_y.data(), dy, 8 * nyv, hipMemcpyDeviceToHost) != hipSuccess) {
+            return 2;
+        }
+        (void)hipFree(dx);
+        (void)hipFree(dy);
+        double sum = 0.0;
+        for (double v : spmm_y) sum += v;
+        printf("spmm: Y = %s (%s) X: spmm %.3fms, k %lld, %lld x %lld values, host sum %.17g\n", Sel ? "the selection" : Sum ? "the sum" : "C",
+               semiring_names[semiring], spmm_ms, (long long)k, (long long)spmm_ny, (long long)k, sum);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+
     int rc = 0;
     if (!save) {
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
@@ -942,7 +1059,24 @@ int main(int argc, char *argv[])
         }
     }
     pem_tiled *Res = Sel ? Sel : Sum;   // the final result when it is a tiling
-    if (out_path && reduce_dim >= 0) {   // the reduced vector as a Matrix-Market dense array (n x 1)
+    if (out_path && spmm_path) {   // Y as a Matrix-Market dense array (R.rows x k, values column by column)
+        FILE *f = fopen(out_path, "w");
+        bool ok = f != nullptr;
+        const int64_t ld = spmm_k > 1 ? spmm_k : 1;
+        if (ok) {
+            ok = fprintf(f, "%%%%MatrixMarket matrix array real general\n%% Y = R X (%s) by pemspgemm (pem-spgemm_amd)\n%lld %lld\n",
+                         semiring_names[semiring], (long long)spmm_ny, (long long)spmm_k) > 0;
+            for (int64_t c = 0; ok && c < spmm_k; ++c)
+                for (int64_t i = 0; ok && i < spmm_ny; ++i) ok = fprintf(f, fp32 ? "%.9g\n" : "%.17g\n", spmm_y[(size_t)(i * ld + c)]) > 0;
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) {
+            fprintf(stderr, "pemspgemm: --out %s: cannot write Y\n", out_path);
+            rc = 2;
+        } else {
+            printf("Y written to %s\n", out_path);
+        }
+    } else if (out_path && reduce_dim >= 0) {   // the reduced vector as a Matrix-Market dense array (n x 1)
         FILE *f = fopen(out_path, "w");
         bool ok = f != nullptr;
         if (ok) {
