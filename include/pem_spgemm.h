@@ -391,6 +391,44 @@ pem_status pem_tiled_spmm(pem_ctx *ctx, const pem_tiled *A, int semiring, int tr
 pem_status pem_tiled_spmm_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, int64_t k, const float *dX, int64_t ldx,
                               float *dY, int64_t ldy, int accumulate);
 
+/* Sampled dense-dense product, SDDMM: R = pattern(S) o (X . Y^T) under a semiring, on the device.
+ *   X is rows x k and Y is cols x k, rows and cols those of the matrix the tiling represents (what pem_tiled_export_csr returns: a
+ *     tiling built with transpose = 1 is its own matrix).  Both are row-major device arrays of the entry point's value type with
+ *     row strides ldx, ldy >= max(k, 1): element (i, c) of X is dX[i * ldx + c].  They need only the value type's alignment, are
+ *     read-only, and may alias or be the same pointer (H . H^T).
+ *   For every stored position (i, j):  R(i, j) = (+)_{c = 0 .. k-1} X[i, c] (x) Y[j, c], with section 3g's arithmetic: plus_times
+ *     is the chain acc = fma(X[i, c], Y[j, c], acc) in ascending c from 0 (fmaf for fp32); min_plus / max_plus / max_times round
+ *     each + / * once and fold with fmin / fmax from +-inf (NaN terms skipped, the sign of a zero result not specified); plus_pair
+ *     stores k (acc + 1 per column) without reading X or Y; lor_land stores 1.0 if some c has both operands != 0 (NaN counts as
+ *     != 0), else 0.0.  k = 0 stores the semiring's start value (0, +inf, -inf, -inf, 0, 0) everywhere.  The pattern is never
+ *     touched: zeros that come out stay entries.  NaN payloads are not specified.  The stored values of S / the old values of t are
+ *     never read (with accumulate = 0): S o (X . Y^T) scaled by S's values is pem_tiled_ewise(S, R, PEM_EWISE_INTERSECT,
+ *     PEM_BINOP_TIMES).
+ *   pem_tiled_sddmm  a new tiling R with S's pattern, holding the sampled product in the entry point's value type (S may hold either
+ *       value type, as a mask may).  R owns its arrays and works everywhere a tiling does (A, B, mask, save / load, set_values*,
+ *       ewise, select, mxv, spmm, export, and a later pem_tiled_set_values_sddmm on R itself for the next X, Y).  It equals, every
+ *       pem_tiled_array and every pem_tiled_info field but the two timings, the tiling pem_tiled_from_csr builds from S's exported
+ *       pattern with these values.  The call waits, like the other builders; its allocations come from the context's arena.  An S
+ *       with nnz = 0 gives a valid empty tiling.
+ *   pem_tiled_set_values_sddmm  in place: t's values (vals and vals_t) become the sampled product at t's own pattern; t must hold the
+ *       entry point's value type (the rule of pem_tiled_set_values*).  accumulate = 1: every fold starts from the entry's old value
+ *       (lor_land: from old != 0), so one call with k = k1 + k2 equals a call on columns [0, k1) followed by an accumulate call on
+ *       columns [k1, k1 + k2), bit for bit (zero signs under min / max excepted).  Bumps t's value version (plans built on t turn
+ *       stale under the rule of pem_tiled_set_values).  Stream-ordered on the context's stream, never waits, reads nothing back;
+ *       allocates only on the tiling's first refresh (the vals_t map of pem_tiled_set_values, an arena allocation: a captured graph
+ *       re-captures once).  No atomics, every value is written once: two calls give identical bits.
+ *   PEM_E_INVALID: a null context, tiling or out; an unknown semiring; accumulate not 0 or 1; k < 0; ldx or ldy below max(k, 1); a
+ *     null dX (dY) where X (Y) has elements and the semiring reads them (every semiring but plus_pair); n * ld overflowing int64;
+ *     the in-place fp64 form on an fp32 tiling or the reverse.  All of these are checked before the device is touched. */
+pem_status pem_tiled_set_values_sddmm(pem_ctx *ctx, pem_tiled *t, int semiring, int64_t k, const double *dX, int64_t ldx, const double *dY,
+                                      int64_t ldy, int accumulate);
+pem_status pem_tiled_set_values_sddmm_f32(pem_ctx *ctx, pem_tiled *t, int semiring, int64_t k, const float *dX, int64_t ldx, const float *dY,
+                                          int64_t ldy, int accumulate);
+pem_status pem_tiled_sddmm(pem_ctx *ctx, const pem_tiled *S, int semiring, int64_t k, const double *dX, int64_t ldx, const double *dY,
+                           int64_t ldy, pem_tiled **out);
+pem_status pem_tiled_sddmm_f32(pem_ctx *ctx, const pem_tiled *S, int semiring, int64_t k, const float *dX, int64_t ldx, const float *dY,
+                               int64_t ldy, pem_tiled **out);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

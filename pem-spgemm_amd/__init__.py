@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "pem_tiled_from_cplan", "pem_tiled_set_values_from_cplan", "pem_tiled_ewise", "pem_tiled_set_values_from_ewise",
     "pem_tiled_export_csr", "pem_tiled_export_csr_f32", "pem_tiled_select", "pem_tiled_set_values_from_select",
     "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32", "pem_tiled_spmm", "pem_tiled_spmm_f32",
+    "pem_tiled_set_values_sddmm", "pem_tiled_set_values_sddmm_f32", "pem_tiled_sddmm", "pem_tiled_sddmm_f32",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -374,15 +375,16 @@ class Tiled:
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, py, int(bool(accumulate))))
         return out
 
-    def _block(self, fn, name, v, n, k=None):
-        """(k, ld) of a 2-D row-major device torch tensor of this tiling's dtype with n rows (and k columns): stride(1) == 1 and
-        stride(0) >= k, so a column slice of a wider row-major tensor is accepted"""
-        want = (f"a 2-D device tensor on cuda:{self.ctx.device} of {self.dtype.name} values, {n} x {'k' if k is None else k}, row-major "
+    def _block(self, fn, name, v, n, k=None, dtype=None):
+        """(k, ld) of a 2-D row-major device torch tensor of dtype (None: this tiling's) with n rows (and k columns): stride(1) == 1
+        and stride(0) >= k, so a column slice of a wider row-major tensor is accepted"""
+        dtype = self.dtype if dtype is None else np.dtype(dtype)
+        want = (f"a 2-D device tensor on cuda:{self.ctx.device} of {dtype.name} values, {n} x {'k' if k is None else k}, row-major "
                 "(stride(1) == 1, stride(0) >= k)")
         if not hasattr(v, "data_ptr"):
             raise ValueError(f"{fn}: want {want} for {name}, got {type(v).__name__}")
         got = f"{v.dtype} of shape {tuple(v.shape)}, strides {tuple(v.stride())} on {v.device}"
-        if (v.dim() != 2 or not v.is_cuda or v.device.index != self.ctx.device or str(v.dtype) != f"torch.{self.dtype.name}" or v.shape[0] != n
+        if (v.dim() != 2 or not v.is_cuda or v.device.index != self.ctx.device or str(v.dtype) != f"torch.{dtype.name}" or v.shape[0] != n
                 or (k is not None and v.shape[1] != k)):
             raise ValueError(f"{fn}: want {want} for {name}, got {got}")
         kk = v.shape[1]
@@ -411,6 +413,43 @@ class Tiled:
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), C.c_int64(k), C.c_void_p(X.data_ptr()), C.c_int64(ldx),
                   C.c_void_p(out.data_ptr()), C.c_int64(ldy), int(bool(accumulate))))
         return out
+
+    def _sddmm_args(self, fn, X, Y, semiring, dtype):
+        """(f32, k, X's pointer and stride, Y's pointer and stride) of an sddmm call; dtype None: X's dtype decides"""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        if dtype is None:
+            name = str(getattr(X, "dtype", "")).replace("torch.", "")
+            if name not in ("float32", "float64"):
+                raise ValueError(f"{fn}: want a 2-D device tensor of float32 or float64 values for X, got {name or type(X).__name__}")
+            dtype = np.dtype(name)
+        if Y is None:
+            if self.rows != self.cols:
+                raise ValueError(f"{fn}: Y=None means Y = X and needs a square tiling, not {self.rows} x {self.cols}")
+            Y = X
+        k, ldx = self._block(fn, "X", X, self.rows, dtype=dtype)
+        _, ldy = self._block(fn, "Y", Y, self.cols, k, dtype=dtype)
+        return (dtype == np.float32, C.c_int64(k), C.c_void_p(X.data_ptr()), C.c_int64(ldx), C.c_void_p(Y.data_ptr()), C.c_int64(ldy))
+
+    def sddmm(self, X, Y=None, semiring="plus_times"):
+        """Sampled dense-dense product: a new tiling R with this tiling's pattern and R(i, j) = the fold
+        over c of X[i, c] (x) Y[j, c] under a semiring of SEMIRINGS -- pattern(S) o (X . Y^T); this tiling's values are never read.
+        X: rows x k, Y: cols x k (None: Y = X, a square tiling), 2-D device torch tensors of one dtype under spmm's rules (stride(1)
+        == 1, stride(0) >= k); R's dtype is X's, whatever this tiling's.  Under plus_times every value is the chain acc = fma(X[i, c],
+        Y[j, c], acc) in ascending c from 0.  Waits.  The next X, Y go into R in place with R.set_values_sddmm."""
+        f32, k, px, ldx, py, ldy = self._sddmm_args("sddmm", X, Y, semiring, None)
+        h = C.c_void_p()
+        fn = lib().pem_tiled_sddmm_f32 if f32 else lib().pem_tiled_sddmm
+        _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], k, px, ldx, py, ldy, C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_sddmm(self, X, Y=None, semiring="plus_times", accumulate=False):
+        """sddmm in place: this tiling's values become the sampled product at its own pattern (X, Y of the tiling's dtype); with
+        accumulate=True every fold starts from the entry's old value (lor_land: from old != 0).  Plans built on the tiling turn stale
+        as after set_values.  Ordered on the context's stream and never waits (see mxv)."""
+        f32, k, px, ldx, py, ldy = self._sddmm_args("set_values_sddmm", X, Y, semiring, self.dtype)
+        fn = lib().pem_tiled_set_values_sddmm_f32 if f32 else lib().pem_tiled_set_values_sddmm
+        _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], k, px, ldx, py, ldy, int(bool(accumulate))))
 
     def reduce(self, op="plus", dim="rows", out=None, accumulate=False):
         """Row or column reduction: out[i] = the left fold, in ascending index, of row i's (dim="cols":

@@ -1,6 +1,6 @@
-// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip): the folds of the matrix-vector
-// products and reductions, and the column-walk schedule.  SpMM folds with the very functions mxv folds with, so column c of
-// A (+).(x) X is bit for bit mxv of X's column c.
+// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip, sddmm.hip): the folds of the
+// matrix-vector products and reductions, the column-walk schedule, and the span of a dense row-major block.  SpMM folds with the
+// very functions mxv folds with, so column c of A (+).(x) X is bit for bit mxv of X's column c; SDDMM folds its chains with them too.
 #pragma once
 #include "spgemm_internal.h"
 
@@ -76,5 +76,16 @@ pem_status ensure_mx_cols(pem_ctx *ctx, const pem_tiled *A);
 // the tiling's value type.  Builds the column schedule on first use; stream-ordered.
 pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const float *x, float *y, int accumulate);
 pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const double *x, double *y, int accumulate);
+
+// the bytes [lo, hi) a row-major n x k block with row stride ld spans (empty when n or k is 0); false when n * ld overflows int64
+// (the argument checks of spmm.hip and sddmm.hip)
+inline bool sp_span(const void *p, int64_t n, int64_t k, int64_t ld, int vb, unsigned __int128 *lo, unsigned __int128 *hi)
+{
+    int64_t nld = 0;
+    if (__builtin_mul_overflow(n, ld, &nld)) return false;
+    *lo = *hi = (unsigned __int128)(uintptr_t)p;
+    if (n > 0 && k > 0) *hi += ((unsigned __int128)(n - 1) * (unsigned __int128)ld + (unsigned __int128)k) * (unsigned)vb;
+    return true;
+}
 
 }  // namespace pem

@@ -219,16 +219,6 @@ static pem_status sp_run(pem_ctx *ctx, const pem_tiled *A, int semiring, bool co
 
 static bool sp_flag_ok(int v) { return v == 0 || v == 1; }
 
-// the bytes [lo, hi) a row-major n x k block with row stride ld spans (empty when n or k is 0); false when n * ld overflows int64
-static bool sp_span(const void *p, int64_t n, int64_t k, int64_t ld, int vb, unsigned __int128 *lo, unsigned __int128 *hi)
-{
-    int64_t nld = 0;
-    if (__builtin_mul_overflow(n, ld, &nld)) return false;
-    *lo = *hi = (unsigned __int128)(uintptr_t)p;
-    if (n > 0 && k > 0) *hi += ((unsigned __int128)(n - 1) * (unsigned __int128)ld + (unsigned __int128)k) * (unsigned)vb;
-    return true;
-}
-
 static pem_status spmm_common(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, int64_t k, const void *dX, int64_t ldx,
                               void *dY, int64_t ldy, int accumulate, int value_bytes, const char *fn)
 {

@@ -396,6 +396,10 @@ int main(int argc, char *argv[])
     // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
     // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
     // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
+    // `--sddmm X.mtx [--sddmm-y Y.mtx]`: the final result R (C, the sum of --add, or what --select kept)
+    // gets the values of pattern(R) o (X Y^T) under the semiring, on the device (pem_tiled_sddmm); X and Y are Matrix-Market `array
+    // real general` files of R.rows and R.cols rows and the same k columns (read as float with --fp32), Y defaults to X.  --out and
+    // the sorted COO files then receive that tiling.  The CSV row describes the product.
     // `--standin NAME [--scale S]`: the seeded C++ stand-in generator takes the place of the file (no SuiteSparse
     // file exists offline); NAME then stands where the path stood, and the remaining positional arguments keep their meaning.
     const char *b_path = nullptr, *out_path = nullptr, *cache_dir = nullptr, *standin = nullptr, *mask_path = nullptr;
@@ -407,6 +411,7 @@ int main(int argc, char *argv[])
     const char *select_spec = nullptr;   // --select OP[:THUNK]
     const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
     const char *spmm_path = nullptr;     // --spmm X.mtx
+    const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;   // --sddmm X.mtx [--sddmm-y Y.mtx]
     static std::string standin_path;
     static std::vector<char *> argv_store;
     bool fp32 = false, tune_split = true;
@@ -432,6 +437,8 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
             else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
             else if (!strcmp(argv[r], "--spmm") && r + 1 < argc) spmm_path = argv[++r];
+            else if (!strcmp(argv[r], "--sddmm") && r + 1 < argc) sddmm_path = argv[++r];
+            else if (!strcmp(argv[r], "--sddmm-y") && r + 1 < argc) sddmm_y_path = argv[++r];
             else if (!strcmp(argv[r], "--no-tune-split")) tune_split = false;
             else if (!strcmp(argv[r], "--chunks") && r + 1 < argc) nchunks = atoi(argv[++r]);
             else argv[w++] = argv[r];
@@ -547,6 +554,39 @@ int main(int argc, char *argv[])
         if (!err.empty()) {
             printf("--spmm %s: %s (want a Matrix-Market array real general file). Exiting.\n", spmm_path, err.c_str());
             return 1;
+        }
+    }
+    // --sddmm: X and Y read up front, so that a bad file is refused before any work
+    int64_t sddmm_xrows = 0, sddmm_yrows = 0, sddmm_k = 0;
+    std::vector<double> sddmm_x, sddmm_y;
+    if (sddmm_y_path && !sddmm_path) {
+        printf("--sddmm-y needs --sddmm <X.mtx>. Exiting.\n");
+        return 1;
+    }
+    if (sddmm_path) {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : reduce_spec ? "--reduce" : spmm_path ? "--spmm" : nullptr;
+        if (clash) {
+            printf("--sddmm does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        std::string err = read_dense_array(sddmm_path, &sddmm_xrows, &sddmm_k, &sddmm_x);
+        if (!err.empty()) {
+            printf("--sddmm %s: %s (want a Matrix-Market array real general file). Exiting.\n", sddmm_path, err.c_str());
+            return 1;
+        }
+        if (sddmm_y_path) {
+            int64_t ky = 0;
+            err = read_dense_array(sddmm_y_path, &sddmm_yrows, &ky, &sddmm_y);
+            if (!err.empty()) {
+                printf("--sddmm-y %s: %s (want a Matrix-Market array real general file). Exiting.\n", sddmm_y_path, err.c_str());
+                return 1;
+            }
+            if (ky != sddmm_k) {
+                printf("--sddmm-y %s: Y has %lld columns, X has %lld. Exiting.\n", sddmm_y_path, (long long)ky, (long long)sddmm_k);
+                return 1;
+            }
+        } else {
+            sddmm_yrows = sddmm_xrows;
         }
     }
     // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op)
@@ -1034,9 +1074,86 @@ int main(int argc, char *argv[])
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
 
+    // --sddmm: the final result's pattern with the values of X Y^T sampled there; its CSR export serves --out and the COO files
+    pem_tiled *Sd = nullptr;
+    std::vector<int32_t> sd_rp, sd_ci;
+    std::vector<double> sd_v;
+    if (sddmm_path) {
+        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Src, &si));
+        if (sddmm_xrows != si.rows || sddmm_yrows != si.cols) {
+            if (sddmm_xrows != si.rows)
+                printf("--sddmm %s: X has %lld rows; the result has %d rows. Exiting.\n", sddmm_path, (long long)sddmm_xrows, si.rows);
+            else
+                printf("--sddmm%s %s: Y has %lld rows; the result has %d columns. Exiting.\n", sddmm_y_path ? "-y" : "",
+                       sddmm_y_path ? sddmm_y_path : sddmm_path, (long long)sddmm_yrows, si.cols);
+            if (Ct) pem_tiled_destroy(ctx, Ct);
+            return 1;
+        }
+        const int64_t k = sddmm_k, ld = k > 1 ? k : 1;
+        const size_t vb = fp32 ? 4 : 8, nxv = (size_t)sddmm_xrows * (size_t)ld, nyv = sddmm_y_path ? (size_t)sddmm_yrows * (size_t)ld : 0;
+        void *dx = nullptr, *dy = nullptr;
+        if (hipMalloc(&dx, vb * nxv + 8) != hipSuccess || (sddmm_y_path && hipMalloc(&dy, vb * nyv + 8) != hipSuccess)) {
+            fprintf(stderr, "pemspgemm: --sddmm: device allocation failed\n");
+            return 2;
+        }
+        const std::vector<double> *hv[2] = {&sddmm_x, &sddmm_y};
+        void *dv[2] = {dx, dy};
+        const size_t nv[2] = {nxv, nyv};
+        for (int q = 0; q < 2; ++q) {
+            if (!nv[q]) continue;
+            if (fp32) {
+                std::vector<float> f(hv[q]->begin(), hv[q]->end());
+                if (hipMemcpy(dv[q], f.data(), 4 * nv[q], hipMemcpyHostToDevice) != hipSuccess) return 2;
+            } else if (hipMemcpy(dv[q], hv[q]->data(), 8 * nv[q], hipMemcpyHostToDevice) != hipSuccess) {
+                return 2;
+            }
+        }
+        if (!sddmm_y_path) dy = dx;   // Y = X: the same pointer
+        CHECK(pem_ctx_synchronize(ctx));
+        auto m0 = std::chrono::high_resolution_clock::now();
+        CHECK(fp32 ? pem_tiled_sddmm_f32(ctx, Src, semiring, k, (const float *)dx, ld, (const float *)dy, ld, &Sd)
+                   : pem_tiled_sddmm(ctx, Src, semiring, k, (const double *)dx, ld, (const double *)dy, ld, &Sd));
+        const double sd_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - m0).count();
+        if (sddmm_y_path) (void)hipFree(dy);
+        (void)hipFree(dx);
+        CHECK(pem_tiled_get_info(Sd, &si));
+        sd_rp.resize((size_t)si.rows + 1);
+        sd_ci.resize((size_t)si.nnz);
+        sd_v.resize((size_t)si.nnz);
+        int64_t nnz = 0;
+        if (fp32) {
+            std::vector<float> vf((size_t)si.nnz);
+            CHECK(pem_tiled_export_csr_f32(ctx, Sd, &nnz, sd_rp.data(), sd_ci.data(), vf.data()));
+            for (size_t e = 0; e < vf.size(); ++e) sd_v[e] = vf[e];
+        } else {
+            CHECK(pem_tiled_export_csr(ctx, Sd, &nnz, sd_rp.data(), sd_ci.data(), sd_v.data()));
+        }
+        double sum = 0.0;
+        for (double v : sd_v) sum += v;
+        printf("sddmm: R = pattern(%s) o (X %s^T) (%s): sddmm %.3fms, k %lld, nnz %lld, host sum %.17g\n", Sel ? "the selection" : Sum ? "the sum" : "C",
+               sddmm_y_path ? "Y" : "X", semiring_names[semiring], sd_ms, (long long)k, (long long)si.nnz, sum);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+
     int rc = 0;
     if (!save) {
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
+    } else if (Sd) {   // the sampled product's entries, sorted by (row, column): its CSR export is that order
+        const char *dir = getenv("PEM_RESULT_DIR") ? getenv("PEM_RESULT_DIR") : "/tmp";
+        std::vector<int32_t> rows(sd_ci.size());
+        for (size_t i = 0; i + 1 < sd_rp.size(); ++i)
+            for (int32_t e = sd_rp[i]; e < sd_rp[i + 1]; ++e) rows[(size_t)e] = (int32_t)i;
+        printf("Saving results to %s/SPGEMM_RESULT_*.txt\n", dir);
+        if (pem_write_result_files(dir, (int64_t)sd_ci.size(), rows.data(), sd_ci.data(), sd_v.data()) != 0) {
+            fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
+            rc = 2;
+        }
     } else {
         const char *dir = getenv("PEM_RESULT_DIR") ? getenv("PEM_RESULT_DIR") : "/tmp";
         std::vector<int32_t> rows((size_t)ci.nnz_c), cols((size_t)ci.nnz_c);
@@ -1091,6 +1208,18 @@ int main(int argc, char *argv[])
         } else {
             printf("vector written to %s\n", out_path);
         }
+    } else if (out_path && Sd) {   // the sampled product as a Matrix-Market file
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Sd, &si));
+        std::string comment = std::string("R = pattern(C) o (X Y^T) (") + semiring_names[semiring] + ")";
+        if (Sel) comment += std::string(", C after select ") + select_spec;
+        comment += " by pemspgemm (pem-spgemm_amd)";
+        if (pem_write_mtx_csr(out_path, si.rows, si.cols, sd_rp.data(), sd_ci.data(), sd_v.data(), comment.c_str()) != 0) {
+            fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
+            rc = 2;
+        } else {
+            printf("R written to %s\n", out_path);
+        }
     } else if (out_path && Res) {   // the sum and / or the selection as a Matrix-Market file (the tiling's CSR export)
         pem_tiled_info si;
         CHECK(pem_tiled_get_info(Res, &si));
@@ -1138,6 +1267,7 @@ int main(int argc, char *argv[])
     if (L != A) pem_tiled_destroy(ctx, L);
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
+    if (Sd) pem_tiled_destroy(ctx, Sd);
     if (Sel) pem_tiled_destroy(ctx, Sel);
     if (Sum) pem_tiled_destroy(ctx, Sum);
     if (Dt) pem_tiled_destroy(ctx, Dt);
