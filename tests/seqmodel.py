@@ -1,0 +1,503 @@
+"""Host model of one context's handles for the operation-sequence test (tests/seqgen.py writes the programs, tests/seqrun.py runs
+them on the GPU next to this model; DESIGN.md, "Sequence test").
+
+Plain Python / numpy, no GPU import.  The model holds, per live handle, what include/pem_spgemm.h lets a caller observe:
+
+  MTiled  rows, cols, dtype, the canonical CSR (rowptr, colidx, vals), a value version, and the provenance pem_internal.h's
+          Derivation keeps (none / plan + transpose / ewise operands + op + pattern + alpha + beta / select source + op + thunk)
+  MPlan   its operands, mask + complement, tile-row range, semiring, options, state 0-3, C as CSR, and the operand versions and
+          semiring under which step 3 last ran: "C is current" is computed from those, never assumed
+
+Model.apply(record) executes one record of a program.  It first evaluates the precondition the header documents and returns either
+the result or the documented status (PEM_E_STATE, PEM_E_INVALID); only refusals the header spells out are modelled.  It adds no
+arithmetic: every value comes from the reference the feature's own GPU test uses (oracle.csr_spgemm, semiringref, maskref,
+ewiseref, selectref, mxvref, spmmref, sddmmref); what is here is the reshaping between CSR and COO those references ask for.
+
+`mutations` switches on one of three deliberate mistakes of the MODEL (negative controls of tests/test_gpu_seq.py; the library
+is never touched): "no_bump" (a refresh leaves the value version alone), "stale_vals_t" (in-place writers leave the values the
+audit's vals_t readers use as they were), "no_option_reset" (set_option leaves the plan's state alone).
+"""
+import numpy as np
+
+import ewiseref
+import maskref
+import mxvref
+import sddmmref
+import selectref
+import semiringref
+import spmmref
+from matgen import cases
+
+PEM_OK, PEM_E_INVALID, PEM_E_STATE = 0, -1, -6
+MINMAX = ("min_plus", "max_plus", "max_times")
+SPECIAL = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 3.0e-310, 1.0e-40, 0.5, -0.5, 2.0])   # test_gpu_sddmm.py's mix
+MUTATIONS = ("no_bump", "stale_vals_t", "no_option_reset")
+
+# pem_cplan_set_option: the options the generator draws from, their defaults (pem_internal.h), whether the value is kept as an
+# integer (else as value != 0), and the step the plan falls back to (spgemm.hip: "the last step the option does not touch")
+OPTION_DEFAULT = dict(prune=1, wide=1, s3_band=1, s3_decode=1, s3_epw=0, s3_idx64=0, s3_mark=1, s3_xcd=1, s2_transposed=2,
+                      s1_segments=0, s1_xl_global=0, s1_force_key64=0)
+OPTION_INT = ("s3_epw", "s2_transposed")
+OPTION_KEEP = dict(prune=0, s1_force_key64=0, s1_xl_global=0, s1_segments=0, wide=1, s3_decode=1, s2_transposed=1, s3_band=2,
+                   s3_epw=2, s3_idx64=2, s3_mark=2, s3_xcd=2)
+
+_CASES = None
+_ORACLE = None
+
+
+def oracle():
+    global _ORACLE
+    if _ORACLE is None:
+        import __graft_entry__ as g
+        _ORACLE = g.load_oracle()
+    return _ORACLE
+
+
+def case(name):
+    global _CASES
+    if _CASES is None:
+        _CASES = cases()
+    return _CASES[name]
+
+
+def rand_matrix(seed, rows, cols, nnz, clustered):
+    """test_gpu_sweep.py's _rand under a seed of its own: (I, J, V) in shuffled file order"""
+    rng = np.random.default_rng(seed)
+    nnz = min(nnz, rows * cols)
+    if clustered:
+        keys = set()
+        for _ in range(max(1, nnz // 200)):
+            r0, c0 = int(rng.integers(0, rows)), int(rng.integers(0, cols))
+            rr = np.clip(r0 + rng.integers(-8, 9, 200), 0, rows - 1)
+            cc = np.clip(c0 + rng.integers(-8, 9, 200), 0, cols - 1)
+            keys.update((rr.astype(np.int64) * cols + cc).tolist())
+        keys = np.sort(np.fromiter(keys, dtype=np.int64))[:nnz]
+    else:
+        keys = rng.choice(rows * cols, nnz, replace=False)
+    v = rng.uniform(-1, 1, len(keys))
+    v[v == 0] = 0.5
+    p = rng.permutation(len(keys))
+    return (keys[p] // cols).astype(np.int32), (keys[p] % cols).astype(np.int32), v[p]
+
+
+def matrix(src):
+    """(rows, cols, I, J, V) of a record's matrix source: {"case": name} or {"rand": [seed, rows, cols, nnz, clustered]}"""
+    if "case" in src:
+        rows, cols, I, J, V, _ = case(src["case"])
+        return rows, cols, I, J, V
+    seed, rows, cols, nnz, clustered = src["rand"]
+    return (rows, cols) + rand_matrix(seed, rows, cols, nnz, bool(clustered))
+
+
+def values(shape, seed, special, dtype):
+    """the values a record names by seed: standard normal, or with test_gpu_sddmm.py's _specials mix"""
+    rng = np.random.default_rng(seed)
+    v = rng.standard_normal(shape)
+    if special:
+        sp = rng.random(v.shape) < 0.25
+        v[sp] = rng.choice(SPECIAL, int(sp.sum()))
+    return v.astype(dtype)
+
+
+def dt(name):
+    return np.dtype({"f64": np.float64, "f32": np.float32}[name])
+
+
+def dtname(dtype):
+    return "f32" if np.dtype(dtype) == np.float32 else "f64"
+
+
+def rows_of(rows, rp):
+    return np.repeat(np.arange(rows, dtype=np.int64), np.diff(np.asarray(rp, np.int64)))
+
+
+def same(got, want, kind="exact"):
+    """test_gpu_sddmm.py's _same: equal bits, NaN equals NaN, and +0 equals -0 only under min / max"""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return False
+    u = np.uint64 if got.dtype == np.float64 else np.uint32
+    ok = (got.view(u) == want.view(u)) | (np.isnan(got) & np.isnan(want))
+    if kind == "minmax":
+        ok |= (got == 0) & (want == 0)
+    return bool(np.all(ok))
+
+
+class MTiled:
+    def __init__(self, rows, cols, dtype, rp, ci, vals, prov=None):
+        self.rows, self.cols, self.dtype = int(rows), int(cols), np.dtype(dtype)
+        self.rp, self.ci = np.asarray(rp, np.int64), np.asarray(ci, np.int64)
+        self.vals = np.ascontiguousarray(vals, self.dtype)
+        self.vals_t = self.vals          # what the vals_t readers see (differs from vals only under the "stale_vals_t" mutation)
+        self.version = 0
+        self.prov = prov
+        self.built = set()               # lazily built structures (coverage bookkeeping only)
+        self.last_writer = None          # the last in-place writer kind (coverage bookkeeping only)
+
+    @property
+    def nnz(self):
+        return len(self.ci)
+
+    @property
+    def tile_rows(self):
+        return (self.rows + 15) // 16
+
+    def coo(self):
+        return rows_of(self.rows, self.rp), self.ci, self.vals
+
+    @classmethod
+    def from_coo(cls, rows, cols, I, J, V, dtype, prov=None):
+        rp, ci, v = semiringref.coo_to_csr(rows, cols, I, J, np.asarray(V, dtype))
+        return cls(rows, cols, dtype, rp, ci, v, prov)
+
+
+class MPlan:
+    def __init__(self, A, B, M, complement, lo, hi, semiring):
+        self.A, self.B, self.M, self.complement, self.lo, self.hi, self.semiring = A, B, M, bool(complement), lo, hi, semiring
+        self.options = dict(OPTION_DEFAULT)
+        self.state = 0
+        self.C = None                    # (rowptr, colidx, vals) of rows [row0, row1), as step 3 last left it
+        self.c_versions, self.c_semiring = None, None
+        self.passes = 0                  # completed pem_spgemm calls since the last option change (coverage bookkeeping only)
+        self.option_epoch = 0
+        self.trail = []                  # coverage bookkeeping only
+
+    @property
+    def row0(self):
+        return 16 * self.lo
+
+    @property
+    def row1(self):
+        return min(16 * self.hi, self.A.rows)
+
+
+class Result:
+    """what one record did: status; wrote = the id of the handle whose contents it (re)wrote, with the `kind` its values are
+    compared under ("exact", or "minmax": +0 == -0); out = what the call returns to the caller (CSR / COO triple or dense array)"""
+
+    def __init__(self, status=PEM_OK, wrote=None, kind="exact", out=None):
+        self.status, self.wrote, self.kind, self.out = status, wrote, kind, out
+
+
+def _kind(name):
+    return "minmax" if name in MINMAX or name in ("min", "max") else "exact"
+
+
+class Model:
+    def __init__(self, mutations=()):
+        assert all(m in MUTATIONS for m in mutations)
+        self.mut = set(mutations)
+        self.t, self.p = {}, {}
+
+    # ---- helpers -----------------------------------------------------------------------------------------------------------
+    def current(self, p):
+        return p.state == 3 and p.c_versions == (p.A.version, p.B.version) and p.c_semiring == p.semiring
+
+    def _wrote(self, T, vals, writer):
+        T.vals = np.ascontiguousarray(vals, T.dtype)
+        if "stale_vals_t" not in self.mut:
+            T.vals_t = T.vals
+        if "no_bump" not in self.mut:
+            T.version += 1
+        T.last_writer = writer
+        T.built.add("vmap_t")
+        for p in self.p.values():
+            if p.A is T or p.B is T:
+                p.trail.append("refresh")
+
+    def adopt(self, tid, vals):
+        """take the device's bits where the header leaves them open (the sign of a zero under min / max, NaN payloads)"""
+        T = self.t[tid]
+        same = T.vals_t is T.vals
+        T.vals = np.ascontiguousarray(vals, T.dtype).copy()
+        if same:
+            T.vals_t = T.vals
+
+    def product(self, p):
+        """C of plan p from its operands' current values, by the references of the plan tests"""
+        A, B = p.A, p.B
+        f32 = A.dtype == np.float32
+        if p.semiring == "plus_times":
+            o = oracle()
+            oa = o.Csr(A.rows, A.cols, rows_of(A.rows, A.rp), A.ci, A.vals.astype(np.float64))
+            ob = o.Csr(B.rows, B.cols, rows_of(B.rows, B.rp), B.ci, B.vals.astype(np.float64))
+            c = o.csr_spgemm(oa, ob, f32=f32)
+            rp, ci, v = (np.array(x) for x in c.arrays())
+            v = v.astype(A.dtype)
+        else:
+            rp, ci, v = semiringref.spgemm((A.rp, A.ci, A.vals), (B.rp, B.ci, B.vals), B.cols, p.semiring, A.dtype)
+        rp = np.asarray(rp, np.int64)
+        r0, r1 = p.row0, p.row1
+        e0, e1 = int(rp[r0]), int(rp[r1])
+        rp, ci, v = rp[r0:r1 + 1] - e0, np.asarray(ci)[e0:e1], np.asarray(v, A.dtype)[e0:e1]
+        if p.M is not None:
+            mi, mj, _ = p.M.coo()
+            rp, ci, v = maskref.filter_csr(rp, ci, v, mi, mj, B.cols, p.complement, row0=r0)
+        return np.asarray(rp, np.int32), np.asarray(ci, np.int32), np.ascontiguousarray(v, A.dtype)
+
+    def products(self, A, B):
+        """scalar products of A*B (the generator's size guard)"""
+        return int(np.diff(B.rp)[A.ci].sum()) if A.nnz else 0
+
+    def _step3(self, p):
+        p.C = self.product(p)
+        p.state = 3
+        p.c_versions, p.c_semiring = (p.A.version, p.B.version), p.semiring
+
+    # ---- one record ----------------------------------------------------------------------------------------------------------
+    def apply(self, rec):
+        op, ids, a = rec
+        with np.errstate(all="ignore"):
+            return getattr(self, "op_" + op)(ids, a)
+
+    # tilings
+    def _new(self, a, T):
+        self.t[a["out"]] = T
+        return Result(wrote=a["out"])
+
+    def _converted(self, a, transpose):
+        rows, cols, I, J, V = matrix(a["src"])
+        if transpose:
+            rows, cols, I, J = cols, rows, J, I
+        return self._new(a, MTiled.from_coo(rows, cols, I, J, V, dt(a["dtype"])))
+
+    def op_from_coo(self, ids, a):
+        return self._converted(a, a["transpose"])
+
+    def op_from_coo_device(self, ids, a):
+        return self._converted(a, a["transpose"])
+
+    def op_from_csr(self, ids, a):
+        return self._converted(a, False)
+
+    def op_close(self, ids, a):
+        del self.t[ids[0]]
+        return Result()
+
+    def op_save_load(self, ids, a):
+        T = self.t[ids[0]]
+        return self._new(a, MTiled(T.rows, T.cols, T.dtype, T.rp, T.ci, T.vals.copy()))
+
+    # plans
+    def op_plan_create(self, ids, a):
+        A, B = self.t[ids[0]], self.t[ids[1]]
+        M = self.t[ids[2]] if ids[2] is not None else None
+        hi = A.tile_rows if a["hi"] < 0 else a["hi"]
+        self.p[a["out"]] = MPlan(A, B, M, a["complement"], a["lo"], hi, a["semiring"])
+        return Result()
+
+    def op_plan_close(self, ids, a):
+        del self.p[ids[0]]
+        return Result()
+
+    def op_step1(self, ids, a):
+        p = self.p[ids[0]]
+        p.state = 1
+        p.trail.append("step1")
+        return Result()
+
+    def op_step2(self, ids, a):
+        p = self.p[ids[0]]
+        if p.state < 1:
+            return Result(PEM_E_STATE)
+        p.state = 2
+        p.trail.append("step2")
+        return Result()
+
+    def op_step3(self, ids, a):
+        p = self.p[ids[0]]
+        if p.state < 2:
+            return Result(PEM_E_STATE)
+        self._step3(p)
+        p.trail.append("step3")
+        return Result(wrote=ids[0], kind=_kind(p.semiring))
+
+    def op_spgemm(self, ids, a):
+        p = self.p[ids[0]]
+        self._step3(p)
+        p.trail.append("warm" if p.passes else "full")
+        p.passes += 1
+        return Result(wrote=ids[0], kind=_kind(p.semiring))
+
+    def op_set_semiring(self, ids, a):
+        self.p[ids[0]].semiring = a["semiring"]
+        return Result()
+
+    def op_set_option(self, ids, a):
+        p = self.p[ids[0]]
+        name, value = a["name"], a["value"]
+        if p.M is not None and name == "wide" and value == 0:
+            return Result(PEM_E_INVALID)
+        v = int(value) if name in OPTION_INT else int(value != 0)
+        if p.options[name] == v:
+            return Result()
+        p.options[name] = v
+        p.passes = 0
+        p.option_epoch += 1
+        p.trail.append("option")
+        if "no_option_reset" not in self.mut:
+            p.state = min(p.state, OPTION_KEEP[name])
+        return Result()
+
+    def op_export_csr(self, ids, a):
+        p = self.p[ids[0]]
+        if not self.current(p):
+            return Result(PEM_E_STATE)
+        return Result(out=p.C, kind=_kind(p.semiring))
+
+    def op_export_coo(self, ids, a):
+        p = self.p[ids[0]]
+        if not self.current(p):
+            return Result(PEM_E_STATE)
+        rp, ci, v = p.C
+        return Result(out=((p.row0 + rows_of(len(rp) - 1, rp)).astype(np.int32), ci, v), kind=_kind(p.semiring))
+
+    # derived tilings
+    def _c_as_tiling(self, p, transpose, prov):
+        rp, ci, v = p.C
+        I = p.row0 + rows_of(len(rp) - 1, rp)
+        A, B = p.A, p.B
+        if transpose:
+            return MTiled.from_coo(B.cols, A.rows, ci, I, v, A.dtype, prov)
+        return MTiled.from_coo(A.rows, B.cols, I, ci, v, A.dtype, prov)
+
+    def op_from_cplan(self, ids, a):
+        p = self.p[ids[0]]
+        if not self.current(p):
+            return Result(PEM_E_STATE)
+        return self._new(a, self._c_as_tiling(p, a["transpose"], ("cplan", ids[0], bool(a["transpose"]))))
+
+    def op_set_values_from_cplan(self, ids, a):
+        T, p = self.t[ids[0]], self.p[ids[1]]
+        if T.prov is None or T.prov[0] != "cplan" or T.prov[1] != ids[1]:
+            return Result(PEM_E_INVALID)
+        if not self.current(p):
+            return Result(PEM_E_STATE)
+        if T.prov[2]:
+            T.built.add("map_cplan")
+        self._wrote(T, self._c_as_tiling(p, T.prov[2], None).vals, "from_cplan")
+        return Result(wrote=ids[0])
+
+    def _ewise(self, A, B, op, pattern, alpha, beta):
+        ai, aj, av = A.coo()
+        bi, bj, bv = B.coo()
+        return ewiseref.ewise(A.cols, (ai, aj, av), (bi, bj, bv), op, pattern, alpha, beta)
+
+    def op_ewise(self, ids, a):
+        A, B = self.t[ids[0]], self.t[ids[1]]
+        I, J, V = self._ewise(A, B, a["op"], a["pattern"], a["alpha"], a["beta"])
+        r = self._new(a, MTiled.from_coo(A.rows, A.cols, I, J, V, A.dtype, ("ewise", ids[0], ids[1], a["op"], a["pattern"], a["alpha"], a["beta"])))
+        r.kind = _kind(a["op"])
+        return r
+
+    def op_set_values_from_ewise(self, ids, a):
+        T = self.t[ids[0]]
+        if T.prov is None or T.prov[0] != "ewise" or (T.prov[1], T.prov[2]) != (ids[1], ids[2]):
+            return Result(PEM_E_INVALID)
+        _, _, V = self._ewise(self.t[ids[1]], self.t[ids[2]], *T.prov[3:])
+        T.built.add("map_ewise")
+        self._wrote(T, V, "from_ewise")
+        return Result(wrote=ids[0], kind=_kind(T.prov[3]))
+
+    def op_select(self, ids, a):
+        A = self.t[ids[0]]
+        I, J, V = selectref.select(*A.coo(), a["op"], a["thunk"], A.dtype)
+        return self._new(a, MTiled.from_coo(A.rows, A.cols, I, J, V, A.dtype, ("select", ids[0], a["op"], a["thunk"])))
+
+    def op_set_values_from_select(self, ids, a):
+        T = self.t[ids[0]]
+        if T.prov is None or T.prov[0] != "select" or T.prov[1] != ids[1] or T.prov[2] not in selectref.POSITIONAL:
+            return Result(PEM_E_INVALID)
+        _, _, V = selectref.select(*self.t[ids[1]].coo(), T.prov[2], T.prov[3], T.dtype)
+        T.built.add("map_select")
+        self._wrote(T, V, "from_select")
+        return Result(wrote=ids[0])
+
+    def sddmm_operands(self, S, a, dtype):
+        """X (rows x k) and Y (cols x k) as column slices of wider buffers, as test_gpu_sddmm.py's _operands"""
+        k = a["k"]
+        Xw = values((S.rows, k + 3), a["seed"], a["special"], dtype)
+        Yw = values((S.cols, k + 11), a["seed"] + 1, a["special"], dtype)
+        return Xw, Yw, Xw[:, 2:2 + k], Yw[:, 5:5 + k]
+
+    def op_sddmm(self, ids, a):
+        S = self.t[ids[0]]
+        dtype = dt(a["dtype"])
+        _, _, X, Y = self.sddmm_operands(S, a, dtype)
+        I, J, _ = S.coo()
+        V = sddmmref.sddmm(I, J, X, Y, a["semiring"], dtype, oracle=oracle())
+        r = self._new(a, MTiled(S.rows, S.cols, dtype, S.rp, S.ci, V))
+        r.kind = _kind(a["semiring"])
+        return r
+
+    # value writers
+    def op_set_values(self, ids, a):
+        T = self.t[ids[0]]
+        V = values(T.nnz, a["seed"], a["special"], T.dtype)
+        if a["order"] == "col":          # V is in (col, row) order: position of every CSR entry in that order
+            I, J, _ = T.coo()
+            pos = np.empty(T.nnz, np.int64)
+            pos[np.lexsort((I, J))] = np.arange(T.nnz)
+            V = V[pos]
+        T.built.add("vmap_" + a["order"])
+        self._wrote(T, V, "set_values_" + a["order"])
+        return Result(wrote=ids[0])
+
+    def op_set_values_device(self, ids, a):
+        return self.op_set_values(ids, a)
+
+    def op_set_values_sddmm(self, ids, a):
+        T = self.t[ids[0]]
+        _, _, X, Y = self.sddmm_operands(T, a, T.dtype)
+        I, J, old = T.coo()
+        V = sddmmref.sddmm(I, J, X, Y, a["semiring"], T.dtype, old=old if a["accumulate"] else None, oracle=oracle())
+        self._wrote(T, V, "sddmm_acc" if a["accumulate"] else "sddmm")
+        return Result(wrote=ids[0], kind=_kind(a["semiring"]))
+
+    # dense readers
+    def op_mxv(self, ids, a):
+        T = self.t[ids[0]]
+        nx, ny = (T.rows, T.cols) if a["transpose"] else (T.cols, T.rows)
+        x = values(nx, a["seed"], a["special"], T.dtype)
+        y0 = values(ny, a["seed"] + 1, a["special"], T.dtype) if a["accumulate"] else None
+        if a["transpose"]:
+            T.built.add("mx_cols")
+        y = mxvref.mxv(T.rows, T.cols, T.rp, T.ci, T.vals, x, a["semiring"], T.dtype, y0=y0, oracle=oracle(), transpose=a["transpose"])
+        return Result(out=np.asarray(y, T.dtype), kind=_kind(a["semiring"]))
+
+    def op_reduce(self, ids, a):
+        T = self.t[ids[0]]
+        ny = T.cols if a["dim"] == "cols" else T.rows
+        y0 = values(ny, a["seed"] + 1, a["special"], T.dtype) if a["accumulate"] else None
+        if a["dim"] == "cols":
+            T.built.add("mx_cols")
+        y = mxvref.reduce(T.rows, T.cols, T.rp, T.ci, T.vals, a["op"], T.dtype, y0=y0, dim=a["dim"])
+        return Result(out=np.asarray(y, T.dtype), kind=_kind(a["op"]))
+
+    def spmm_operands(self, T, a):
+        """X as a column slice of a wider buffer, Y as the first k columns of one"""
+        k = a["k"]
+        nx, ny = (T.rows, T.cols) if a["transpose"] else (T.cols, T.rows)
+        Xw = values((nx, k + 3), a["seed"], a["special"], T.dtype)
+        Yfull = values((ny, k + 2), a["seed"] + 1, a["special"], T.dtype)
+        return Xw, Yfull
+
+    def op_spmm(self, ids, a):
+        T = self.t[ids[0]]
+        k = a["k"]
+        Xw, Yfull = self.spmm_operands(T, a)
+        if a["transpose"]:
+            T.built.add("mx_cols")
+        Y = spmmref.spmm_into(T.rows, T.cols, T.rp, T.ci, T.vals, Xw[:, 1:1 + k], Yfull, k, a["semiring"], T.dtype, accumulate=a["accumulate"],
+                              oracle=oracle(), transpose=a["transpose"])
+        return Result(out=Y, kind=_kind(a["semiring"]))
+
+    # housekeeping: nothing a caller can observe changes
+    def op_trim(self, ids, a):
+        return Result()
+
+    def op_reserve(self, ids, a):
+        return Result()
+
+    def op_synchronize(self, ids, a):
+        return Result()
