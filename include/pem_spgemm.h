@@ -447,8 +447,8 @@ typedef enum {
     PEM_OPT_WARM = 3,               /* 1 (default): repeat passes re-use the previous pass's sizes (device-verified); 0: read back */
     PEM_OPT_S3_BAND = 4,            /* 1 (default): many-pair C tiles of deep plans go to the wave-per-tile kernel              */
     PEM_OPT_EXPORT_ROWS = 7,        /* 0 (default): balanced chunk export; 1: 16 lanes per tile row (A/B baseline)             */
-    PEM_OPT__TEST_FIRST = 5,        /* (5, 6, 8-17: pem_test.h)                                                                 */
-    PEM_OPT__LAST = 18              /* one past the largest value                                                               */
+    PEM_OPT__TEST_FIRST = 5,        /* (5, 6, 8-20: pem_test.h)                                                                 */
+    PEM_OPT__LAST = 21              /* one past the largest value                                                               */
 } pem_option;
 pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, int64_t value);
 pem_status pem_cplan_get_option(const pem_cplan *plan, pem_option which, int64_t *value);

@@ -34,6 +34,14 @@ extern "C" {
 #define PEM_OPT_S3_POISON      ((pem_option)17) /* test hook: 1 fills C's values [0, nnz_c) with the NaN bit pattern 0x7FF4 per 16-bit half (fp64 and
                                                    fp32 alike) on the context's stream before step 3's kernels, so that an entry no kernel writes
                                                    keeps it; 2: the fill only, no step-3 kernel (a negative control for tests); 0 (default): off */
+#define PEM_OPT_S1_CLASS_SCAN  ((pem_option)18) /* 1 (default): step 1's row classification scans its own row totals (one launch less) where its grid
+                                                   fits the chained scan's 128 workgroups (65536 tile rows); 0: classification, then a scan launch */
+#define PEM_OPT_S2_TAIL_FOLD   ((pem_option)19) /* 1 (default): on repeat passes of plans of up to 8192 groups of 256 C tiles the offsets kernel sums the
+                                                   group counts in front of its groups itself; 0: a scan launch of the group counts before it      */
+#define PEM_OPT_S1_ONE_LAUNCH  ((pem_option)20) /* step 1's row bins in ONE launch on the main stream, rows above 8192 keys in segments: 0 never (the
+                                                   forked bins); 2 (default): where a plan sorts 32-bit keys, has no oversized row and no more
+                                                   segments than CUs (decided by its first pass), PEM_OPT_S1_SEGMENTS not set; 1: the same with any
+                                                   number of segments, and with PEM_OPT_S1_SEGMENTS set as well                                  */
 
 /* a further value of pem_cplan_array: int32[T_C] of a masked plan (pem_cplan_create_masked), for every C tile M's tile id at its
  * (tile row, tile column), -1 where M has none (complement masks only); readable after step 1 */

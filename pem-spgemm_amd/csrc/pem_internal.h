@@ -422,6 +422,11 @@ struct pem_cplan {
     pem::DevBuf seg_list;              // int2 per segment: (tile row, segment | segments of the row << 16)
     int opt_s2_transposed = 2;         // step 2's tile product from A's transposed masks: 0 never, 1 always, 2 on repeat passes of deep plans (see s2_pair_mask_t)
     int opt_s1_segments = 0;           // 1: rows above the 8192-key bin are sorted in column-range segments, one workgroup each (off by default: see s1_rowseg_kernel)
+    int opt_s1_class_scan = 1;         // 1: the row classification scans its own row totals where its grid fits the chained scan (s1_rowclass_kernel<.., SCAN>)
+    int opt_s2_tail_fold = 1;          // 1: on repeat passes s2_offsets_kernel sums the group counts in front of its groups itself (no scan launch between)
+    bool group_nnz_scanned = false;    // group_nnz holds the scanned group counts (else the counts: ensure_c_rowcolidx scans them first)
+    int opt_s1_one_launch = 2;         // step 1's row bins in one launch (s1_bins_kernel): 0 never, 1 wherever possible, 2 (default) where the big rows' segments are no more than CUs
+    int s1_one = -1;                   // ... the plan's mode, decided by its first pass from the counts: -1 not yet, 0 forked bins, 1 one launch
     int64_t w_nxl = 0;
     int w_nrows_xl = 0, w_max_xl = 0;
 };

@@ -3,6 +3,7 @@
 // reduce_by_key call sites (spgemm.cu:869-927, 990-1061, 1168, 1242, 1288) and the warp
 // scan of NSPARSE/utils_cuda_scan.h:19-35.  No thrust, no rocPRIM: plain HIP.
 #include "pem_internal.h"
+#include "scan_chain.h"
 #include <algorithm>
 #include <cstdarg>
 
@@ -281,24 +282,7 @@ constexpr int SCAN_TILE = SCAN_THREADS * 4;      // int4 per thread
 constexpr int SCAN_TILES_PER_BLOCK = 8;
 constexpr int SCAN_BLOCK_ITEMS = SCAN_TILE * SCAN_TILES_PER_BLOCK;
 
-template <typename T> __device__ __forceinline__ T wave_inclusive_scan(T v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        T t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-template <typename T> __device__ __forceinline__ T wave_reduce_sum(T v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
+// (wave_inclusive_scan / wave_reduce_sum: scan_chain.h)
 __global__ void __launch_bounds__(SCAN_THREADS) scan_reduce_kernel(const int *__restrict__ in, size_t n,
                                                                    long long *__restrict__ bsum)
 {
@@ -471,8 +455,7 @@ __global__ void __launch_bounds__(1024) scan_small_kernel(const int *in, int *ou
 // more -- the one this kernel had was wrong for in-place scans).  Should the wait ever run out (it cannot, see above),
 // FLAG_INTERNAL makes the host fail the call instead of returning a wrong scan.  The last block to finish clears the
 // words for the next scan.  A single 1024-thread block took 17 us for 62 k items and 35 us for 75 k.
-constexpr int SCAN_MID_ITEMS = 2048, SCAN_MID_BLOCKS = 128;
-constexpr unsigned long long SCAN_MID_VALID = 1ull << 63;
+constexpr int SCAN_MID_ITEMS = 2048;   // (SCAN_MID_BLOCKS and the look-back itself: scan_chain.h, shared with step 1's row classification)
 
 // (blockIdx.y: up to two independent arrays scanned by one launch -- step 1 scans its per-row tile counts and its per-256-pairs
 // first-pair counts back to back; each array has its own look-back words, and blocks past an array's end leave at once)
@@ -495,10 +478,9 @@ __global__ void __launch_bounds__(256) scan_mid_kernel(ScanMidArgs args, unsigne
     int *out = args.out[y];
     const size_t n = args.n[y];
     long long *total64 = args.total64[y];
-    unsigned long long *state = state_all + (size_t)y * (SCAN_MID_BLOCKS + 2);
-    int *ctl = reinterpret_cast<int *>(state + SCAN_MID_BLOCKS);   // done, ticket
+    unsigned long long *state = state_all + (size_t)y * SCAN_MID_SET_WORDS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_ticket = atomicAdd(&ctl[1], 1);
+    if (tid == 0) s_ticket = scan_chain_ticket(state);
     __syncthreads();
     const int blk = s_ticket;
     const size_t i0 = (size_t)blk * SCAN_MID_ITEMS + (size_t)tid * 8;
@@ -526,21 +508,8 @@ __global__ void __launch_bounds__(256) scan_mid_kernel(ScanMidArgs args, unsigne
     if (wave == 0) {
         if (blk == stall_ticket)                    // test hook: every later ticket has to sit out a long wait
             for (int k = 0; k < 50; ++k) __builtin_amdgcn_s_sleep(127);   // ~0.2 ms
-        // (62 bits of total: the block's own sum can exceed 2^31 when the scan as a whole overflows -- flagged below)
-        if (lane == 0) __hip_atomic_store(&state[blk], SCAN_MID_VALID | (unsigned long long)btotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        long long excl = 0;
-        bool ok = false;
-        for (long long polls = 0; polls < (1ll << 24) && !ok; ++polls) {
-            const unsigned long long a = lane < blk ? __hip_atomic_load(&state[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : SCAN_MID_VALID;
-            const unsigned long long b = 64 + lane < blk ? __hip_atomic_load(&state[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : SCAN_MID_VALID;
-            if (__ballot(!(a & SCAN_MID_VALID) || !(b & SCAN_MID_VALID)) == 0) {
-                excl = wave_reduce_sum((long long)(a & ~SCAN_MID_VALID) + (long long)(b & ~SCAN_MID_VALID));
-                ok = true;
-            } else {
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        if (!ok && lane == 0) flags[FLAG_INTERNAL] = 1;
+        if (lane == 0) scan_chain_publish(state, blk, btotal);
+        const long long excl = scan_chain_lookback(state, blk, lane, flags);
         if (lane == 0) s_excl = excl;
     }
     __syncthreads();
@@ -564,20 +533,15 @@ __global__ void __launch_bounds__(256) scan_mid_kernel(ScanMidArgs args, unsigne
             if (total64) *total64 = total;
             if (total > 0x7FFFFFFFLL) flags[FLAG_OVERFLOW] = 1;
         }
-        // the last block to get here has seen every other block read what it needed: clear the words for the next scan
-        if (atomicAdd(&ctl[0], 1) == nblk - 1) {
-            for (int b = 0; b < nblk; ++b) __hip_atomic_store(&state[b], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctl[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctl[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        scan_chain_done(state, nblk);
     }
 }
 
-static pem_status scan_mid_state(pem_ctx *ctx)
+pem_status scan_mid_state(pem_ctx *ctx)
 {
-    if (!ctx->scan_state.p) {   // look-back words + completion counter (two sets: scan_mid_kernel takes two arrays), zero between scans
-        PEM_TRY(ctx->scan_state.reserve(sizeof(unsigned long long) * 2 * (SCAN_MID_BLOCKS + 2)));
-        PEM_HIP(hipMemsetAsync(ctx->scan_state.p, 0, sizeof(unsigned long long) * 2 * (SCAN_MID_BLOCKS + 2), ctx->stream));
+    if (!ctx->scan_state.p) {   // look-back words + completion counter (scan_mid_kernel takes two arrays, step 1's row classification a set of its own), zero between scans
+        PEM_TRY(ctx->scan_state.reserve(sizeof(unsigned long long) * SCAN_MID_SETS * SCAN_MID_SET_WORDS));
+        PEM_HIP(hipMemsetAsync(ctx->scan_state.p, 0, sizeof(unsigned long long) * SCAN_MID_SETS * SCAN_MID_SET_WORDS, ctx->stream));
     }
     return PEM_OK;
 }

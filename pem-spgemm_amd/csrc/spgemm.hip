@@ -88,6 +88,12 @@ extern "C" pem_status pem_cplan_create(pem_ctx *ctx, const pem_tiled *A, const p
     p->opt_idx64 = env_is("PEM_S3_IDX64", "1");
     p->opt_mark = !env_is("PEM_S3_MARK", "0");
     p->opt_s1_segments = env_is("PEM_S1_SEGMENTS", "1");
+    p->opt_s1_class_scan = !env_is("PEM_S1_CLASS_SCAN", "0");
+    p->opt_s2_tail_fold = !env_is("PEM_S2_TAIL_FOLD", "0");
+    {
+        const char *e = getenv("PEM_S1_ONE_LAUNCH");
+        p->opt_s1_one_launch = e ? atoi(e) : 2;
+    }
     {
         const char *e = getenv("PEM_S3_EPW");
         p->opt_epw = e ? atoi(e) : 0;
@@ -201,6 +207,9 @@ static int *plan_option_slot(pem_cplan *p, pem_option which)
     case PEM_OPT_S1_SEGMENTS: return &p->opt_s1_segments;
     case PEM_OPT_S2_TRANSPOSED: return &p->opt_s2_transposed;
     case PEM_OPT_S3_POISON: return &p->opt_s3_poison;
+    case PEM_OPT_S1_CLASS_SCAN: return &p->opt_s1_class_scan;
+    case PEM_OPT_S2_TAIL_FOLD: return &p->opt_s2_tail_fold;
+    case PEM_OPT_S1_ONE_LAUNCH: return &p->opt_s1_one_launch;
     default: return nullptr;
     }
 }
@@ -218,7 +227,7 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
                   which == PEM_OPT_WIDE ? "PEM_OPT_WIDE" : "PEM_OPT_STEP1_GLOBAL_SORT", (long long)value);
         return PEM_E_INVALID;
     }
-    const int v = (which == PEM_OPT_S1_XLCAP || which == PEM_OPT_S3_EPW || which == PEM_OPT_S2_TRANSPOSED || which == PEM_OPT_S3_POISON) ? (int)value : (value != 0);
+    const int v = (which == PEM_OPT_S1_XLCAP || which == PEM_OPT_S3_EPW || which == PEM_OPT_S2_TRANSPOSED || which == PEM_OPT_S3_POISON || which == PEM_OPT_S1_ONE_LAUNCH) ? (int)value : (value != 0);
     if (*slot == v) return PEM_OK;
     *slot = v;
     // a repeat pass re-uses the sizes (and possibly the captured graph) of the previous one: whatever changes the kernels
@@ -230,14 +239,15 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
     int keep = 3;
     switch ((int)which) {
     case PEM_OPT_PRUNE: case PEM_OPT_STEP1_GLOBAL_SORT: case PEM_OPT_S1_FORCE_KEY64: case PEM_OPT_S1_XLCAP: case PEM_OPT_S1_XL_GLOBAL:
-    case PEM_OPT_S1_SEGMENTS: keep = 0; break;
-    case PEM_OPT_WIDE: case PEM_OPT_S3_DECODE: case PEM_OPT_S2_TRANSPOSED: keep = 1; break;
+    case PEM_OPT_S1_SEGMENTS: case PEM_OPT_S1_CLASS_SCAN: case PEM_OPT_S1_ONE_LAUNCH: keep = 0; break;
+    case PEM_OPT_WIDE: case PEM_OPT_S3_DECODE: case PEM_OPT_S2_TRANSPOSED: case PEM_OPT_S2_TAIL_FOLD: keep = 1; break;
     case PEM_OPT_S3_BAND: case PEM_OPT_S3_EPW: case PEM_OPT_S3_IDX64: case PEM_OPT_S3_MARK: case PEM_OPT_S3_XCD:
     case PEM_OPT_S3_POISON: keep = 2; break;
     default: break;                                    // warm passes, the export variant, serial bins: no step's result changes
     }
     if (plan->state > keep) plan->state = keep;
     if (keep == 0) {
+        plan->s1_one = -1;             // (what the bins' mode was decided from may have changed)
         plan->pairs_ready = false;
         plan->compact_valid = plan->c_rowidx_valid = false;
     }

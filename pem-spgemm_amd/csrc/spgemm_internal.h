@@ -10,6 +10,7 @@ namespace pem {
 
 constexpr int S3_CHUNK = 256;   // C entries per chunk of step 3's work index (= entries one wave takes, or half of them)
 constexpr int S2_GROUP = 256;   // C tiles per group of step 2's entry counts
+constexpr int S2_FOLD_GROUPS = 8192;   // ... and how many groups s2_offsets_kernel sums in front of its own (at most eight 16-byte loads per thread)
 
 // repeat pass on an unchanged plan: the sizes the host assumed (from the previous pass) against what this pass computed
 // counters of a pass of step 1 (plan->bin_count, ints): populations of the five row bins and of the oversized rows, the
@@ -24,10 +25,11 @@ struct WarmCheck {
     int masked;                        // masked plan: the mask filter's kept pairs and C tiles (d_scalars[4], [5]) are compared too
     long long Pm, TCm;
 };
+// (nnz_now: the pass's C_nnz -- d_scalars[2], or the value itself where the checking thread is the one that computed it)
 __device__ __forceinline__ void warm_check(const WarmCheck &w, const long long *__restrict__ d_scalars, const int *__restrict__ bin_count,
-                                           int *__restrict__ flags)
+                                           int *__restrict__ flags, const long long nnz_now)
 {
-    if (d_scalars[0] != w.P || d_scalars[1] != w.TC || d_scalars[2] != w.nnz || d_scalars[3] != w.Pall || bin_count[0] != w.c[0] ||
+    if (d_scalars[0] != w.P || d_scalars[1] != w.TC || nnz_now != w.nnz || d_scalars[3] != w.Pall || bin_count[0] != w.c[0] ||
         bin_count[1] != w.c[1] || bin_count[2] != w.c[2] || bin_count[3] != w.c[3] || bin_count[4] != w.c[4] || bin_count[BC_XL_TOTAL] != w.nxl || bin_count[BC_SEGS] != w.nsegs)
         flags[FLAG_CAPACITY] = 1;
     if (w.masked && (d_scalars[4] != w.Pm || d_scalars[5] != w.TCm)) flags[FLAG_CAPACITY] = 1;
@@ -35,6 +37,11 @@ __device__ __forceinline__ void warm_check(const WarmCheck &w, const long long *
         // the caller guarantees that nothing after this thread sets a flag in this pass (s2_offsets_kernel + step 3: none do)
         for (int i = 0; i < NUM_FLAGS; ++i) w.host_flags[i] = flags[i];
     }
+}
+__device__ __forceinline__ void warm_check(const WarmCheck &w, const long long *__restrict__ d_scalars, const int *__restrict__ bin_count,
+                                           int *__restrict__ flags)
+{
+    warm_check(w, d_scalars, bin_count, flags, d_scalars[2]);
 }
 
 // the size check of a repeat pass of this plan (host_flags unset)

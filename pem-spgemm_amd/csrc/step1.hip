@@ -20,6 +20,7 @@
 // products are dead, 83 % of scircuit's: the sort kernels spent a third to a half of their instructions on products they then
 // dropped, and the bins had to bound a row's products BEFORE pruning).
 #include "spgemm_internal.h"
+#include "scan_chain.h"
 
 using namespace pem;
 
@@ -177,6 +178,7 @@ constexpr int S1_QB0 = 6, S1_QB1 = 9, S1_QB2 = 11, S1_QB3 = 13, S1_QB4 = 15;    
 constexpr int S1_NLIST = 6;              // row lists: the five bins + the oversized rows
 constexpr int S1_PC1 = 64, S1_PC2 = 256, S1_PC3 = 1024;   // pieces (chunks) per row a bin's table holds (= its threads)
 constexpr int S1_SEG_T = 1024;           // keys per column-range segment of a big row (aimed at; a segment's sort holds 2048)
+constexpr int S1_NOSEG = 1 << 30;        // bit of the segment count: a big row that cannot be cut into segments (classification for both modes)
 constexpr int S1_XLL_MAX = 1 << 18;      // rows with more live products than this take the global sort (one workgroup -- or 256 segments -- per row would take too long)
 
 __global__ void __launch_bounds__(256) s1_total_kernel(const int *__restrict__ a_tile_colidx, int a_lo, int nA, const int *__restrict__ b_tile_rowptr,
@@ -430,17 +432,33 @@ __global__ void __launch_bounds__(64 * S1_XW, 8) s1_expand_kernel(const int *__r
 // (stable LDS radix sort on the column bits); above that one workgroup per row with the keys in global memory.
 // Also: the 64-bit total of ALL products (the reference's P, summed from the chunks), the closing words of the pass's arrays,
 // step 2's group counters, and the re-arming of the live list's allocator for the next pass.
+// SCAN: the kernel also scans the live totals into row_l (exclusive; row_l[mt] and scalars[0] = the total, P), which took a
+// launch of scan_mid_kernel behind it -- one short kernel, a chain of dependent round trips on a mostly empty chip, 6-10 us.
+// Where the grid is at most SCAN_MID_BLOCKS workgroups of S1_RC_SCAN_THREADS rows (webbase-1M: 62 501 tile rows, 123
+// workgroups) the scan's chain (scan_chain.h) runs here: a workgroup takes ITS rows by ticket, publishes their total as soon
+// as the rows' totals are known, bins its rows, and only then sums the totals of the earlier tickets -- by then they are there.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) s1_rowclass_kernel(const int *__restrict__ a_tile_rowptr, int tr_lo, int a_lo, int mt, int nchunks,
+constexpr int S1_RC_SCAN_THREADS = 512;
+template <int THREADS, bool SCAN>
+__global__ void __launch_bounds__(THREADS) s1_rowclass_kernel(const int *__restrict__ a_tile_rowptr, int tr_lo, int a_lo, int mt, int nchunks,
                                                           const int2 *__restrict__ aseg, const int2 *__restrict__ chunk_seg,
                                                           const long long *__restrict__ chunk_n, int tiny_ok, int cap4, int xlcap,
                                                           int *__restrict__ row_l, int4 *__restrict__ row_desc, int *__restrict__ row_list,
                                                           int *__restrict__ bin_count, int *__restrict__ xl_base, int *__restrict__ row_tc,
                                                           long long *__restrict__ scalars, int *__restrict__ flags, int *__restrict__ pairs_offset,
                                                           int *__restrict__ group_nnz, int ngroups, int *__restrict__ blk_heads, int nblk,
-                                                          int seg_on, int2 *__restrict__ seg_list)
+                                                          int seg_on, int2 *__restrict__ seg_list, unsigned long long *__restrict__ chain)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    __shared__ int s_ticket;
+    __shared__ long long rc_wsum[THREADS / 64];
+    __shared__ long long s_excl;
+    int blk = blockIdx.x;
+    if constexpr (SCAN) {
+        if (threadIdx.x == 0) s_ticket = scan_chain_ticket(chain);
+        __syncthreads();
+        blk = s_ticket;
+    }
+    const int i = blk * THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const unsigned long long lt = (1ull << lane) - 1ull;
     int nl = 0, np = 0;
@@ -466,7 +484,7 @@ __global__ void __launch_bounds__(256) s1_rowclass_kernel(const int *__restrict_
                 nl = tot > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)tot;                  // (beyond int32 the scan of the totals reports the overflow)
             }
         }
-        row_l[i] = nl;
+        if constexpr (!SCAN) row_l[i] = nl;
         row_desc[i] = make_int4((int)pos0, cnt0, (int)pos1, nl);
         xl_base[i] = -1;
         row_tc[i] = 0;
@@ -480,12 +498,20 @@ __global__ void __launch_bounds__(256) s1_rowclass_kernel(const int *__restrict_
         else if (nl <= S1_CAP3 && np <= S1_PC3) bin = 3;
         else if (nl <= cap4 && np <= S1_PC3) bin = 4;
         // rows above the 8192-key bin: column-range segments, one workgroup each (list 4 holds the rows, seg_list the segments)
-        if (seg_on && bin >= 4) bin = (nl <= S1_XLL_MAX && np <= S1_PC2) ? 4 : 5;
+        // seg_on == 2: BOTH -- list 4 holds the rows of the 32768-key bin as without segments AND seg_list their segments, so that
+        // the host can choose between the forked bins and the one launch (s1_bins_kernel) once it has the counts, on the plan's
+        // first pass, without classifying again.  A row of more pieces than a segment's table holds cannot be cut: it marks the
+        // segment count (S1_NOSEG) and the plan keeps the forked bins.
+        if (seg_on == 1 && bin >= 4) bin = (nl <= S1_XLL_MAX && np <= S1_PC2) ? 4 : 5;
         if (nl > xlcap) bin = 5;                                 // test hook: rows above xlcap live products take the oversized-row path
         if (seg_on && bin == 4) {
-            const int G = (nl + S1_SEG_T - 1) / S1_SEG_T;
-            const int s0 = atomicAdd(&bin_count[BC_SEGS], G);
-            for (int g = 0; g < G; ++g) seg_list[s0 + g] = make_int2(i, g | (G << 16));
+            if (seg_on == 2 && np > S1_PC2) {
+                atomicOr(&bin_count[BC_SEGS], S1_NOSEG);
+            } else {
+                const int G = (nl + S1_SEG_T - 1) / S1_SEG_T;
+                const int s0 = atomicAdd(&bin_count[BC_SEGS], G) & (S1_NOSEG - 1);
+                for (int g = 0; g < G; ++g) seg_list[s0 + g] = make_int2(i, g | (G << 16));
+            }
         }
     }
     // slots by ballot + prefix popcount inside a wave, one LDS atomic per wave and bin inside the block, ONE global
@@ -494,7 +520,18 @@ __global__ void __launch_bounds__(256) s1_rowclass_kernel(const int *__restrict_
     __shared__ long long blk_all;
     if (threadIdx.x < S1_NLIST) blk_cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) blk_all = 0;
+    long long rc_inc = 0;
+    if constexpr (SCAN) {
+        rc_inc = wave_inclusive_scan((long long)nl);
+        if (lane == 63) rc_wsum[threadIdx.x >> 6] = rc_inc;
+    }
     __syncthreads();
+    long long rc_btotal = 0;
+    if constexpr (SCAN) {   // the workgroup's total, for the later tickets: out as early as it is known
+#pragma unroll
+        for (int w = 0; w < THREADS / 64; ++w) rc_btotal += rc_wsum[w];
+        if (threadIdx.x == 0) scan_chain_publish(chain, blk, rc_btotal);
+    }
     int wbase = 0, rank = 0;
 #pragma unroll
     for (int b = 0; b < S1_NLIST; ++b) {
@@ -518,7 +555,30 @@ __global__ void __launch_bounds__(256) s1_rowclass_kernel(const int *__restrict_
     __syncthreads();
     if (threadIdx.x < S1_NLIST) blk_base[threadIdx.x] = blk_cnt[threadIdx.x] ? atomicAdd(&bin_count[threadIdx.x], blk_cnt[threadIdx.x]) : 0;
     if (threadIdx.x == 0 && blk_all) atomicAdd(reinterpret_cast<unsigned long long *>(&scalars[3]), (unsigned long long)blk_all);
+    if constexpr (SCAN) {   // the last wave (the first ones hold the atomics above) sums the totals of the earlier tickets
+        if ((threadIdx.x >> 6) == THREADS / 64 - 1) {
+            const long long excl = scan_chain_lookback(chain, blk, lane, flags);
+            if (lane == 0) s_excl = excl;
+        }
+    }
     __syncthreads();
+    if constexpr (SCAN) {
+        const long long carry = s_excl;
+        long long woff = 0;
+#pragma unroll
+        for (int w = 0; w < THREADS / 64; ++w)
+            if (w < (int)(threadIdx.x >> 6)) woff += rc_wsum[w];
+        if (i < mt) row_l[i] = (int)(carry + woff + rc_inc - nl);
+        if (threadIdx.x == 0) {
+            if (blk == (int)gridDim.x - 1) {                     // (the last ticket: rows past mt add nothing, so this is the total)
+                const long long total = carry + rc_btotal;
+                row_l[mt] = (int)total;
+                scalars[0] = total;
+                if (total > 0x7FFFFFFFLL) flags[FLAG_OVERFLOW] = 1;
+            }
+            scan_chain_done(chain, (int)gridDim.x);
+        }
+    }
     if (bin >= 0) row_list[(size_t)bin * mt + blk_base[bin] + wbase + rank] = i;
     if (bin == 5) {                                              // oversized rows are few
         xl_base[i] = atomicAdd(&bin_count[BC_XL_TOTAL], nl);
@@ -555,6 +615,18 @@ template <> __device__ __forceinline__ uint64_t s1_shfl_xor<uint64_t>(uint64_t v
     return (uint64_t)__shfl_xor((unsigned long long)v, mask, 64);
 }
 
+// The barrier of a THREADS-thread row sort.  A one-wave sort (THREADS == 64) owns its LDS slice alone -- the wave's LDS accesses
+// are issued in program order, so it needs no workgroup barrier, and must not have one where sixteen such sorts of different
+// lengths share a workgroup (s1_bins_kernel): only the compiler is told not to move LDS accesses across the point.
+template <int THREADS> __device__ __forceinline__ void s1_sync()
+{
+    if constexpr (THREADS == 64) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __syncthreads();
+    }
+}
 template <typename KeyT, int THREADS, int EPT, int LOGT>
 __device__ __forceinline__ void s1_bitonic_regs(KeyT (&v)[EPT], KeyT *lds, const int tid, const bool reverse = false)
 {
@@ -600,20 +672,20 @@ __device__ __forceinline__ void s1_bitonic_regs(KeyT (&v)[EPT], KeyT *lds, const
                 const bool lower = (tid & tm) == 0;
 #pragma unroll
                 for (int m = 0; m < EPT; ++m) lds[m * THREADS + tid] = v[m];
-                __syncthreads();
+                s1_sync<THREADS>();
 #pragma unroll
                 for (int m = 0; m < EPT; ++m) {
                     const KeyT pv = lds[m * THREADS + (tid ^ tm)];
                     const bool up = (((tid << LOGE) | m) & kk) == 0;
                     v[m] = ((v[m] < pv) == (lower == up)) ? v[m] : pv;
                 }
-                __syncthreads();
+                s1_sync<THREADS>();
             }
         }
     }
 #pragma unroll
     for (int m = 0; m < EPT; ++m) lds[reverse ? (THREADS * EPT - 1 - ((tid << LOGE) | m)) : ((tid << LOGE) | m)] = v[m];
-    __syncthreads();
+    s1_sync<THREADS>();
 }
 // ------------------------------------------------------------------------------------------
 // phase 3: the row sorts.  A row's live products arrive as (tile column, position in the row's live list) keys; equal tile
@@ -637,15 +709,13 @@ __device__ __forceinline__ void s1_note_heads(int *__restrict__ blk_heads, const
 }
 
 // rows of at most 64 live products in at most two pieces: one wave, one key per lane, everything in registers
-__global__ void __launch_bounds__(256) s1_tiny_kernel(const int *__restrict__ row_list, int nrows_bin, const int4 *__restrict__ row_desc,
-                                                      const int *__restrict__ row_lbase, const int *__restrict__ lj, const int2 *__restrict__ lab,
-                                                      int *__restrict__ pairs_a, int *__restrict__ pairs_b, int *__restrict__ pair_col,
-                                                      int *__restrict__ blk_heads, int *__restrict__ row_tc)
+// (one wave: tile row i)
+__device__ __forceinline__ void s1_tiny_row(const int i, const int4 *__restrict__ row_desc, const int *__restrict__ row_lbase,
+                                            const int *__restrict__ lj, const int2 *__restrict__ lab, int *__restrict__ pairs_a,
+                                            int *__restrict__ pairs_b, int *__restrict__ pair_col, int *__restrict__ blk_heads,
+                                            int *__restrict__ row_tc)
 {
     const int lane = threadIdx.x & 63;
-    const int li = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (li >= nrows_bin) return;                                 // (wave-uniform)
-    const int i = __builtin_amdgcn_readfirstlane(row_list[li]);
     const int4 d = row_desc[i];                                  // (first piece, its length, second piece, live total)
     const int lp0 = row_lbase[i], nl = d.w;
     const bool valid = lane < nl;
@@ -680,6 +750,15 @@ __global__ void __launch_bounds__(256) s1_tiny_kernel(const int *__restrict__ ro
         s1_note_heads(blk_heads, lp0, bal);
         row_tc[i] = __popcll(bal);
     }
+}
+__global__ void __launch_bounds__(256) s1_tiny_kernel(const int *__restrict__ row_list, int nrows_bin, const int4 *__restrict__ row_desc,
+                                                      const int *__restrict__ row_lbase, const int *__restrict__ lj, const int2 *__restrict__ lab,
+                                                      int *__restrict__ pairs_a, int *__restrict__ pairs_b, int *__restrict__ pair_col,
+                                                      int *__restrict__ blk_heads, int *__restrict__ row_tc)
+{
+    const int li = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (li >= nrows_bin) return;                                 // (wave-uniform)
+    s1_tiny_row(__builtin_amdgcn_readfirstlane(row_list[li]), row_desc, row_lbase, lj, lab, pairs_a, pairs_b, pair_col, blk_heads, row_tc);
 }
 
 template <typename KeyT, int CAP, int QB, int THREADS>
@@ -780,7 +859,7 @@ struct S1Row {
         KeyT v[EPT];
 #pragma unroll
         for (int m = 0; m < EPT; ++m) v[m] = keys[m * THREADS + tid];
-        __syncthreads();   // everyone has its keys in registers before the sort's LDS stages overwrite them
+        s1_sync<THREADS>();   // everyone has its keys in registers before the sort's LDS stages overwrite them
         s1_bitonic_regs<KeyT, THREADS, EPT, LOGT>(v, keys, tid);
     }
 };
@@ -833,9 +912,9 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
 {
     constexpr int LOGT = THREADS == 64 ? 6 : THREADS == 256 ? 8 : 10;
     constexpr int EMAX = CAP / THREADS, WAVES = THREADS / 64;
-    static_assert(EMAX == 8 || EMAX == 32, "a bin sorts up to 8 (or, for the largest, 32) keys per thread");
+    static_assert(EMAX == 8 || EMAX == 32 || (EMAX == 2 && THREADS == 1024), "a bin sorts up to 8 (or, for the largest, 32) keys per thread; 2048-key rows on sixteen waves: 2");
     static_assert(CAP <= (1 << QB), "the key's index field holds every position of the row's list");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = THREADS == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;   // (one-wave rows: also as one of many in a workgroup)
     (void)li;
     (void)LOGT;
 #ifdef PEM_S1_DEBUG
@@ -868,7 +947,7 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
         int ex = inc - cnt;
         if (THREADS > 64 && np > 64) {               // (block-uniform) the pieces spill over the first wave
             if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
+            s1_sync<THREADS>();
 #pragma unroll
             for (int w = 0; w < WAVES; ++w)
                 if (w < wave) ex += wsum[w];
@@ -879,7 +958,7 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
         }
         if (tid == 0) pdst[np] = nl;
     }
-    __syncthreads();
+    s1_sync<THREADS>();
     S1_DBG_MARK(0);
     // the keys: (tile column, position in the row's list), list order.  Every thread takes positions of the list, finds their
     // piece (a short search over the table; most rows have one piece) and loads from the live list: all the row's loads are
@@ -904,7 +983,7 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
         while (upto < nl) upto <<= 1;
         for (int x = nl + tid; x < upto; x += THREADS) keys[x] = ~KeyT(0);
     }
-    __syncthreads();
+    s1_sync<THREADS>();
     S1_DBG_MARK(1);
     S1Row<KeyT, CAP, QB, THREADS> row;
     row.keys = keys;
@@ -969,7 +1048,7 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
     int base = mytiles;
     if constexpr (THREADS > 64) {
         if (lane == 0) wsum[wave] = mytiles;
-        __syncthreads();
+        s1_sync<THREADS>();
         base = 0;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) base += wsum[w];
@@ -991,7 +1070,7 @@ __device__ __forceinline__ void s1_rowsort_row(KeyT *const keys, unsigned *const
         }
     }
 #endif
-    __syncthreads();                                  // the tables are rebuilt by the next row
+    s1_sync<THREADS>();                                  // the tables are rebuilt by the next row
 }
 
 template <typename KeyT, int CAP, int QB, int THREADS>
@@ -1049,25 +1128,22 @@ __global__ void __launch_bounds__(1024, 4)
 // 8 us less (the other bins then set its length); the round-2 stand-in, 104 such rows: step 1 0.61 ms against 0.50 -- 1 300
 // workgroups each reading a 12 k-key row.  So the option (PEM_OPT_S1_SEGMENTS) is OFF by default.  Ranges are cut evenly over B's tile columns; one that holds more than 2048 keys is halved until it fits, a
 // single column with more than 2048 keys (a C tile of that many pairs) is emitted as it stands -- one column needs no sort.
+// one segment (the LDS arrays are the calling kernel's: keys[S1_CAP2], gidx[S1_CAP2] -- position in the row's list of the key at
+// every position of the segment's list --, psrc[S1_PC2], pdst[S1_PC2 + 1], wcnt / wlow / wsum[16])
 template <typename KeyT>
-__global__ void __launch_bounds__(1024) s1_rowseg_kernel(const int2 *__restrict__ seg_list, int nsegs, const int *__restrict__ a_tile_rowptr, int tr_lo,
-                                                        int a_lo, const int2 *__restrict__ aseg, const int *__restrict__ row_lbase,
-                                                        const int *__restrict__ lj, const int2 *__restrict__ lab, int tile_cols,
-                                                        int *__restrict__ pairs_a, int *__restrict__ pairs_b, int *__restrict__ pair_col,
-                                                        int *__restrict__ blk_heads, int *__restrict__ row_tc)
+__device__ __forceinline__ void s1_rowseg_one(KeyT *const keys, unsigned *const gidx, unsigned *const psrc, int *const pdst, int *const wcnt,
+                                              int *const wlow, int *const wsum, const int2 sd, const int *__restrict__ a_tile_rowptr, int tr_lo,
+                                              int a_lo, const int2 *__restrict__ aseg, const int *__restrict__ row_lbase,
+                                              const int *__restrict__ lj, const int2 *__restrict__ lab, int tile_cols,
+                                              int *__restrict__ pairs_a, int *__restrict__ pairs_b, int *__restrict__ pair_col,
+                                              int *__restrict__ blk_heads, int *__restrict__ row_tc)
 {
     // (sixteen waves: every segment reads its whole row, and with four waves a directory row's 12 k keys were two dozen dependent
     // round trips per wave -- 60 us for a segment whose sort takes four)
     constexpr int CAP = S1_CAP2, QB = S1_QB2, THREADS = 1024, WAVES = 16, LOGT = 10;
-    __shared__ KeyT keys[CAP];
-    __shared__ unsigned gidx[CAP];       // position in the row's list of the key at every position of the segment's list
-    __shared__ unsigned psrc[S1_PC2];
-    __shared__ int pdst[S1_PC2 + 1];
-    __shared__ int wcnt[WAVES], wlow[WAVES], wsum[WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    for (int si = blockIdx.x; si < nsegs; si += gridDim.x) {
-        const int2 sd = seg_list[si];
+    {
         const int i = sd.x, g = sd.y & 0xFFFF, G = sd.y >> 16;
         const int ra0 = a_tile_rowptr[tr_lo + i] - a_lo, ra1 = a_tile_rowptr[tr_lo + i + 1] - a_lo;
         const int lp0 = row_lbase[i], nl = row_lbase[i + 1] - lp0;
@@ -1233,6 +1309,99 @@ __global__ void __launch_bounds__(1024) s1_rowseg_kernel(const int2 *__restrict_
         if (lane == 0 && tiles) atomicAdd(&row_tc[i], tiles);
         __syncthreads();                                 // the tables are rebuilt by the next segment
     }
+}
+template <typename KeyT>
+__global__ void __launch_bounds__(1024) s1_rowseg_kernel(const int2 *__restrict__ seg_list, int nsegs, const int *__restrict__ a_tile_rowptr, int tr_lo,
+                                                        int a_lo, const int2 *__restrict__ aseg, const int *__restrict__ row_lbase,
+                                                        const int *__restrict__ lj, const int2 *__restrict__ lab, int tile_cols,
+                                                        int *__restrict__ pairs_a, int *__restrict__ pairs_b, int *__restrict__ pair_col,
+                                                        int *__restrict__ blk_heads, int *__restrict__ row_tc)
+{
+    __shared__ KeyT keys[S1_CAP2];
+    __shared__ unsigned gidx[S1_CAP2];
+    __shared__ unsigned psrc[S1_PC2];
+    __shared__ int pdst[S1_PC2 + 1];
+    __shared__ int wcnt[16], wlow[16], wsum[16];
+    for (int si = blockIdx.x; si < nsegs; si += gridDim.x)
+        s1_rowseg_one<KeyT>(keys, gidx, psrc, pdst, wcnt, wlow, wsum, seg_list[si], a_tile_rowptr, tr_lo, a_lo, aseg, row_lbase, lj, lab, tile_cols,
+                            pairs_a, pairs_b, pair_col, blk_heads, row_tc);
+}
+
+// ALL ROW BINS IN ONE LAUNCH (32-bit keys, no oversized rows, few rows above 8192 keys: see launch_rowsorts).  As four kernels on
+// four streams the bins cost two cross-queue edges in a replayed graph -- 8 us until the main stream's bins start, 18-26 us until
+// the auxiliary streams' do, 10 us for the join -- and a fork that four hardware queues must be there for.  Here a 1024-thread
+// workgroup's role comes from blockIdx against the bin populations, the long roles first:
+//   segments of the rows above 8192 keys (s1_rowseg_one)      one workgroup per column-range segment
+//   8192-key rows                                             one workgroup per row, stable LDS radix sort
+//   2048-key rows                                             one workgroup per row through the same radix body at CAP 2048 (the
+//                                                             four-wave bitonic body holds workgroup barriers inside data-dependent
+//                                                             trip counts, so four rows cannot share a workgroup as they are)
+//   512-key rows, tiny rows                                   sixteen per workgroup, one wave each, no workgroup barrier
+// LDS: the 8192-key role's 56 KB (keys 32, pieces 8, histogram 16): two workgroups per CU, which is also what 64 VGPRs allow.
+struct S1BinsArgs {
+    const int *row_list;
+    int mt, n0, n1, n2, n3, nsegs;
+    const int2 *seg_list;
+    const int *a_tile_rowptr;
+    int tr_lo, a_lo;
+    const int2 *aseg;
+    const int *row_lbase;
+    const int4 *row_desc;
+    const int *lj;
+    const int2 *lab;
+    int tile_cols, bits_tc;
+    int *pairs_a, *pairs_b, *pair_col, *blk_heads, *row_tc;
+};
+constexpr int S1_BINS_LDS = 4 * S1_CAP3 + 4 * 1024 + 4 * 1028 + 4 * 16 + 4 * 16 * 256;
+constexpr int S1_BINS_W1 = 4 * S1_CAP1 + 4 * S1_PC1 + 4 * (S1_PC1 + 4) + 16;    // bytes of one wave's 512-key row
+static_assert(16 * S1_BINS_W1 <= S1_BINS_LDS && 8 * S1_CAP2 + 8 * S1_PC2 + 16 + 3 * 64 <= S1_BINS_LDS, "every role fits the 8192-key role's LDS");
+__global__ void __launch_bounds__(1024, 8) s1_bins_kernel(const S1BinsArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[S1_BINS_LDS];
+    const int wave = threadIdx.x >> 6;
+    int b = blockIdx.x;
+    if (b < a.nsegs) {
+        uint32_t *keys = reinterpret_cast<uint32_t *>(smem);
+        unsigned *gidx = keys + S1_CAP2, *psrc = gidx + S1_CAP2;
+        int *pdst = reinterpret_cast<int *>(psrc + S1_PC2), *wcnt = pdst + S1_PC2 + 4, *wlow = wcnt + 16, *wsum = wlow + 16;
+        s1_rowseg_one<uint32_t>(keys, gidx, psrc, pdst, wcnt, wlow, wsum, a.seg_list[b], a.a_tile_rowptr, a.tr_lo, a.a_lo, a.aseg, a.row_lbase, a.lj,
+                                a.lab, a.tile_cols, a.pairs_a, a.pairs_b, a.pair_col, a.blk_heads, a.row_tc);
+        return;
+    }
+    b -= a.nsegs;
+    if (b < a.n3 + a.n2) {
+        uint32_t *keys = reinterpret_cast<uint32_t *>(smem);
+        unsigned *psrc = keys + S1_CAP3;
+        int *pdst = reinterpret_cast<int *>(psrc + 1024), *wsum = pdst + 1028;
+        unsigned *hist = reinterpret_cast<unsigned *>(wsum + 16);
+        if (b < a.n3)
+            s1_rowsort_row<uint32_t, S1_CAP3, S1_QB3, 1024>(keys, psrc, pdst, wsum, hist, a.row_list[(size_t)3 * a.mt + b], b, a.a_tile_rowptr, a.tr_lo,
+                                                            a.a_lo, a.aseg, a.row_lbase, a.lj, a.lab, a.pairs_a, a.pairs_b, a.pair_col, a.blk_heads,
+                                                            a.row_tc, S1_QB3 + a.bits_tc);
+        else
+            s1_rowsort_row<uint32_t, S1_CAP2, S1_QB2, 1024>(keys, psrc, pdst, wsum, hist, a.row_list[(size_t)2 * a.mt + b - a.n3], b - a.n3,
+                                                            a.a_tile_rowptr, a.tr_lo, a.a_lo, a.aseg, a.row_lbase, a.lj, a.lab, a.pairs_a, a.pairs_b,
+                                                            a.pair_col, a.blk_heads, a.row_tc, S1_QB2 + a.bits_tc);
+        return;
+    }
+    b -= a.n3 + a.n2;
+    const int nb1 = (a.n1 + 15) >> 4;
+    if (b < nb1) {
+        const int li = b * 16 + wave;
+        if (li >= a.n1) return;                                  // (wave-uniform; no workgroup barrier below)
+        uint32_t *keys = reinterpret_cast<uint32_t *>(smem + (size_t)wave * S1_BINS_W1);
+        unsigned *psrc = keys + S1_CAP1;
+        int *pdst = reinterpret_cast<int *>(psrc + S1_PC1), *wsum = pdst + S1_PC1 + 4;
+        s1_rowsort_row<uint32_t, S1_CAP1, S1_QB1, 64>(keys, psrc, pdst, wsum, nullptr, __builtin_amdgcn_readfirstlane(a.row_list[(size_t)a.mt + li]), li,
+                                                      a.a_tile_rowptr, a.tr_lo, a.a_lo, a.aseg, a.row_lbase, a.lj, a.lab, a.pairs_a, a.pairs_b,
+                                                      a.pair_col, a.blk_heads, a.row_tc, S1_QB1 + a.bits_tc);
+        return;
+    }
+    b -= nb1;
+    const int li = b * 16 + wave;
+    if (li < a.n0)
+        s1_tiny_row(__builtin_amdgcn_readfirstlane(a.row_list[li]), a.row_desc, a.row_lbase, a.lj, a.lab, a.pairs_a, a.pairs_b, a.pair_col, a.blk_heads,
+                    a.row_tc);
 }
 
 // Oversized rows (above the largest LDS bin, or more pieces than a bin's table holds): the row's pieces are copied into the
@@ -1599,10 +1768,41 @@ struct S1Lanes {
     }
 };
 
-static void launch_rowsorts(pem_ctx *ctx, pem_cplan *p, S1Lanes &lanes, const int *counts, int mt, int bits_tc, bool force64, int nsegs)
+static void launch_rowsorts(pem_ctx *ctx, pem_cplan *p, S1Lanes &lanes, const int *counts, int mt, int bits_tc, bool force64, int nsegs, bool seg_on,
+                            bool one_launch)
 {
     const pem_tiled *A = p->A;
     int *rl = p->row_list.as<int>();
+    if (one_launch) {                      // every bin in one launch on the main stream (s1_bins_kernel; the caller checked what it needs)
+        S1BinsArgs a;
+        a.row_list = rl;
+        a.mt = mt;
+        a.n0 = counts[0];
+        a.n1 = counts[1];
+        a.n2 = counts[2];
+        a.n3 = counts[3];
+        a.nsegs = nsegs;
+        a.seg_list = p->seg_list.as<int2>();
+        a.a_tile_rowptr = A->tile_rowptr.as<int>();
+        a.tr_lo = p->tr_lo;
+        a.a_lo = p->a_lo;
+        a.aseg = p->aseg.as<int2>();
+        a.row_lbase = p->row_lbase.as<int>();
+        a.row_desc = p->row_desc.as<int4>();
+        a.lj = p->live_j.as<int>();
+        a.lab = p->live_ab.as<int2>();
+        a.tile_cols = p->B->tile_cols;
+        a.bits_tc = bits_tc;
+        a.pairs_a = p->pairs_a.as<int>();
+        a.pairs_b = p->pairs_b.as<int>();
+        a.pair_col = p->pair_col.as<int>();
+        a.blk_heads = p->blk_heads.as<int>();
+        a.row_tc = p->c_tile_rowptr.as<int>();
+        const size_t grid = (size_t)nsegs + counts[3] + counts[2] + (counts[1] + 15) / 16 + (counts[0] + 15) / 16;
+        lanes.on(0);
+        if (grid > 0) PEM_LAUNCH(ctx, s1_bins_kernel, (unsigned)grid, 1024, a);
+        return;
+    }
 
 #define PEM_ROWSORT_ARGS(BIN, QB)                                                                                                        \
     rl + (size_t)(BIN) * mt, counts[BIN], A->tile_rowptr.as<int>(), p->tr_lo, p->a_lo, p->aseg.as<int2>(), p->row_lbase.as<int>(),       \
@@ -1618,9 +1818,9 @@ static void launch_rowsorts(pem_ctx *ctx, pem_cplan *p, S1Lanes &lanes, const in
                              THREADS, PEM_ROWSORT_ARGS(BIN, QB));                                                                        \
     } while (0)
     const int ncu = ctx->cu_count > 0 ? ctx->cu_count : 256;
-    const bool merge_big = !p->opt_s1_segments && !p->opt_s1_serial && counts[4] > 0 && counts[3] > 0 && counts[3] + counts[4] <= ncu &&
+    const bool merge_big = !seg_on && !p->opt_s1_serial && counts[4] > 0 && counts[3] > 0 && counts[3] + counts[4] <= ncu &&
                            bits_tc + S1_QB4 <= 32 && !force64;
-    if (p->opt_s1_segments) {
+    if (seg_on) {
         if (nsegs > 0) {                   // rows above the 8192-key bin, one workgroup per column-range segment
             lanes.on(0);
             if (bits_tc + S1_QB2 <= 32 && !force64)
@@ -1730,8 +1930,19 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
     }
     const int nblk_reset = p->warm_pass ? (int)(p->w_P / 256 + 1) : 0;   // (the buffer is in place since the plan's first pass)
     // rows above the 8192-key bin are sorted in column-range segments (PEM_OPT_S1_SEGMENTS = 0: one workgroup per row, the
-    // 32768-key bin); a row has at most nl / 1024 + 1 segments
-    const int seg_on = p->opt_s1_segments != 0;
+    // 32768-key bin); a row has at most nl / 1024 + 1 segments.
+    // ONE LAUNCH for all bins (s1_bins_kernel, PEM_OPT_S1_ONE_LAUNCH): 32-bit keys, no oversized rows, and the rows above 8192 keys in
+    // segments -- no more of those than CUs (option 1: any number).  Segments change what the classification does, and a plan's
+    // first pass learns its counts only after it -- so where the one launch is possible at all the classification emits BOTH lists
+    // (seg_on 2: list 4 as without segments, and the segments), the first pass decides from its counts (s1_one) and every later
+    // pass of the plan finds the same lists.
+    const int ncu_bins = ctx->cu_count > 0 ? ctx->cu_count : 256;
+    // (PEM_OPT_S1_SEGMENTS keeps its meaning: a plan that asks for the segments gets s1_rowseg_kernel on the forked path, unless
+    // the one launch is forced as well)
+    const bool one_allowed = p->opt_s1_one_launch != 0 && !force64 && bits_tc + S1_QB3 <= 32 && !p->opt_s1_serial &&
+                             (p->opt_s1_segments == 0 || p->opt_s1_one_launch == 1);
+    const int seg_on = p->opt_s1_segments != 0 ? 1 : (one_allowed ? 2 : 0);
+    if (!one_allowed) p->s1_one = 0;
     PEM_TRY(p->seg_list.reserve(sizeof(int2) * (ncap / S1_SEG_T + (size_t)mt + 16)));
     const int prune = p->opt_prune;
     PEM_LAUNCH(ctx, s1_expand_kernel, (unsigned)(nchunks > 0 ? nchunks : 1), 64 * S1_XW, A->tile_colidx.as<int>(), A->tile_occ.as<uint32_t>(),
@@ -1742,13 +1953,23 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
     // are scanned in place (row r's pairs, and its C tile slots, start at row_lbase[r])
     {
         const size_t span = std::max(std::max((size_t)mt, (size_t)nchunks), (size_t)1);
-        PEM_LAUNCH(ctx, s1_rowclass_kernel, grid_for(span, 256), 256, A->tile_rowptr.as<int>(), p->tr_lo, p->a_lo, mt, nchunks, p->aseg.as<int2>(),
-                   p->chunk_seg.as<int2>(), p->chunk_n.as<long long>(), tiny_ok, cap4, xlcap, p->row_lbase.as<int>(), p->row_desc.as<int4>(),
-                   p->row_list.as<int>(), p->bin_count.as<int>(), p->xl_base.as<int>(), p->c_tile_rowptr.as<int>(),
-                   reinterpret_cast<long long *>(ctx->d_scalars), ctx->d_flags, p->pairs_offset.as<int>(), p->group_nnz.as<int>(), ngroups_reset,
-                   p->blk_heads.as<int>(), nblk_reset, seg_on, p->seg_list.as<int2>());
+#define PEM_ROWCLASS(NAME, THREADS, SCAN, CHAIN)                                                                                                  \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s1_rowclass_kernel<THREADS, SCAN>), grid_for(span, THREADS), THREADS, A->tile_rowptr.as<int>(), p->tr_lo, p->a_lo, mt, \
+                     nchunks, p->aseg.as<int2>(), p->chunk_seg.as<int2>(), p->chunk_n.as<long long>(), tiny_ok, cap4, xlcap, p->row_lbase.as<int>(), \
+                     p->row_desc.as<int4>(), p->row_list.as<int>(), p->bin_count.as<int>(), p->xl_base.as<int>(), p->c_tile_rowptr.as<int>(),       \
+                     reinterpret_cast<long long *>(ctx->d_scalars), ctx->d_flags, p->pairs_offset.as<int>(), p->group_nnz.as<int>(), ngroups_reset, \
+                     p->blk_heads.as<int>(), nblk_reset, seg_on, p->seg_list.as<int2>(), CHAIN)
+        // the classification scans its own row totals where its grid fits the chained scan (PEM_OPT_S1_CLASS_SCAN); above that,
+        // the scan takes a launch of its own behind it
+        if (p->opt_s1_class_scan && span <= (size_t)S1_RC_SCAN_THREADS * SCAN_MID_BLOCKS) {
+            PEM_TRY(scan_mid_state(ctx));
+            PEM_ROWCLASS("s1_rowclass_kernel<scan>", S1_RC_SCAN_THREADS, true, ctx->scan_state.as<unsigned long long>() + 2 * SCAN_MID_SET_WORDS);
+        } else {
+            PEM_ROWCLASS("s1_rowclass_kernel", 256, false, (unsigned long long *)nullptr);
+            PEM_TRY(exclusive_scan_i32(ctx, p->row_lbase.as<int>(), p->row_lbase.as<int>(), (size_t)mt, ctx->d_scalars));
+        }
+#undef PEM_ROWCLASS
     }
-    PEM_TRY(exclusive_scan_i32(ctx, p->row_lbase.as<int>(), p->row_lbase.as<int>(), (size_t)mt, ctx->d_scalars));
     // one read-back: P, the bin populations and the product total of the oversized rows
     int64_t P = 0, Pall = 0;
     int counts[5];
@@ -1778,6 +1999,9 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
         p->w_P = P;
         p->w_Pall = Pall;
     }
+    if (!p->warm_pass && one_allowed)
+        p->s1_one = nrows_xl == 0 && n_xl == 0 && nsegs < S1_NOSEG && (nsegs <= ncu_bins || p->opt_s1_one_launch == 1) ? 1 : 0;
+    const bool one_mode = p->s1_one == 1;
     p->npairs_all = Pall;
     if (P > 0x7FFFFFFFll) {
         set_error("step 1: %lld live tile pairs exceed the int32 range of the reference's pair arrays", (long long)P);
@@ -1820,8 +2044,8 @@ static pem_status step1_rows_impl(pem_ctx *ctx, pem_cplan *p)
         // four: hipGraphLaunch of a capture forked onto more streams than queues has ended in a segmentation fault inside the runtime
         // (five streams on four queues, four on two).  Fewer queues: the bins run one after another on the main stream, as under
         // PEM_OPT_S1_SERIAL -- same kernels, same results.
-        S1Lanes lanes(ctx, p->opt_s1_serial != 0 || (ctx->capturing && ctx->hw_queues < 4));
-        launch_rowsorts(ctx, p, lanes, counts, mt, bits_tc, force64, nsegs);
+        S1Lanes lanes(ctx, p->opt_s1_serial != 0 || one_mode || (ctx->capturing && ctx->hw_queues < 4));
+        launch_rowsorts(ctx, p, lanes, counts, mt, bits_tc, force64, nsegs, seg_on == 1, one_mode);
         if (xl_local) {
             lanes.on(3);
             xl_gather(1);

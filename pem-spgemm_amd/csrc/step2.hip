@@ -426,9 +426,15 @@ __global__ void __launch_bounds__(S2_GROUP) s2_entries_kernel(const uint32_t *__
 // 39 MB in, 78 MB out on webbase-1M, where s2_entries_kernel re-reads 618 MB of masks to emit 69 MB of bytes (0.18 ms
 // against 0.03).  The bytes (Ctiles_rowColIdx, spgemm.cu:582-587) are then materialised on demand like Ctiles_rowPtr
 // (ensure_c_rowcolidx).
+// FOLD (repeat passes of plans of up to S2_FOLD_GROUPS groups): group_base holds the group COUNTS as s2_tiles_kernel left them --
+// final when this kernel starts -- and every workgroup sums the counts in front of its four groups itself: at most 32 KB from L2,
+// eight 16-byte loads per thread in flight together and one block reduction, where the scan between the two kernels was a launch of
+// one workgroup (5 us, a chain of round trips on an empty chip).  The lane that writes the closing offset has C_nnz: it leaves it in
+// d_scalars[2] and runs the repeat pass's size check.  The counts stay unscanned; ensure_c_rowcolidx scans them when it needs them.
+template <bool FOLD>
 __global__ void __launch_bounds__(256) s2_offsets_kernel(const uint16_t *__restrict__ c_cnt, long long ntc, const int *__restrict__ group_base,
                                                          int *__restrict__ c_tile_nnz_ptr, int *__restrict__ chunk_tile, int *__restrict__ flags,
-                                                         WarmCheck wc, const long long *__restrict__ d_scalars, const int *__restrict__ bin_count)
+                                                         WarmCheck wc, long long *d_scalars, const int *__restrict__ bin_count)
 {
     // one WAVE per group of S2_GROUP = 256 tiles, four consecutive tiles per lane (one 8-byte load, one 16-byte store): the
     // group's base comes from the scanned group counts, so no wave waits for another (one tile per lane and a block scan
@@ -436,7 +442,27 @@ __global__ void __launch_bounds__(256) s2_offsets_kernel(const uint16_t *__restr
     static_assert(S2_GROUP == 256, "four tiles per lane of one wave");
     const int lane = threadIdx.x & 63;
     const long long g = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (wc.on && g == 0 && lane == 0) warm_check(wc, d_scalars, bin_count, flags);
+    int gbase = 0;
+    if constexpr (FOLD) {
+        __shared__ int f_wsum[4];
+        const int wave = threadIdx.x >> 6;
+        const int4 *cnt4 = reinterpret_cast<const int4 *>(group_base);
+        const int nq = (int)blockIdx.x;                         // 16-byte words in front of the workgroup's four groups
+        int s = 0;
+#pragma unroll 8
+        for (int k = threadIdx.x; k < nq; k += 256) {
+            const int4 q = cnt4[k];
+            s += q.x + q.y + q.z + q.w;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+        if (lane == 0) f_wsum[wave] = s;
+        __syncthreads();
+        gbase = f_wsum[0] + f_wsum[1] + f_wsum[2] + f_wsum[3];
+        for (int w = 0; w < wave; ++w) gbase += group_base[4 * nq + w];   // (the buffer holds four words past the last group)
+    } else {
+        if (wc.on && g == 0 && lane == 0) warm_check(wc, d_scalars, bin_count, flags);
+    }
     const long long t = g * S2_GROUP + 4 * lane;
     if (t > ntc) return;                                    // (only lanes above a live one leave: the scan below reads downwards)
     int n[4] = {0, 0, 0, 0};
@@ -458,7 +484,8 @@ __global__ void __launch_bounds__(256) s2_offsets_kernel(const uint16_t *__restr
         if (lane >= d) inc += o;
     }
     int o4[4];
-    o4[0] = group_base[g] + inc - tsum;
+    if constexpr (!FOLD) gbase = group_base[g];
+    o4[0] = gbase + inc - tsum;
     o4[1] = o4[0] + n[0];
     o4[2] = o4[1] + n[1];
     o4[3] = o4[2] + n[2];
@@ -468,6 +495,14 @@ __global__ void __launch_bounds__(256) s2_offsets_kernel(const uint16_t *__restr
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (t + k <= ntc) c_tile_nnz_ptr[t + k] = o4[k];             // (t + k == ntc: the closing offset = C_nnz)
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (t + k == ntc) {                                     // one lane of the grid
+                    d_scalars[2] = o4[k];
+                    if (wc.on) warm_check(wc, d_scalars, bin_count, flags, (long long)o4[k]);
+                }
+        }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -571,7 +606,11 @@ pem_status pem::step2_impl(pem_ctx *ctx, pem_cplan *p)
             else
                 PEM_S2_TILES("s2_tiles_kernel", false);
 #undef PEM_S2_TILES
-            PEM_TRY(exclusive_scan_i32(ctx, group_nnz, group_nnz, ngroups, ctx->d_scalars + 2));
+            // a repeat pass knows C_nnz and has its buffers in place: the offsets kernel sums the group counts itself (FOLD); a
+            // first pass needs the total on the host, to size C, before the offsets can be written
+            const bool fold = p->warm_pass && decode && p->opt_s2_tail_fold && ngroups <= (size_t)S2_FOLD_GROUPS;
+            if (!fold) PEM_TRY(exclusive_scan_i32(ctx, group_nnz, group_nnz, ngroups, ctx->d_scalars + 2));
+            p->group_nnz_scanned = !fold;
             if (p->warm_pass) {
                 nnzc = p->w_nnz;
             } else {
@@ -600,9 +639,15 @@ pem_status pem::step2_impl(pem_ctx *ctx, pem_cplan *p)
                 p->flags_mirrored = true;
             }
             if (decode) {
-                PEM_LAUNCH(ctx, s2_offsets_kernel, grid_for(((ntc + S2_GROUP) / S2_GROUP) * 64, 256), 256, p->c_tile_cnt.as<uint16_t>(), (long long)ntc,
-                           group_nnz, p->c_tile_nnz_ptr.as<int>(), p->s3_chunk_tile.as<int>(), ctx->d_flags, wc,
-                           reinterpret_cast<const long long *>(ctx->d_scalars), p->bin_count.as<int>());
+#define PEM_S2_OFFSETS(NAME, FOLD)                                                                                                     \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s2_offsets_kernel<FOLD>), grid_for(((ntc + S2_GROUP) / S2_GROUP) * 64, 256), 256, p->c_tile_cnt.as<uint16_t>(), \
+                     (long long)ntc, group_nnz, p->c_tile_nnz_ptr.as<int>(), p->s3_chunk_tile.as<int>(), ctx->d_flags, wc,              \
+                     reinterpret_cast<long long *>(ctx->d_scalars), p->bin_count.as<int>())
+                if (fold)
+                    PEM_S2_OFFSETS("s2_offsets_kernel<fold>", true);
+                else
+                    PEM_S2_OFFSETS("s2_offsets_kernel", false);
+#undef PEM_S2_OFFSETS
                 p->c_rowcolidx_valid = false;
             } else {
                 PEM_TRY(p->c_rowcolidx.reserve((size_t)nnzc + 16));
@@ -684,6 +729,10 @@ pem_status pem::ensure_c_rowcolidx(pem_ctx *ctx, const pem_cplan *cp)
     PEM_ENTER(ctx);
     PEM_TRY(p->c_rowcolidx.reserve((size_t)p->nnz_c + 16));
     if (ntc > 0) {
+        if (!p->group_nnz_scanned) {   // the pass's offsets kernel summed the counts itself and left them as they were
+            PEM_TRY(exclusive_scan_i32(ctx, p->group_nnz.as<int>(), p->group_nnz.as<int>(), (ntc + S2_GROUP - 1) / S2_GROUP, nullptr));
+            p->group_nnz_scanned = true;
+        }
         WarmCheck wc = {};
         PEM_LAUNCH(ctx, s2_entries_kernel, (unsigned)((ntc + S2_GROUP) / S2_GROUP), S2_GROUP, p->c_mask.as<uint32_t>(), (long long)ntc,
                    p->group_nnz.as<int>(), (long long)p->nnz_c, p->c_tile_nnz_ptr.as<int>(), p->c_rowcolidx.as<uint8_t>(), p->s3_chunk_tile.as<int>(),
