@@ -334,6 +334,44 @@ typedef enum {
 pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out);
 pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
 
+/* Extract and transpose (GraphBLAS GrB_extract / GrB_transpose): the operations that re-index a tiling, on
+ * the device.  None is typed: values are only copied, so one entry point serves fp64 and fp32 tilings, as pem_tiled_select does.
+ *   pem_tiled_extract  a new tiling R = A(I, J) of ni x nj and A's value type, owning its arrays: R stores (p, q) exactly where A
+ *       stores (I[p], J[q]), with that value copied bit for bit (explicit zeros stay; NaN payloads, -0.0, infinities and subnormals
+ *       arrive unchanged).  I and J are host arrays; they may be in any order and may repeat indices (scipy's A[I][:, J]).
+ *       I == NULL means all rows in order: ni is then ignored and R has A.rows rows.  J likewise.  A submatrix, a row or column
+ *       sample, a symmetric permutation P*A*P^T (I = J = p) are all this call.
+ *     Coordinates are those of the matrix the tiling represents (the matrix pem_tiled_export_csr returns): a tiling built with
+ *       transpose = 1 is its own matrix.
+ *     R equals the tiling pem_tiled_from_csr builds from the extracted matrix (every pem_tiled_info field but the two timings, every
+ *       pem_tiled_array).  Tiles left without entries are not in R; if nothing is stored, R is a valid tiling with nnz = 0.  R works
+ *       everywhere a tiling does (A, B, mask, save / load, set_values*, flop count, split, ewise, select, mxv, spmm, sddmm, export,
+ *       extract, transpose).
+ *     Refusals, all checked before anything is returned (*out stays NULL).  PEM_E_INVALID: a null context, tiling or out; a non-null
+ *       list with n < 1 or n > INT32_MAX; an index < 0 or >= the dimension.  PEM_E_OVERFLOW: the result's entries or tiles exceed
+ *       the int32 index range (repeated indices multiply entries); it is found by the counting pass, before the result is allocated.
+ *     A's values are read as they are when the call is made (stream order); the call waits, and its allocations come from the
+ *       context's arena (a captured graph re-captures once).  Besides the tiling's own arrays R keeps device copies of I and J for
+ *       the refresh: 4 * (ni + nj) bytes (nothing for a null list).
+ *   pem_tiled_extract_device  the same with dI, dJ in device memory on the context's device, read in stream order (they may be
+ *       changed or freed once the call returns).  The indices are checked by the call's first kernel; a bad index is never used as
+ *       an address.
+ *   pem_tiled_set_values_from_extract  rewrites t's vals and vals_t in place from A's current values and bumps t's value version (the
+ *       pattern of an extract does not depend on A's values, so every extract is refreshable).  Stream-ordered, never waits, reads
+ *       nothing back; only the first call allocates (an int32 per entry: the slot of its value in A's vals).  PEM_E_INVALID unless t
+ *       was made by pem_tiled_extract / pem_tiled_extract_device from exactly this A (the serial rule of
+ *       pem_tiled_set_values_from_ewise).
+ *   pem_tiled_transpose  a new tiling R = A^T of A.cols x A.rows, owning its arrays: array for array the tiling
+ *       pem_tiled_from_coo(.., transpose = 1) builds from A's exported entries.  Any tiling works as A (converted, loaded, from_cplan,
+ *       ewise, select, sddmm, extract).  PEM_E_INVALID: a null argument.  Waits; arena allocations, as above.
+ *   pem_tiled_set_values_from_transpose  as pem_tiled_set_values_from_extract, for a t made by pem_tiled_transpose from exactly this A. */
+pem_status pem_tiled_transpose(pem_ctx *ctx, const pem_tiled *A, pem_tiled **out);
+pem_status pem_tiled_set_values_from_transpose(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
+pem_status pem_tiled_extract(pem_ctx *ctx, const pem_tiled *A, const int32_t *I, int64_t ni, const int32_t *J, int64_t nj, pem_tiled **out);
+pem_status pem_tiled_extract_device(pem_ctx *ctx, const pem_tiled *A, const int32_t *dI, int64_t ni, const int32_t *dJ, int64_t nj,
+                                    pem_tiled **out);
+pem_status pem_tiled_set_values_from_extract(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
+
 /* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
  * the fold of every row or column, on the device.
  *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)

@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "pem_tiled_export_csr", "pem_tiled_export_csr_f32", "pem_tiled_select", "pem_tiled_set_values_from_select",
     "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32", "pem_tiled_spmm", "pem_tiled_spmm_f32",
     "pem_tiled_set_values_sddmm", "pem_tiled_set_values_sddmm_f32", "pem_tiled_sddmm", "pem_tiled_sddmm_f32",
+    "pem_tiled_transpose", "pem_tiled_set_values_from_transpose", "pem_tiled_extract", "pem_tiled_extract_device",
+    "pem_tiled_set_values_from_extract",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -343,6 +345,73 @@ class Tiled:
         """Refresh a tiling made by A.select(op, k) with a positional op from A's current values, in place.  Ordered on the context's
         stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
+
+    def _index_list(self, name, L, dim):
+        """one argument of extract -> (kind, list, n): kind None (all), "host" (a C-contiguous int32 array) or "device" (a torch
+        int32 tensor on the context's device)"""
+        if L is None:
+            return None, None, 0
+        if isinstance(L, slice):
+            L = np.arange(*L.indices(dim), dtype=np.int32)
+        if hasattr(L, "data_ptr"):
+            if L.is_cuda:
+                dev = L.device.index if L.device.index is not None else 0
+                if str(L.dtype) != "torch.int32" or L.dim() != 1 or not L.is_contiguous() or dev != self.ctx.device:
+                    raise ValueError(f"extract: want a contiguous 1-d int32 tensor on device {self.ctx.device} for {name}, "
+                                     f"got {L.dtype} {tuple(L.shape)} on {L.device}")
+                return "device", L, L.numel()
+            L = L.numpy()
+        a = np.asarray(L)
+        if a.ndim != 1:
+            raise ValueError(f"extract: {name} must be one-dimensional, not {a.shape}")
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"extract: {name} must hold integers, not {a.dtype}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= dim):
+            raise ValueError(f"extract: {name} holds an index outside 0 .. {dim - 1} (negative indices are not wrapped)")
+        return "host", np.ascontiguousarray(a, dtype=np.int32), a.size
+
+    def extract(self, rows=None, cols=None):
+        """Extract: R = A(rows, cols) as a new tiling of this one's dtype; R stores (p, q) where this
+        tiling stores (rows[p], cols[q]), values copied bit for bit.  Each argument: None (all, in order), a slice, a host integer
+        array-like (checked; negative indices are refused, not wrapped) or a torch int32 tensor on the context's device.  Lists may be
+        in any order and may repeat indices (scipy's A[rows][:, cols]).  Waits."""
+        kr, I, ni = self._index_list("rows", rows, self.rows)
+        kc, J, nj = self._index_list("cols", cols, self.cols)
+        device = "device" in (kr, kc)
+        if device:   # one device and one host list: upload the host one
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            if kr == "host":
+                I = torch.from_numpy(I).to(dev)
+            if kc == "host":
+                J = torch.from_numpy(J).to(dev)
+            torch.cuda.current_stream(dev).synchronize()   # (the lists are read on the context's stream)
+            # (an empty tensor has a null pointer, which would mean "all": any non-null one lets the library refuse n = 0)
+            pI, pJ = (None if x is None else C.c_void_p(x.data_ptr() or 1) for x in (I, J))
+            fn = lib().pem_tiled_extract_device
+        else:
+            pI, pJ = (None if x is None else _p(x, C.c_int32) for x in (I, J))
+            fn = lib().pem_tiled_extract
+        h = C.c_void_p()
+        _check(fn(self.ctx._h, self._h, pI, C.c_int64(ni), pJ, C.c_int64(nj), C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_extract(self, A):
+        """Refresh a tiling made by A.extract(rows, cols) from A's current values, in place.  Ordered on the context's stream; returns
+        without waiting."""
+        _check(lib().pem_tiled_set_values_from_extract(self.ctx._h, self._h, A._h))
+
+    def transpose(self):
+        """Transpose: this tiling's matrix transposed, as a new tiling built on the device -- the arrays
+        of from_coo(.., transpose=True) of the exported entries.  Waits."""
+        h = C.c_void_p()
+        _check(lib().pem_tiled_transpose(self.ctx._h, self._h, C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_transpose(self, A):
+        """Refresh a tiling made by A.transpose() from A's current values, in place.  Ordered on the context's stream; returns without
+        waiting."""
+        _check(lib().pem_tiled_set_values_from_transpose(self.ctx._h, self._h, A._h))
 
     def _vector(self, fn, name, v, n):
         """the device pointer of a torch tensor of n values of this tiling's dtype (the check of set_values_device)"""

@@ -197,7 +197,7 @@ static pem_status c_tiling(pem_ctx *ctx, const pem_cplan *p, pem_tiled *T)
 
 // C^T from C's tiling Tc
 template <typename VT>
-static pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled *T)
+static pem_status transposed_tiling_t(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled *T)
 {
     const size_t nt = (size_t)Tc->ntiles;
     set_tiled_shape(T, Tc->value_bytes, Tc->cols, Tc->rows);
@@ -223,6 +223,11 @@ static pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled
     return check_internal(hf);
 }
 
+pem_status pem::transposed_tiling(pem_ctx *ctx, const pem_tiled *Tc, pem_tiled *T)
+{
+    return Tc->value_bytes == 4 ? transposed_tiling_t<float>(ctx, Tc, T) : transposed_tiling_t<double>(ctx, Tc, T);
+}
+
 // C's tiling into T, or C^T's from a C tiling of its own (freed once C^T is built)
 static pem_status cplan_build(pem_ctx *ctx, const pem_cplan *plan, int transpose, pem_tiled *T)
 {
@@ -232,7 +237,7 @@ static pem_status cplan_build(pem_ctx *ctx, const pem_cplan *plan, int transpose
     if (!transpose) return c_tiling(ctx, plan, T);
     std::unique_ptr<pem_tiled> Tc(new pem_tiled());
     pem_status s = c_tiling(ctx, plan, Tc.get());
-    if (s == PEM_OK) s = Tc->value_bytes == 4 ? transposed_tiling<float>(ctx, Tc.get(), T) : transposed_tiling<double>(ctx, Tc.get(), T);
+    if (s == PEM_OK) s = transposed_tiling(ctx, Tc.get(), T);
     (void)hipStreamSynchronize(ctx->stream);   // (C's tiling goes back to the arena)
     return s;
 }
@@ -254,7 +259,7 @@ extern "C" pem_status pem_tiled_from_cplan(pem_ctx *ctx, const pem_cplan *plan, 
 }
 
 // the map of a C^T tiling on its first refresh: counts in CSC order, scan, fill.  Stream-ordered, no read-back.
-static pem_status build_cmap(pem_ctx *ctx, pem_tiled *T)
+pem_status pem::build_transpose_map(pem_ctx *ctx, pem_tiled *T)
 {
     const size_t nnz = (size_t)T->nnz, nt = (size_t)T->ntiles;
     DevBuf &cmap = T->derived.map, cbase;
@@ -289,6 +294,6 @@ extern "C" pem_status pem_tiled_set_values_from_cplan(pem_ctx *ctx, pem_tiled *t
     }
     const bool tr = t->derived.op != 0;   // C^T: through the map; C: c_vals as it is
     return refresh_derived(
-        ctx, t, [&] { return tr ? build_cmap(ctx, t) : PEM_OK; },
+        ctx, t, [&] { return tr ? build_transpose_map(ctx, t) : PEM_OK; },
         [&] { refresh_gather(ctx, t, plan->c_vals.p, tr ? t->derived.map.as<int>() : nullptr); });
 }

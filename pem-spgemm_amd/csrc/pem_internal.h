@@ -298,13 +298,17 @@ uint64_t next_tiled_serial();
 //                                              operand slots in A's and B's vals (-1: none).
 //   SELECT  pem_tiled_select (select.hip)      src[0] = A's serial; op; p0 = thunk.  src_tiles: int[T], A's tile feeding every tile.
 //                                              map: int32[nnz + 4], every entry's value slot in A's vals.
+//   TRANSPOSE pem_tiled_transpose (extract.hip) src[0] = A's serial.  map: int32[nnz + 4], every entry's value slot in A's vals (the
+//                                              map of a C^T tiling, chain.hip).
+//   EXTRACT pem_tiled_extract (extract.hip)    src[0] = A's serial.  idx[0], idx[1]: device copies of I and J (int32[ni], int32[nj];
+//                                              unallocated where the list was null = all).  map: as SELECT's.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;
-    DevBuf src_tiles, map;
+    DevBuf src_tiles, map, idx[2];
     bool map_ready = false;
 };
 

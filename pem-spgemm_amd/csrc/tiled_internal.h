@@ -1,5 +1,5 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip).  A derived tiling (chain.hip, ewise.hip, select.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, extract.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.
 #pragma once
@@ -31,6 +31,12 @@ pem_status ensure_vmap_t(pem_ctx *ctx, pem_tiled *T);
 // vals[e] = vals_t[vmap_t[e]] = src[map[e]], or src[e] where map is null (values.hip).  src holds T's value type; map is
 // 16-byte aligned with at least nnz + 4 ints.  vmap_t must be ready.
 void refresh_gather(pem_ctx *ctx, pem_tiled *T, const void *src, const int *map);
+// the tiling T of S^T from a complete tiling S, by S's column-side arrays (tile CSC, tile_rec_t, vals_t): no entry-level sort
+// (chain.hip; pem_tiled_from_cplan(.., 1), pem_tiled_transpose and the column side of pem_tiled_extract).  The caller has zeroed
+// the flags and sets T's provenance.  Synchronises.
+pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *S, pem_tiled *T);
+// T->derived.map of such a T: every entry's slot in S's vals (int32[nnz + 4]).  Stream-ordered, no read-back (chain.hip).
+pem_status build_transpose_map(pem_ctx *ctx, pem_tiled *T);
 
 // The shell of pem_tiled_from_cplan, pem_tiled_ewise and pem_tiled_select (their arguments checked, *out cleared): build(T) into
 // a fresh tiling, the time into conv_ms, synchronised; the tiling goes to *out on success and is freed otherwise.

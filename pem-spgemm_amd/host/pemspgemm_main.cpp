@@ -367,6 +367,58 @@ static std::string read_dense_array(const char *path, int64_t *rows, int64_t *k,
     return err;
 }
 
+// An index list of --extract-rows / --extract-cols: a Matrix-Market `array` file of one column, `integer` or `real` with integral
+// values, holding 1-based indices like a coordinate file; idx receives them 0-based.  "" or what is wrong with the file.
+static std::string read_index_array(const char *path, std::vector<int32_t> *idx)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return "cannot open the file";
+    char line[4096];
+    std::string err;
+    if (!fgets(line, sizeof line, f)) err = "empty file";
+    char banner[64] = "", object[64] = "", format[64] = "", field[64] = "", symmetry[64] = "";
+    if (err.empty() && sscanf(line, "%63s %63s %63s %63s %63s", banner, object, format, field, symmetry) != 5) err = "no Matrix-Market header";
+    auto lower = [](char *t) { for (; *t; ++t) *t = (char)tolower((unsigned char)*t); };
+    lower(banner), lower(object), lower(format), lower(field), lower(symmetry);
+    if (err.empty() && (strcmp(banner, "%%matrixmarket") || strcmp(object, "matrix"))) err = "no Matrix-Market header";
+    if (err.empty() && strcmp(format, "array")) err = std::string("a ") + format + " file, not an array (dense) file";
+    if (err.empty() && strcmp(field, "integer") && strcmp(field, "real")) err = std::string("a ") + field + " file, not an integer or real one";
+    if (err.empty() && strcmp(symmetry, "general")) err = std::string("a ") + symmetry + " array, not a general one";
+    long long m = -1, n = -1;
+    while (err.empty()) {
+        if (!fgets(line, sizeof line, f)) {
+            err = "no size line";
+            break;
+        }
+        if (line[0] == '%') continue;
+        if (sscanf(line, "%lld %lld", &m, &n) != 2 || m < 0 || n < 0) err = "bad size line";
+        break;
+    }
+    if (err.empty() && n != 1) err = "an array of " + std::to_string(n) + " columns, not of one";
+    if (err.empty() && (m < 1 || m > 2147483647ll)) err = "a list of " + std::to_string(m) + " indices, not of 1 .. 2^31 - 1";
+    if (err.empty()) {
+        idx->assign((size_t)m, 0);
+        for (long long j = 0; j < m; ++j) {
+            double v;
+            if (fscanf(f, "%lf", &v) != 1) {
+                err = "fewer values than the size line says";
+                break;
+            }
+            if (!(std::floor(v) == v)) {
+                err = "index " + std::to_string(j + 1) + " is not an integer";
+                break;
+            }
+            if (!(v >= 1.0 && v <= 2147483647.0)) {
+                err = "index " + std::to_string(j + 1) + " is out of range (indices are 1-based)";
+                break;
+            }
+            (*idx)[(size_t)j] = (int32_t)((long long)v - 1);
+        }
+    }
+    fclose(f);
+    return err;
+}
+
 int main(int argc, char *argv[])
 {
     // Beyond the reference: `--B <file.mtx>` multiplies by a second matrix instead of A itself,
@@ -390,6 +442,10 @@ int main(int argc, char *argv[])
     // OP, one of tril triu diag offdiag row_le row_gt col_le col_gt (THUNK an integer k) or value_eq value_ne value_lt value_le
     // value_gt value_ge abs_gt (THUNK a value); THUNK defaults to 0.  The result becomes a tiling (pem_tiled_from_cplan, or the
     // ewise sum) and is filtered on the device (pem_tiled_select); --out then writes what is kept.  The CSV row describes the product.
+    // `--extract-rows I.mtx` / `--extract-cols J.mtx`, either or both: the final result R (C, the sum of
+    // --add, or what --select kept) becomes R(I, J) on the device (pem_tiled_extract).  Each file is a Matrix-Market `array` file of
+    // one column holding 1-based indices (`integer`, or `real` with integral values), in any order, repeats allowed.  --reduce,
+    // --spmm, --sddmm and --out then see the extracted tiling.  The CSV row describes the product.
     // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
     // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
     // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
@@ -409,6 +465,7 @@ int main(int argc, char *argv[])
     const char *add_path = nullptr;   // --add D.mtx: C = alpha*(A*B) (+) beta*D
     double add_alpha = 1.0, add_beta = 1.0;
     const char *select_spec = nullptr;   // --select OP[:THUNK]
+    const char *extract_paths[2] = {nullptr, nullptr};   // --extract-rows I.mtx, --extract-cols J.mtx
     const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
     const char *spmm_path = nullptr;     // --spmm X.mtx
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;   // --sddmm X.mtx [--sddmm-y Y.mtx]
@@ -435,6 +492,8 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--alpha") && r + 1 < argc) add_alpha = atof(argv[++r]);
             else if (!strcmp(argv[r], "--beta") && r + 1 < argc) add_beta = atof(argv[++r]);
             else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
+            else if (!strcmp(argv[r], "--extract-rows") && r + 1 < argc) extract_paths[0] = argv[++r];
+            else if (!strcmp(argv[r], "--extract-cols") && r + 1 < argc) extract_paths[1] = argv[++r];
             else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
             else if (!strcmp(argv[r], "--spmm") && r + 1 < argc) spmm_path = argv[++r];
             else if (!strcmp(argv[r], "--sddmm") && r + 1 < argc) sddmm_path = argv[++r];
@@ -538,6 +597,23 @@ int main(int argc, char *argv[])
         }
         if (select_op <= PEM_SELECT_COL_GT && !(std::floor(select_thunk) == select_thunk && std::fabs(select_thunk) <= 2147483648.0)) {
             printf("--select %s: the positional op %s needs an integral thunk k with |k| <= 2^31. Exiting.\n", select_spec, name.c_str());
+            return 1;
+        }
+    }
+    // --extract-rows / --extract-cols: the lists read up front, so that a bad file is refused before any work
+    static const char *const extract_flags[2] = {"--extract-rows", "--extract-cols"};
+    std::vector<int32_t> extract_idx[2];
+    for (int q = 0; q < 2; ++q) {
+        if (!extract_paths[q]) continue;
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : nullptr;
+        if (clash) {
+            printf("%s does not combine with %s. Exiting.\n", extract_flags[q], clash);
+            return 1;
+        }
+        const std::string err = read_index_array(extract_paths[q], &extract_idx[q]);
+        if (!err.empty()) {
+            printf("%s %s: %s (want a Matrix-Market array file of one column of 1-based indices). Exiting.\n", extract_flags[q], extract_paths[q],
+                   err.c_str());
             return 1;
         }
     }
@@ -984,10 +1060,41 @@ int main(int argc, char *argv[])
                Sum ? "the sum" : "C", si.conv_ms, sel_total_ms, (long long)si.nnz, (long long)src.nnz);
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
+    pem_tiled *Ext = nullptr;   // --extract-rows / --extract-cols: R(I, J) of C, of the sum or of the selection
+    if (extract_paths[0] || extract_paths[1]) {
+        auto x0 = std::chrono::high_resolution_clock::now();
+        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info xi, src;
+        CHECK(pem_tiled_get_info(Src, &src));
+        const int dims[2] = {src.rows, src.cols};
+        for (int q = 0; q < 2; ++q)
+            for (size_t j = 0; j < extract_idx[q].size(); ++j)
+                if (extract_idx[q][j] >= dims[q]) {
+                    printf("%s %s: index %zu is %d; the result has %d %s. Exiting.\n", extract_flags[q], extract_paths[q], j + 1,
+                           extract_idx[q][j] + 1, dims[q], q ? "columns" : "rows");
+                    if (Ct) pem_tiled_destroy(ctx, Ct);
+                    return 1;
+                }
+        CHECK(pem_tiled_extract(ctx, Src, extract_paths[0] ? extract_idx[0].data() : nullptr, (int64_t)extract_idx[0].size(),
+                                extract_paths[1] ? extract_idx[1].data() : nullptr, (int64_t)extract_idx[1].size(), &Ext));
+        const double ext_total_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - x0).count();
+        CHECK(pem_tiled_get_info(Ext, &xi));
+        printf("extract: %s x %s of %s: extract %.2fms, total %.2fms, %d x %d, nnz %lld from %lld\n",
+               extract_paths[0] ? std::to_string(extract_idx[0].size()).append(" rows").c_str() : "all rows",
+               extract_paths[1] ? std::to_string(extract_idx[1].size()).append(" columns").c_str() : "all columns",
+               Sel ? "the selection" : Sum ? "the sum" : "C", xi.conv_ms, ext_total_ms, xi.rows, xi.cols, (long long)xi.nnz, (long long)src.nnz);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+    pem_tiled *const Last = Ext ? Ext : Sel ? Sel : Sum;   // the final result when it is a tiling, and what the lines below call it
+    const char *const last_name = Ext ? "the extract" : Sel ? "the selection" : Sum ? "the sum" : "C";
 
     std::vector<double> red;   // --reduce: the vector, on the host
     if (reduce_dim >= 0) {
-        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        pem_tiled *Src = Last, *Ct = nullptr;
         if (!Src) {
             CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
             Src = Ct;
@@ -1018,14 +1125,14 @@ int main(int argc, char *argv[])
         double sum = 0.0;
         for (double v : red) sum += v;
         printf("reduce: %s %s of %s: reduce %.3fms, %zu values, host sum %.17g\n", reduce_dim == PEM_REDUCE_COLS ? "cols" : "rows",
-               add_op_names[reduce_op], Sel ? "the selection" : Sum ? "the sum" : "C", red_ms, n, sum);
+               add_op_names[reduce_op], last_name, red_ms, n, sum);
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
 
     std::vector<double> spmm_y;   // --spmm: Y, row-major, on the host
     int64_t spmm_ny = 0;
     if (spmm_path) {
-        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        pem_tiled *Src = Last, *Ct = nullptr;
         if (!Src) {
             CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
             Src = Ct;
@@ -1069,7 +1176,7 @@ int main(int argc, char *argv[])
         (void)hipFree(dy);
         double sum = 0.0;
         for (double v : spmm_y) sum += v;
-        printf("spmm: Y = %s (%s) X: spmm %.3fms, k %lld, %lld x %lld values, host sum %.17g\n", Sel ? "the selection" : Sum ? "the sum" : "C",
+        printf("spmm: Y = %s (%s) X: spmm %.3fms, k %lld, %lld x %lld values, host sum %.17g\n", last_name,
                semiring_names[semiring], spmm_ms, (long long)k, (long long)spmm_ny, (long long)k, sum);
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
@@ -1079,7 +1186,7 @@ int main(int argc, char *argv[])
     std::vector<int32_t> sd_rp, sd_ci;
     std::vector<double> sd_v;
     if (sddmm_path) {
-        pem_tiled *Src = Sel ? Sel : Sum, *Ct = nullptr;
+        pem_tiled *Src = Last, *Ct = nullptr;
         if (!Src) {
             CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
             Src = Ct;
@@ -1136,7 +1243,7 @@ int main(int argc, char *argv[])
         }
         double sum = 0.0;
         for (double v : sd_v) sum += v;
-        printf("sddmm: R = pattern(%s) o (X %s^T) (%s): sddmm %.3fms, k %lld, nnz %lld, host sum %.17g\n", Sel ? "the selection" : Sum ? "the sum" : "C",
+        printf("sddmm: R = pattern(%s) o (X %s^T) (%s): sddmm %.3fms, k %lld, nnz %lld, host sum %.17g\n", last_name,
                sddmm_y_path ? "Y" : "X", semiring_names[semiring], sd_ms, (long long)k, (long long)si.nnz, sum);
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
@@ -1175,7 +1282,11 @@ int main(int argc, char *argv[])
             rc = 2;
         }
     }
-    pem_tiled *Res = Sel ? Sel : Sum;   // the final result when it is a tiling
+    pem_tiled *Res = Last;   // the final result when it is a tiling
+    const std::string extract_note = !Ext ? std::string()
+                                          : std::string(", extract ") + (extract_paths[0] ? std::string("rows ") + extract_paths[0] : std::string()) +
+                                                (extract_paths[0] && extract_paths[1] ? ", " : "") +
+                                                (extract_paths[1] ? std::string("columns ") + extract_paths[1] : std::string());
     if (out_path && spmm_path) {   // Y as a Matrix-Market dense array (R.rows x k, values column by column)
         FILE *f = fopen(out_path, "w");
         bool ok = f != nullptr;
@@ -1213,6 +1324,7 @@ int main(int argc, char *argv[])
         CHECK(pem_tiled_get_info(Sd, &si));
         std::string comment = std::string("R = pattern(C) o (X Y^T) (") + semiring_names[semiring] + ")";
         if (Sel) comment += std::string(", C after select ") + select_spec;
+        comment += extract_note;
         comment += " by pemspgemm (pem-spgemm_amd)";
         if (pem_write_mtx_csr(out_path, si.rows, si.cols, sd_rp.data(), sd_ci.data(), sd_v.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
@@ -1235,6 +1347,7 @@ int main(int argc, char *argv[])
         }
         std::string comment = Sum ? std::string("C = alpha*A*B + beta*D (") + semiring_names[semiring] + ")" : std::string("C = A*B (") + semiring_names[semiring] + ")";
         if (Sel) comment += std::string(", select ") + select_spec;
+        comment += extract_note;
         comment += " by pemspgemm (pem-spgemm_amd)";
         if (pem_write_mtx_csr(out_path, si.rows, si.cols, rp.data(), cidx.data(), cv.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
@@ -1268,6 +1381,7 @@ int main(int argc, char *argv[])
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
     if (Sd) pem_tiled_destroy(ctx, Sd);
+    if (Ext) pem_tiled_destroy(ctx, Ext);
     if (Sel) pem_tiled_destroy(ctx, Sel);
     if (Sum) pem_tiled_destroy(ctx, Sum);
     if (Dt) pem_tiled_destroy(ctx, Dt);
