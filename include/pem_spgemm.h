@@ -372,6 +372,47 @@ pem_status pem_tiled_extract_device(pem_ctx *ctx, const pem_tiled *A, const int3
                                     pem_tiled **out);
 pem_status pem_tiled_set_values_from_extract(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
 
+/* Assign (GraphBLAS GrB_assign with no mask and no replace): writing a submatrix back, on the device -- the
+ * dual of pem_tiled_extract.  None is typed: values are copied or combined in the tiling's own type, so one entry point serves fp64
+ * and fp32 tilings.
+ *   pem_tiled_assign  a new tiling Z of C's shape and value type, owning its arrays: C with Z(I, J) = A (accum = PEM_ACCUM_NONE) or
+ *       Z(I, J) = op(C(I, J), A) (accum = a pem_binop).  C and A are not changed.  I holds ni row indices of C and J nj column indices
+ *       of C, host arrays in any order that must not repeat an index (GraphBLAS leaves repeats undefined; they are refused here).
+ *       I == NULL means all rows in order: ni is then ignored.  J likewise.  A is ni x nj (with a null I, A.rows == C.rows; J alike).
+ *       C and A may be the same handle where the shapes allow it.
+ *     Coordinates are those of the matrix the tiling represents (the matrix pem_tiled_export_csr returns).
+ *     Outside I x J, Z stores what C stores, bit for bit.
+ *     Inside, without an accum: Z stores (I[p], J[q]) exactly where A stores (p, q), with A's value bit for bit; C's entries in the
+ *       region that A does not store are deleted, so assigning an empty ni x nj tiling clears the region.
+ *     Inside, with an accum: Z stores the entry where C or A stores it; where both do, the value is op(c, a) under pem_tiled_ewise's
+ *       arithmetic with alpha = beta = 1 (one rounding in the value type, fmin / fmax NaN rules, LOR / LAND giving 1.0 / 0.0); where
+ *       only one does, that one's value unchanged.
+ *     Explicit zeros and results that come out as 0 stay entries.  Tiles left without entries are not in Z; if nothing is stored, Z is
+ *       a valid tiling with nnz = 0.  Z equals the tiling pem_tiled_from_coo builds from the assigned matrix (every pem_tiled_info field
+ *       but the two timings, every pem_tiled_array) and works everywhere a tiling does (A, B, mask, save / load, set_values*, ewise,
+ *       select, extract, transpose, mxv, spmm, sddmm, export, assign).
+ *     Refusals, all checked before anything is returned (*out stays NULL, no handle changes).  PEM_E_INVALID: a null context, C, A or
+ *       out; an unknown accum; different value types; a non-null list with n < 1 or n > INT32_MAX; an index < 0 or >= C's dimension;
+ *       a repeated index; A's shape not ni x nj.  PEM_E_OVERFLOW: Z's entries or tiles exceed the int32 index range (with an accum
+ *       only); it is found by a counting pass, before Z's payload is allocated.
+ *     C's and A's values are read as they are when the call is made (stream order); the call waits, and its allocations come from the
+ *       context's arena (a captured graph re-captures once); every intermediate is back in the arena when it returns.  Besides the
+ *       tiling's own arrays Z keeps the inverses of the lists for the refresh: 4 * (C.rows + C.cols) bytes (nothing for a null list).
+ *   pem_tiled_assign_device  the same with dI, dJ in device memory on the context's device, read in stream order (they may be changed
+ *       or freed once the call returns).  Range and repeats are checked by the call's first kernel; a bad index is never used as an
+ *       address.
+ *   pem_tiled_set_values_from_assign  rewrites t's vals and vals_t in place from the current values of C and A, recomputing op(c, a)
+ *       where both feed an entry, and bumps t's value version (the pattern of an assign does not depend on any value, so every assign
+ *       is refreshable).  Stream-ordered, never waits, reads nothing back; only the first call allocates (an int32 pair per entry:
+ *       its slots in C's and A's vals, -1 for none).  PEM_E_INVALID unless t was made by pem_tiled_assign / pem_tiled_assign_device
+ *       from exactly this C and this A in this order (the serial rule of pem_tiled_set_values_from_ewise). */
+enum { PEM_ACCUM_NONE = -1 };   /* otherwise a pem_binop */
+pem_status pem_tiled_assign(pem_ctx *ctx, const pem_tiled *C, const pem_tiled *A, const int32_t *I, int64_t ni, const int32_t *J, int64_t nj,
+                            int accum, pem_tiled **out);
+pem_status pem_tiled_assign_device(pem_ctx *ctx, const pem_tiled *C, const pem_tiled *A, const int32_t *dI, int64_t ni, const int32_t *dJ,
+                                   int64_t nj, int accum, pem_tiled **out);
+pem_status pem_tiled_set_values_from_assign(pem_ctx *ctx, pem_tiled *t, const pem_tiled *C, const pem_tiled *A);
+
 /* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
  * the fold of every row or column, on the device.
  *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)

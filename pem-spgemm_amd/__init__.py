@@ -53,12 +53,13 @@ ABI_SYMBOLS = [
     "pem_tiled_mxv", "pem_tiled_mxv_f32", "pem_tiled_reduce", "pem_tiled_reduce_f32", "pem_tiled_spmm", "pem_tiled_spmm_f32",
     "pem_tiled_set_values_sddmm", "pem_tiled_set_values_sddmm_f32", "pem_tiled_sddmm", "pem_tiled_sddmm_f32",
     "pem_tiled_transpose", "pem_tiled_set_values_from_transpose", "pem_tiled_extract", "pem_tiled_extract_device",
-    "pem_tiled_set_values_from_extract",
+    "pem_tiled_set_values_from_extract", "pem_tiled_assign", "pem_tiled_assign_device", "pem_tiled_set_values_from_assign",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
 EWISE_PATTERNS = dict(union=0, intersect=1)
 BINOPS = dict(plus=0, times=1, min=2, max=3, lor=4, land=5)
+ACCUM_NONE = -1   # PEM_ACCUM_NONE: Tiled.assign without an accum
 
 # enum pem_select_op (include/pem_spgemm.h): Tiled.select's ops, by value; the first eight are positional
 SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
@@ -346,8 +347,8 @@ class Tiled:
         stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
 
-    def _index_list(self, name, L, dim):
-        """one argument of extract -> (kind, list, n): kind None (all), "host" (a C-contiguous int32 array) or "device" (a torch
+    def _index_list(self, name, L, dim, what="extract"):
+        """one argument of extract or assign -> (kind, list, n): kind None (all), "host" (a C-contiguous int32 array) or "device" (a torch
         int32 tensor on the context's device)"""
         if L is None:
             return None, None, 0
@@ -357,17 +358,17 @@ class Tiled:
             if L.is_cuda:
                 dev = L.device.index if L.device.index is not None else 0
                 if str(L.dtype) != "torch.int32" or L.dim() != 1 or not L.is_contiguous() or dev != self.ctx.device:
-                    raise ValueError(f"extract: want a contiguous 1-d int32 tensor on device {self.ctx.device} for {name}, "
+                    raise ValueError(f"{what}: want a contiguous 1-d int32 tensor on device {self.ctx.device} for {name}, "
                                      f"got {L.dtype} {tuple(L.shape)} on {L.device}")
                 return "device", L, L.numel()
             L = L.numpy()
         a = np.asarray(L)
         if a.ndim != 1:
-            raise ValueError(f"extract: {name} must be one-dimensional, not {a.shape}")
+            raise ValueError(f"{what}: {name} must be one-dimensional, not {a.shape}")
         if a.size and a.dtype.kind not in "iu":
-            raise ValueError(f"extract: {name} must hold integers, not {a.dtype}")
+            raise ValueError(f"{what}: {name} must hold integers, not {a.dtype}")
         if a.size and (int(a.min()) < 0 or int(a.max()) >= dim):
-            raise ValueError(f"extract: {name} holds an index outside 0 .. {dim - 1} (negative indices are not wrapped)")
+            raise ValueError(f"{what}: {name} holds an index outside 0 .. {dim - 1} (negative indices are not wrapped)")
         return "host", np.ascontiguousarray(a, dtype=np.int32), a.size
 
     def extract(self, rows=None, cols=None):
@@ -400,6 +401,41 @@ class Tiled:
         """Refresh a tiling made by A.extract(rows, cols) from A's current values, in place.  Ordered on the context's stream; returns
         without waiting."""
         _check(lib().pem_tiled_set_values_from_extract(self.ctx._h, self._h, A._h))
+
+    def assign(self, A, rows=None, cols=None, accum=None):
+        """Assign: Z = this tiling (C) with Z(rows, cols) = A, or with accum (one of BINOPS)
+        Z(rows, cols) = accum(C(rows, cols), A), as a new tiling of C's shape and dtype; C and A are not changed.  Without an accum C's
+        entries in the region that A does not store are deleted.  rows, cols: as for extract -- None (all, in order), a slice, a host
+        integer array-like (checked: a negative index or a repeat raises ValueError) or a torch int32 tensor on the context's device
+        (checked by the library).  A is len(rows) x len(cols).  Waits."""
+        if accum is not None and accum not in BINOPS:
+            raise ValueError(f"unknown accum {accum!r}; None or one of {sorted(BINOPS)}")
+        kr, I, ni = self._index_list("rows", rows, self.rows, "assign")
+        kc, J, nj = self._index_list("cols", cols, self.cols, "assign")
+        for k, L, name in ((kr, I, "rows"), (kc, J, "cols")):
+            if k == "host" and len(np.unique(L)) != len(L):
+                raise ValueError(f"assign: {name} repeats an index")
+        if "device" in (kr, kc):   # one device and one host list: upload the host one
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            if kr == "host":
+                I = torch.from_numpy(I).to(dev)
+            if kc == "host":
+                J = torch.from_numpy(J).to(dev)
+            torch.cuda.current_stream(dev).synchronize()   # (the lists are read on the context's stream)
+            pI, pJ = (None if x is None else C.c_void_p(x.data_ptr() or 1) for x in (I, J))
+            fn = lib().pem_tiled_assign_device
+        else:
+            pI, pJ = (None if x is None else _p(x, C.c_int32) for x in (I, J))
+            fn = lib().pem_tiled_assign
+        h = C.c_void_p()
+        _check(fn(self.ctx._h, self._h, A._h, pI, C.c_int64(ni), pJ, C.c_int64(nj), ACCUM_NONE if accum is None else BINOPS[accum], C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_assign(self, C_, A):
+        """Refresh a tiling made by C_.assign(A, rows, cols, accum) from C_'s and A's current values, in place.  Ordered on the
+        context's stream; returns without waiting."""
+        _check(lib().pem_tiled_set_values_from_assign(self.ctx._h, self._h, C_._h, A._h))
 
     def transpose(self):
         """Transpose: this tiling's matrix transposed, as a new tiling built on the device -- the arrays

@@ -346,7 +346,7 @@ static pem_status match_tiles(pem_ctx *ctx, const pem_tiled *A, const pem_tiled 
 }
 
 template <typename VT>
-static pem_status ewise_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const EwParams &prm, pem_tiled *R)
+static pem_status ewise_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, const EwParams &prm, pem_tiled *R, const char *fn)
 {
     hipStream_t st = ctx->stream;
     set_tiled_shape(R, A->value_bytes, A->rows, A->cols);
@@ -370,7 +370,7 @@ static pem_status ewise_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled 
     PEM_TRY(exclusive_scan_i32(ctx, ptr.as<int>(), ptr.as<int>(), nt, ctx->d_scalars));
     int64_t nnz = 0;
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 1, &nnz));
-    PEM_TRY(check_result_entries(ctx, nnz, "pem_tiled_ewise"));
+    PEM_TRY(check_result_entries(ctx, nnz, fn));
     R->nnz = nnz;
     const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
     PEM_TRY(reserve_payload(ctx, R));
@@ -409,8 +409,14 @@ extern "C" pem_status pem_tiled_ewise(pem_ctx *ctx, const pem_tiled *A, const pe
     PEM_TRY(check_operands(A, B, fn));
     const EwParams prm{pattern, op, alpha, beta};
     return build_derived(ctx, out, [&](pem_tiled *R) {
-        return A->value_bytes == 4 ? ewise_build<float>(ctx, A, B, prm, R) : ewise_build<double>(ctx, A, B, prm, R);
+        return A->value_bytes == 4 ? ewise_build<float>(ctx, A, B, prm, R, fn) : ewise_build<double>(ctx, A, B, prm, R, fn);
     });
+}
+
+pem_status pem::union_tiling(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled *R, const char *fn)
+{
+    const EwParams prm{PEM_EWISE_UNION, op, 1.0, 1.0};
+    return A->value_bytes == 4 ? ewise_build<float>(ctx, A, B, prm, R, fn) : ewise_build<double>(ctx, A, B, prm, R, fn);
 }
 
 static EwParams params_of(const pem_tiled *t)
@@ -431,11 +437,17 @@ static pem_status ewise_map(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, cons
 }
 
 template <typename VT>
-static void ewise_refresh(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
+static void ewise_refresh(pem_ctx *ctx, pem_tiled *t, const void *a_vals, const void *b_vals, const EwParams &prm)
 {
     const size_t nnz = (size_t)t->nnz;
-    PEM_LAUNCH(ctx, ew_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->derived.map.as<int2>(), t->vmap_t.as<int>(), nnz, A->vals.as<VT>(),
-               B->vals.as<VT>(), params_of(t), t->vals.as<VT>(), t->vals_t.as<VT>());
+    PEM_LAUNCH(ctx, ew_refresh_kernel<VT>, grid_for(nnz, 256), 256, t->derived.map.as<int2>(), t->vmap_t.as<int>(), nnz, static_cast<const VT *>(a_vals),
+               static_cast<const VT *>(b_vals), prm, t->vals.as<VT>(), t->vals_t.as<VT>());
+}
+
+void pem::refresh_pairs(pem_ctx *ctx, pem_tiled *t, const void *a_vals, const void *b_vals, int op)
+{
+    const EwParams prm{PEM_EWISE_UNION, op, 1.0, 1.0};
+    t->value_bytes == 4 ? ewise_refresh<float>(ctx, t, a_vals, b_vals, prm) : ewise_refresh<double>(ctx, t, a_vals, b_vals, prm);
 }
 
 extern "C" pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B)
@@ -452,5 +464,5 @@ extern "C" pem_status pem_tiled_set_values_from_ewise(pem_ctx *ctx, pem_tiled *t
     const bool f32 = t->value_bytes == 4;
     return refresh_derived(
         ctx, t, [&] { return f32 ? ewise_map<float>(ctx, t, A, B) : ewise_map<double>(ctx, t, A, B); },
-        [&] { f32 ? ewise_refresh<float>(ctx, t, A, B) : ewise_refresh<double>(ctx, t, A, B); });
+        [&] { f32 ? ewise_refresh<float>(ctx, t, A->vals.p, B->vals.p, params_of(t)) : ewise_refresh<double>(ctx, t, A->vals.p, B->vals.p, params_of(t)); });
 }

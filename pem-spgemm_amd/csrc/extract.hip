@@ -47,9 +47,11 @@ __device__ __forceinline__ int ex_src(const int *__restrict__ L, const long long
 }
 
 // 16 lanes per output tile row P, lane = local row r.  slots[16P + r] = tiles of source tile row I[16P + r] >> 4 where lane r leads
-// it, else 0; later[16P + r] = 1 for a leader that is not its tile row's first.  np = output tile rows.
+// it, else 0; later[16P + r] = 1 for a leader that is not its tile row's first.  np = output tile rows.  holes (scatter_tiling
+// only): a negative index is an output row without entries, not a range error.
 __global__ void __launch_bounds__(256) ex_slots_kernel(const int *__restrict__ I, long long ni, int a_rows, const int *__restrict__ a_rowptr,
-                                                       long long np, int *__restrict__ slots, int *__restrict__ later, int *__restrict__ flags)
+                                                       long long np, int holes, int *__restrict__ slots, int *__restrict__ later,
+                                                       int *__restrict__ flags)
 {
     const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int r = threadIdx.x & 15;
@@ -57,10 +59,10 @@ __global__ void __launch_bounds__(256) ex_slots_kernel(const int *__restrict__ I
     int S = -1;
     if (live && g < ni) {
         const int s = ex_src(I, g);
-        if (s < 0 || s >= a_rows)
-            flags[FLAG_RANGE] = 1;   // (the lane takes no part: a bad index is never an address)
-        else
+        if (s >= 0 && s < a_rows)
             S = s >> 4;
+        else if (!(holes && s < 0))
+            flags[FLAG_RANGE] = 1;   // (the lane takes no part: a bad index is never an address)
     }
     bool dup = false, before = false;
 #pragma unroll
@@ -98,7 +100,7 @@ __global__ void ex_cand_kernel(const int *__restrict__ I, const int *__restrict_
 }
 
 // what lane r of candidate c reads: A's tile at (source tile row, tc) and the tile_rec word of the source row there (0: none).
-// A candidate equal to the one before it is a duplicate and reads nothing.
+// A candidate equal to the one before it is a duplicate and reads nothing; so does a hole (a negative index, scatter_tiling).
 struct ExRow {
     int t;
     uint32_t rec;
@@ -114,6 +116,7 @@ __device__ __forceinline__ ExRow ex_row(const uint64_t *__restrict__ keys, const
     const long long p = 16 * (long long)(key >> bits_tc) + r;
     if (p >= ni) return x;
     const int s = ex_src(I, p);
+    if (s < 0) return x;
     x.t = mask_find_tile(a_rowptr, a_colidx, s >> 4, (int)(key & ((1ull << bits_tc) - 1ull)));
     if (x.t >= 0) x.rec = a_rec[16 * (size_t)x.t + (s & 15)];
     return x;
@@ -228,9 +231,9 @@ __global__ void __launch_bounds__(256) ex_map_kernel(const long long *__restrict
 // host side
 // ------------------------------------------------------------------------------------------
 // G = A(I, :) for a device list dI of ni checked-on-device indices (null: every row in order, ni = A's rows).  The flags were zeroed
-// by the caller.
+// by the caller.  holes: a negative index is an empty output row (scatter_tiling).
 template <typename VT>
-static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, int64_t ni, pem_tiled *G, const char *fn)
+static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, int64_t ni, bool holes, pem_tiled *G, const char *fn)
 {
     set_tiled_shape(G, A->value_bytes, (int)ni, A->cols);
     const size_t np = (size_t)G->tile_rows, ns = 16 * np;
@@ -238,8 +241,8 @@ static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, i
     DevBuf slots, later;   // per (output tile row, local row): candidates it leads -> their offset; a non-first leader
     PEM_TRY(slots.reserve(sizeof(int) * (ns + 4)));
     PEM_TRY(later.reserve(sizeof(int) * (ns + 4)));
-    PEM_LAUNCH(ctx, ex_slots_kernel, grid_for(ns, 256), 256, dI, (long long)ni, A->rows, A->tile_rowptr.as<int>(), (long long)np, slots.as<int>(),
-               later.as<int>(), ctx->d_flags);
+    PEM_LAUNCH(ctx, ex_slots_kernel, grid_for(ns, 256), 256, dI, (long long)ni, A->rows, A->tile_rowptr.as<int>(), (long long)np, holes ? 1 : 0,
+               slots.as<int>(), later.as<int>(), ctx->d_flags);
     PEM_TRY(exclusive_scan_i32_pair(ctx, slots.as<int>(), later.as<int>(), ns, ctx->d_scalars, ctx->d_scalars + 1));
     int64_t tot[2] = {0, 0};
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
@@ -292,9 +295,38 @@ static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, i
     return derive_tiled(ctx, G, headx, bits_tr, bits_tc);
 }
 
-static pem_status gather(pem_ctx *ctx, const pem_tiled *A, const int *dI, int64_t ni, pem_tiled *G, const char *fn)
+static pem_status gather(pem_ctx *ctx, const pem_tiled *A, const int *dI, int64_t ni, bool holes, pem_tiled *G, const char *fn)
 {
-    return A->value_bytes == 4 ? gather_rows<float>(ctx, A, dI, ni, G, fn) : gather_rows<double>(ctx, A, dI, ni, G, fn);
+    return A->value_bytes == 4 ? gather_rows<float>(ctx, A, dI, ni, holes, G, fn) : gather_rows<double>(ctx, A, dI, ni, holes, G, fn);
+}
+
+// R = A(d[0], d[1]) for device lists of n[0] and n[1] indices (null: all).  The flags were zeroed by the caller.
+static pem_status gather_both(pem_ctx *ctx, const pem_tiled *A, const int *const d[2], const int64_t n[2], bool holes, pem_tiled *R, const char *fn)
+{
+    if (!d[1]) return gather(ctx, A, d[0], n[0], holes, R, fn);
+    // the column side: (gather of the transposed rows by J)^T.  Every intermediate goes back to the arena when this returns.
+    std::unique_ptr<pem_tiled> G1, T1(new pem_tiled()), G2(new pem_tiled());
+    const pem_tiled *src = A;
+    if (d[0]) {
+        G1.reset(new pem_tiled());
+        PEM_TRY(gather(ctx, A, d[0], n[0], holes, G1.get(), fn));
+        src = G1.get();
+    }
+    PEM_TRY(transposed_tiling(ctx, src, T1.get()));
+    G1.reset();
+    PEM_TRY(gather(ctx, T1.get(), d[1], n[1], holes, G2.get(), fn));
+    T1.reset();
+    return transposed_tiling(ctx, G2.get(), R);
+}
+
+pem_status pem::scatter_tiling(pem_ctx *ctx, const pem_tiled *A, const int *inv_i, int rows, const int *inv_j, int cols, pem_tiled *S, const char *fn)
+{
+    const int *const d[2] = {inv_i, inv_j};
+    const int64_t n[2] = {rows, cols};
+    PEM_TRY(zero_flags(ctx));
+    pem_status s = gather_both(ctx, A, d, n, true, S, fn);
+    (void)hipStreamSynchronize(ctx->stream);   // (the intermediates went back to the arena)
+    return s;
 }
 
 // R = A(I, J).  The lists (host or device memory, null = all) are first copied into R's derivation, and those copies are what every
@@ -315,20 +347,7 @@ static pem_status extract_build(pem_ctx *ctx, const pem_tiled *A, const int32_t 
         PEM_HIP(hipMemcpyAsync(b.p, L[k], sizeof(int) * (size_t)n[k], on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
         d[k] = b.as<int>();
     }
-    if (!d[1]) return gather(ctx, A, d[0], n[0], R, fn);
-    // the column side: (gather of the transposed rows by J)^T.  Every intermediate goes back to the arena when this returns.
-    std::unique_ptr<pem_tiled> G1, T1(new pem_tiled()), G2(new pem_tiled());
-    const pem_tiled *src = A;
-    if (d[0]) {
-        G1.reset(new pem_tiled());
-        PEM_TRY(gather(ctx, A, d[0], n[0], G1.get(), fn));
-        src = G1.get();
-    }
-    PEM_TRY(transposed_tiling(ctx, src, T1.get()));
-    G1.reset();
-    PEM_TRY(gather(ctx, T1.get(), d[1], n[1], G2.get(), fn));
-    T1.reset();
-    return transposed_tiling(ctx, G2.get(), R);
+    return gather_both(ctx, A, d, n, false, R, fn);
 }
 
 static bool list_size_ok(const void *L, int64_t n, const char *which, const char *fn)

@@ -167,7 +167,7 @@ struct PendingSpan {
 };
 
 // device-side status words, zeroed at the start of every ABI call that launches kernels
-enum DevFlag { FLAG_RANGE = 0, FLAG_DUP = 1, FLAG_OVERFLOW = 2, FLAG_CAPACITY = 3, FLAG_INTERNAL = 4, NUM_FLAGS = 8 };
+enum DevFlag { FLAG_RANGE = 0, FLAG_DUP = 1, FLAG_OVERFLOW = 2, FLAG_CAPACITY = 3, FLAG_INTERNAL = 4, FLAG_REPEAT = 5, NUM_FLAGS = 8 };
 
 }  // namespace pem
 
@@ -302,9 +302,12 @@ uint64_t next_tiled_serial();
 //                                              map of a C^T tiling, chain.hip).
 //   EXTRACT pem_tiled_extract (extract.hip)    src[0] = A's serial.  idx[0], idx[1]: device copies of I and J (int32[ni], int32[nj];
 //                                              unallocated where the list was null = all).  map: as SELECT's.
+//   ASSIGN  pem_tiled_assign (assign.hip)      src = C's and A's serials; op = accum (PEM_ACCUM_NONE or a pem_binop).  idx[0], idx[1]:
+//                                              the inverses of I and J (int32[C.rows], int32[C.cols]: p where I[p] == i, else -1;
+//                                              unallocated where the list was null).  map: as EWISE's, slots in C's and A's vals.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;

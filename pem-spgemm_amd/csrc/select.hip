@@ -96,6 +96,33 @@ __global__ void sel_band_kernel(const long long *__restrict__ keys, const uint16
     flag[t] = n != 0;
 }
 
+// the region predicate of pem_tiled_assign (drop_region), one lane per A tile like sel_band_kernel: an entry is kept unless its row is
+// in I and its column in J.  rowbits[P] / colbits[Q] = the members among tile row P's rows / tile column Q's columns (null: all of
+// them), so new mask row r = mask & ~(rowbits[P] >> r & 1 ? colbits[Q] : 0) and a tile wholly outside the region costs one AND.
+__global__ void sel_region_kernel(const long long *__restrict__ keys, const uint16_t *__restrict__ masks, long long ta,
+                                  const uint16_t *__restrict__ rowbits, const uint16_t *__restrict__ colbits, uint32_t *__restrict__ nm,
+                                  int *__restrict__ cnt, int *__restrict__ flag)
+{
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ta) return;
+    const long long key = keys[t];
+    const unsigned rb = rowbits ? rowbits[key >> 32] : 0xFFFFu, cb = colbits ? colbits[key & 0xFFFFFFFFll] : 0xFFFFu;
+    const uint4 *pm = reinterpret_cast<const uint4 *>(masks + 16 * t);
+    const uint4 m0 = pm[0], m1 = pm[1];
+    unsigned w[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+    int n = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        w[q] &= ~((((rb >> (2 * q)) & 1u) ? cb : 0u) | (((rb >> (2 * q + 1)) & 1u) ? cb << 16 : 0u));
+        n += __popc(w[q]);
+    }
+    uint4 *po = reinterpret_cast<uint4 *>(nm + 8 * t);
+    po[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    po[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    cnt[t] = n;
+    flag[t] = n != 0;
+}
+
 // value ops: one wave per chunk of 64 consecutive A tiles, one ENTRY per lane.  Lane = tile first: its entry offset stays in the
 // lane's register; then every lane takes one entry of the chunk (its tile by a shuffle search over the offsets), tests its value and
 // ORs the keep bit into the tile's mask word in LDS.  Lane = tile again: nm, cnt and flag as sel_band_kernel writes them.
@@ -247,32 +274,23 @@ __global__ void __launch_bounds__(256) sel_map_kernel(const int *__restrict__ sr
 // ------------------------------------------------------------------------------------------
 static bool sel_positional(int op) { return op >= PEM_SELECT_TRIL && op <= PEM_SELECT_COL_GT; }
 
-template <typename VT>
-static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled *R)
+// the route around its mask kernel: masks(nm, roff, rid) launches the kernel that writes every A tile's new masks, kept count and
+// non-empty flag
+template <typename VT, typename Masks>
+static pem_status select_route(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, const char *fn, Masks masks)
 {
     set_tiled_shape(R, A->value_bytes, A->rows, A->cols);
-    R->derived.kind = Derivation::SELECT;
-    R->derived.src[0] = A->serial;
-    R->derived.op = op;
-    R->derived.p0 = thunk;
     const size_t ta = (size_t)A->ntiles;
     PEM_TRY(zero_flags(ctx));
     DevBuf nm, roff, rid;   // per A tile: new masks (uint32[8]); kept count -> R entry offset; non-empty flag -> R tile id
     PEM_TRY(nm.reserve(sizeof(uint32_t) * 8 * (ta + 1)));
     PEM_TRY(roff.reserve(sizeof(int) * (ta + 4)));
     PEM_TRY(rid.reserve(sizeof(int) * (ta + 4)));
-    if (ta) {
-        if (sel_positional(op))
-            PEM_LAUNCH(ctx, sel_band_kernel, grid_for(ta, 256), 256, A->tile_keys.as<long long>(), A->masks.as<uint16_t>(), (long long)ta, op,
-                       (long long)thunk, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>());
-        else
-            PEM_LAUNCH(ctx, sel_value_kernel<VT>, grid_for((ta + 63) / 64 * 64, 256), 256, A->tile_nnz_ptr.as<int>(), A->rowcolidx.as<uint8_t>(),
-                       A->vals.as<VT>(), (long long)ta, op, (VT)thunk, nm.as<uint32_t>(), roff.as<int>(), rid.as<int>());
-    }
+    if (ta) masks(nm.as<uint32_t>(), roff.as<int>(), rid.as<int>());
     PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ta, ctx->d_scalars, ctx->d_scalars + 1));
     int64_t tot[2] = {0, 0};
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
-    PEM_TRY(check_result_entries(ctx, tot[0], "pem_tiled_select"));
+    PEM_TRY(check_result_entries(ctx, tot[0], fn));
     const size_t nnz = (size_t)tot[0], nt = (size_t)tot[1];
     R->nnz = (int64_t)nnz;
     R->ntiles = (int64_t)nt;
@@ -287,6 +305,39 @@ static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double 
                    R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->derived.src_tiles.as<int>(), R->rowcolidx.as<uint8_t>(), headx,
                    R->vals.as<VT>());
     return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
+}
+
+template <typename VT>
+static pem_status select_build(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled *R)
+{
+    R->derived.kind = Derivation::SELECT;
+    R->derived.src[0] = A->serial;
+    R->derived.op = op;
+    R->derived.p0 = thunk;
+    const size_t ta = (size_t)A->ntiles;
+    return select_route<VT>(ctx, A, R, "pem_tiled_select", [&](uint32_t *nm, int *roff, int *rid) {
+        if (sel_positional(op))
+            PEM_LAUNCH(ctx, sel_band_kernel, grid_for(ta, 256), 256, A->tile_keys.as<long long>(), A->masks.as<uint16_t>(), (long long)ta, op,
+                       (long long)thunk, nm, roff, rid);
+        else
+            PEM_LAUNCH(ctx, sel_value_kernel<VT>, grid_for((ta + 63) / 64 * 64, 256), 256, A->tile_nnz_ptr.as<int>(), A->rowcolidx.as<uint8_t>(),
+                       A->vals.as<VT>(), (long long)ta, op, (VT)thunk, nm, roff, rid);
+    });
+}
+
+template <typename VT>
+static pem_status region_build(pem_ctx *ctx, const pem_tiled *C, const uint16_t *rowbits, const uint16_t *colbits, pem_tiled *R, const char *fn)
+{
+    const size_t ta = (size_t)C->ntiles;
+    return select_route<VT>(ctx, C, R, fn, [&](uint32_t *nm, int *roff, int *rid) {
+        PEM_LAUNCH(ctx, sel_region_kernel, grid_for(ta, 256), 256, C->tile_keys.as<long long>(), C->masks.as<uint16_t>(), (long long)ta, rowbits,
+                   colbits, nm, roff, rid);
+    });
+}
+
+pem_status pem::drop_region(pem_ctx *ctx, const pem_tiled *C, const uint16_t *rowbits, const uint16_t *colbits, pem_tiled *R, const char *fn)
+{
+    return C->value_bytes == 4 ? region_build<float>(ctx, C, rowbits, colbits, R, fn) : region_build<double>(ctx, C, rowbits, colbits, R, fn);
 }
 
 static bool select_args_ok(int op, double thunk, const char *fn)

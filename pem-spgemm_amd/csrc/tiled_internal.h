@@ -1,5 +1,5 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, extract.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, extract.hip, assign.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.
 #pragma once
@@ -37,6 +37,19 @@ void refresh_gather(pem_ctx *ctx, pem_tiled *T, const void *src, const int *map)
 pem_status transposed_tiling(pem_ctx *ctx, const pem_tiled *S, pem_tiled *T);
 // T->derived.map of such a T: every entry's slot in S's vals (int32[nnz + 4]).  Stream-ordered, no read-back (chain.hip).
 pem_status build_transpose_map(pem_ctx *ctx, pem_tiled *T);
+
+// ---- the stages of pem_tiled_assign (assign.hip), each the route of its unit with an internal argument ----
+// S = A(inv_i, inv_j), rows x cols: extract's gather where an index of -1 is a hole, an output row or column without entries
+// (extract.hip).  The lists are device arrays of rows and cols checked values (null: the identity); S gets no provenance.
+pem_status scatter_tiling(pem_ctx *ctx, const pem_tiled *A, const int *inv_i, int rows, const int *inv_j, int cols, pem_tiled *S, const char *fn);
+// R = C without its entries in the region: select's positional route with the predicate "not (row in I and column in J)"
+// (select.hip).  rowbits[P] / colbits[Q]: bit r set where row 16P + r / column 16Q + r is in the list (null: every one is).
+pem_status drop_region(pem_ctx *ctx, const pem_tiled *C, const uint16_t *rowbits, const uint16_t *colbits, pem_tiled *R, const char *fn);
+// R = op(A, B) over the union of the patterns, alpha = beta = 1: pem_tiled_ewise's build under the caller's name (ewise.hip).
+// R's provenance is ewise's; the caller may replace it.
+pem_status union_tiling(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled *R, const char *fn);
+// pem_tiled_set_values_from_ewise's kernel on t's int2 map (t->derived.map) and two value arrays of t's type, alpha = beta = 1
+void refresh_pairs(pem_ctx *ctx, pem_tiled *t, const void *a_vals, const void *b_vals, int op);
 
 // The shell of pem_tiled_from_cplan, pem_tiled_ewise and pem_tiled_select (their arguments checked, *out cleared): build(T) into
 // a fresh tiling, the time into conv_ms, synchronised; the tiling goes to *out on success and is freed otherwise.

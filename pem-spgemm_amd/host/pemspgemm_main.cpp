@@ -446,6 +446,11 @@ int main(int argc, char *argv[])
     // --add, or what --select kept) becomes R(I, J) on the device (pem_tiled_extract).  Each file is a Matrix-Market `array` file of
     // one column holding 1-based indices (`integer`, or `real` with integral values), in any order, repeats allowed.  --reduce,
     // --spmm, --sddmm and --out then see the extracted tiling.  The CSV row describes the product.
+    // `--assign-into D.mtx [--assign-rows I.mtx] [--assign-cols J.mtx] [--assign-accum OP]`: after the
+    // product and any --add / --select / --extract-*, the final result R is written into D at (I, J) on the device (pem_tiled_assign):
+    // D(I, J) = R, or D(I, J) = OP(D(I, J), R) with OP one of plus times min max lor land.  The lists are files like --extract-rows'
+    // (1-based, any order, no repeats; absent = all); R must be |I| x |J|.  D is read with --fp32 like A.  --reduce, --spmm, --sddmm,
+    // --out and the sorted COO files then see that tiling.  The CSV row describes the product.
     // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
     // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
     // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
@@ -466,6 +471,8 @@ int main(int argc, char *argv[])
     double add_alpha = 1.0, add_beta = 1.0;
     const char *select_spec = nullptr;   // --select OP[:THUNK]
     const char *extract_paths[2] = {nullptr, nullptr};   // --extract-rows I.mtx, --extract-cols J.mtx
+    const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP
+    const char *assign_paths[2] = {nullptr, nullptr};                  // --assign-rows I.mtx, --assign-cols J.mtx
     const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
     const char *spmm_path = nullptr;     // --spmm X.mtx
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;   // --sddmm X.mtx [--sddmm-y Y.mtx]
@@ -494,6 +501,10 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--select") && r + 1 < argc) select_spec = argv[++r];
             else if (!strcmp(argv[r], "--extract-rows") && r + 1 < argc) extract_paths[0] = argv[++r];
             else if (!strcmp(argv[r], "--extract-cols") && r + 1 < argc) extract_paths[1] = argv[++r];
+            else if (!strcmp(argv[r], "--assign-into") && r + 1 < argc) assign_into = argv[++r];
+            else if (!strcmp(argv[r], "--assign-rows") && r + 1 < argc) assign_paths[0] = argv[++r];
+            else if (!strcmp(argv[r], "--assign-cols") && r + 1 < argc) assign_paths[1] = argv[++r];
+            else if (!strcmp(argv[r], "--assign-accum") && r + 1 < argc) assign_accum_name = argv[++r];
             else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
             else if (!strcmp(argv[r], "--spmm") && r + 1 < argc) spmm_path = argv[++r];
             else if (!strcmp(argv[r], "--sddmm") && r + 1 < argc) sddmm_path = argv[++r];
@@ -615,6 +626,48 @@ int main(int argc, char *argv[])
             printf("%s %s: %s (want a Matrix-Market array file of one column of 1-based indices). Exiting.\n", extract_flags[q], extract_paths[q],
                    err.c_str());
             return 1;
+        }
+    }
+    // --assign-into: the accum by name and the lists read up front, so that a bad option or file is refused before any work
+    static const char *const assign_flags[2] = {"--assign-rows", "--assign-cols"};
+    std::vector<int32_t> assign_idx[2];
+    int assign_accum = PEM_ACCUM_NONE;
+    if (!assign_into) {
+        const char *lone = assign_paths[0] ? assign_flags[0] : assign_paths[1] ? assign_flags[1] : assign_accum_name ? "--assign-accum" : nullptr;
+        if (lone) {
+            printf("%s needs --assign-into <D.mtx>. Exiting.\n", lone);
+            return 1;
+        }
+    } else {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : nullptr;
+        if (clash) {
+            printf("--assign-into does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        if (assign_accum_name) {
+            for (int i = 0; i < 6; ++i)
+                if (!strcmp(assign_accum_name, add_op_names[i])) assign_accum = i;
+            if (assign_accum == PEM_ACCUM_NONE) {
+                printf("--assign-accum %s: unknown op (plus, times, min, max, lor, land). Exiting.\n", assign_accum_name);
+                return 1;
+            }
+        }
+        for (int q = 0; q < 2; ++q) {
+            if (!assign_paths[q]) continue;
+            const std::string err = read_index_array(assign_paths[q], &assign_idx[q]);
+            if (!err.empty()) {
+                printf("%s %s: %s (want a Matrix-Market array file of one column of 1-based indices). Exiting.\n", assign_flags[q], assign_paths[q],
+                       err.c_str());
+                return 1;
+            }
+            std::vector<int32_t> sorted(assign_idx[q]);
+            std::sort(sorted.begin(), sorted.end());
+            const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+            if (dup != sorted.end()) {
+                printf("%s %s: index %d is repeated; assign is defined for lists without repeats only. Exiting.\n", assign_flags[q], assign_paths[q],
+                       *dup + 1);
+                return 1;
+            }
         }
     }
     // --spmm: X read up front, so that a bad file is refused before any work
@@ -910,6 +963,34 @@ int main(int argc, char *argv[])
             return 2;
         }
     }
+    pem_tiled *Into = nullptr;   // --assign-into: D, in the value type of A
+    pem_coo cinto;
+    memset(&cinto, 0, sizeof cinto);
+    if (assign_into) {
+        if (read_input(assign_into, &cinto) != 0) return 1;
+        const int dims[2] = {cinto.rows, cinto.cols};
+        for (int q = 0; q < 2; ++q)
+            for (size_t j = 0; j < assign_idx[q].size(); ++j)
+                if (assign_idx[q][j] >= dims[q]) {
+                    printf("%s %s: index %zu is %d; %s has %d %s. Exiting.\n", assign_flags[q], assign_paths[q], j + 1, assign_idx[q][j] + 1,
+                           assign_into, dims[q], q ? "columns" : "rows");
+                    pem_coo_free(&cinto);
+                    return 1;
+                }
+        pem_status ds;
+        if (fp32) {
+            std::vector<float> vf((size_t)cinto.nnz);
+            for (int64_t e = 0; e < cinto.nnz; ++e) vf[(size_t)e] = (float)cinto.V[e];
+            ds = pem_tiled_from_coo_f32(ctx, cinto.rows, cinto.cols, cinto.nnz, cinto.I, cinto.J, vf.data(), 0, &Into);
+        } else {
+            ds = pem_tiled_from_coo(ctx, cinto.rows, cinto.cols, cinto.nnz, cinto.I, cinto.J, cinto.V, 0, &Into);
+        }
+        if (ds != PEM_OK) {
+            fprintf(stderr, "pemspgemm: conversion of %s failed: %s\n", assign_into, pem_last_error());
+            pem_coo_free(&cinto);
+            return 2;
+        }
+    }
     if (fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", argv[1], ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
     printf("MATRIX B\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", b_path ? b_path : argv[1], ib.rows, ib.cols, (long long)ib.nnz);
@@ -1089,8 +1170,39 @@ int main(int argc, char *argv[])
                Sel ? "the selection" : Sum ? "the sum" : "C", xi.conv_ms, ext_total_ms, xi.rows, xi.cols, (long long)xi.nnz, (long long)src.nnz);
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
-    pem_tiled *const Last = Ext ? Ext : Sel ? Sel : Sum;   // the final result when it is a tiling, and what the lines below call it
-    const char *const last_name = Ext ? "the extract" : Sel ? "the selection" : Sum ? "the sum" : "C";
+    pem_tiled *Asg = nullptr;   // --assign-into: D with D(I, J) = R, R being C, the sum, the selection or the extract
+    if (Into) {
+        auto g0 = std::chrono::high_resolution_clock::now();
+        pem_tiled *Src = Ext ? Ext : Sel ? Sel : Sum, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info gi, src, di;
+        CHECK(pem_tiled_get_info(Src, &src));
+        CHECK(pem_tiled_get_info(Into, &di));
+        const long long want_r = assign_paths[0] ? (long long)assign_idx[0].size() : di.rows;
+        const long long want_c = assign_paths[1] ? (long long)assign_idx[1].size() : di.cols;
+        if (src.rows != want_r || src.cols != want_c) {
+            printf("--assign-into %s: the result is %d x %d but the region is %lld x %lld (%s is %d x %d). Exiting.\n", assign_into, src.rows, src.cols,
+                   want_r, want_c, assign_into, di.rows, di.cols);
+            if (Ct) pem_tiled_destroy(ctx, Ct);
+            return 1;
+        }
+        CHECK(pem_tiled_assign(ctx, Into, Src, assign_paths[0] ? assign_idx[0].data() : nullptr, (int64_t)assign_idx[0].size(),
+                               assign_paths[1] ? assign_idx[1].data() : nullptr, (int64_t)assign_idx[1].size(), assign_accum, &Asg));
+        const double asg_total_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - g0).count();
+        CHECK(pem_tiled_get_info(Asg, &gi));
+        printf("assign: %s into %s at %s x %s%s%s: assign %.2fms, total %.2fms, %d x %d, nnz %lld (D %lld, the result %lld)\n",
+               Ext ? "the extract" : Sel ? "the selection" : Sum ? "the sum" : "C", assign_into,
+               assign_paths[0] ? std::to_string(assign_idx[0].size()).append(" rows").c_str() : "all rows",
+               assign_paths[1] ? std::to_string(assign_idx[1].size()).append(" columns").c_str() : "all columns",
+               assign_accum == PEM_ACCUM_NONE ? "" : ", accum ", assign_accum == PEM_ACCUM_NONE ? "" : add_op_names[assign_accum], gi.conv_ms,
+               asg_total_ms, gi.rows, gi.cols, (long long)gi.nnz, (long long)di.nnz, (long long)src.nnz);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+    pem_tiled *const Last = Asg ? Asg : Ext ? Ext : Sel ? Sel : Sum;   // the final result when it is a tiling, and what the lines below call it
+    const char *const last_name = Asg ? "the assigned matrix" : Ext ? "the extract" : Sel ? "the selection" : Sum ? "the sum" : "C";
 
     std::vector<double> red;   // --reduce: the vector, on the host
     if (reduce_dim >= 0) {
@@ -1261,6 +1373,27 @@ int main(int argc, char *argv[])
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
             rc = 2;
         }
+    } else if (Asg) {   // the assigned matrix's entries, sorted by (row, column): its CSR export is that order
+        const char *dir = getenv("PEM_RESULT_DIR") ? getenv("PEM_RESULT_DIR") : "/tmp";
+        pem_tiled_info gi;
+        CHECK(pem_tiled_get_info(Asg, &gi));
+        std::vector<int32_t> rp((size_t)gi.rows + 1), rows((size_t)gi.nnz), cols((size_t)gi.nnz);
+        std::vector<double> vals((size_t)gi.nnz);
+        int64_t nnz = 0;
+        if (fp32) {
+            std::vector<float> vf((size_t)gi.nnz);
+            CHECK(pem_tiled_export_csr_f32(ctx, Asg, &nnz, rp.data(), cols.data(), vf.data()));
+            for (size_t e = 0; e < vf.size(); ++e) vals[e] = vf[e];
+        } else {
+            CHECK(pem_tiled_export_csr(ctx, Asg, &nnz, rp.data(), cols.data(), vals.data()));
+        }
+        for (size_t i = 0; i + 1 < rp.size(); ++i)
+            for (int32_t e = rp[i]; e < rp[i + 1]; ++e) rows[(size_t)e] = (int32_t)i;
+        printf("Saving results to %s/SPGEMM_RESULT_*.txt\n", dir);
+        if (pem_write_result_files(dir, nnz, rows.data(), cols.data(), vals.data()) != 0) {
+            fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
+            rc = 2;
+        }
     } else {
         const char *dir = getenv("PEM_RESULT_DIR") ? getenv("PEM_RESULT_DIR") : "/tmp";
         std::vector<int32_t> rows((size_t)ci.nnz_c), cols((size_t)ci.nnz_c);
@@ -1287,6 +1420,11 @@ int main(int argc, char *argv[])
                                           : std::string(", extract ") + (extract_paths[0] ? std::string("rows ") + extract_paths[0] : std::string()) +
                                                 (extract_paths[0] && extract_paths[1] ? ", " : "") +
                                                 (extract_paths[1] ? std::string("columns ") + extract_paths[1] : std::string());
+    const std::string assign_note = !Asg ? std::string()
+                                         : std::string(", assigned into ") + assign_into +
+                                               (assign_paths[0] ? std::string(" rows ") + assign_paths[0] : std::string()) +
+                                               (assign_paths[1] ? std::string(" columns ") + assign_paths[1] : std::string()) +
+                                               (assign_accum == PEM_ACCUM_NONE ? std::string() : std::string(" accum ") + add_op_names[assign_accum]);
     if (out_path && spmm_path) {   // Y as a Matrix-Market dense array (R.rows x k, values column by column)
         FILE *f = fopen(out_path, "w");
         bool ok = f != nullptr;
@@ -1325,6 +1463,7 @@ int main(int argc, char *argv[])
         std::string comment = std::string("R = pattern(C) o (X Y^T) (") + semiring_names[semiring] + ")";
         if (Sel) comment += std::string(", C after select ") + select_spec;
         comment += extract_note;
+        comment += assign_note;
         comment += " by pemspgemm (pem-spgemm_amd)";
         if (pem_write_mtx_csr(out_path, si.rows, si.cols, sd_rp.data(), sd_ci.data(), sd_v.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
@@ -1348,6 +1487,7 @@ int main(int argc, char *argv[])
         std::string comment = Sum ? std::string("C = alpha*A*B + beta*D (") + semiring_names[semiring] + ")" : std::string("C = A*B (") + semiring_names[semiring] + ")";
         if (Sel) comment += std::string(", select ") + select_spec;
         comment += extract_note;
+        comment += assign_note;
         comment += " by pemspgemm (pem-spgemm_amd)";
         if (pem_write_mtx_csr(out_path, si.rows, si.cols, rp.data(), cidx.data(), cv.data(), comment.c_str()) != 0) {
             fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
@@ -1381,6 +1521,9 @@ int main(int argc, char *argv[])
     if (Mt) pem_tiled_destroy(ctx, Mt);
     pem_coo_free(&cm);
     if (Sd) pem_tiled_destroy(ctx, Sd);
+    if (Asg) pem_tiled_destroy(ctx, Asg);
+    if (Into) pem_tiled_destroy(ctx, Into);
+    pem_coo_free(&cinto);
     if (Ext) pem_tiled_destroy(ctx, Ext);
     if (Sel) pem_tiled_destroy(ctx, Sel);
     if (Sum) pem_tiled_destroy(ctx, Sum);
