@@ -448,6 +448,40 @@ pem_status pem_tiled_mxv_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int
 pem_status pem_tiled_reduce(pem_ctx *ctx, const pem_tiled *A, int op, int dim, double *dy, int accumulate);
 pem_status pem_tiled_reduce_f32(pem_ctx *ctx, const pem_tiled *A, int op, int dim, float *dy, int accumulate);
 
+/* Frontier products: pem_tiled_mxv with a sparse input vector and an output mask, and the breadth-first
+ * search built on it.
+ *   pem_tiled_mxv_frontier  orientation, lengths and coordinates as pem_tiled_mxv.  dx_present: nx bytes, x_j is present where its byte
+ *       is nonzero (NULL: every x_j is present).  dy_mask: ny bytes; output i is allowed when dy_mask is NULL or (dy_mask[i] != 0) !=
+ *       mask_complement.  dy_present: ny bytes, written (NULL: not wanted).  All are device arrays on the context's device (a bool or
+ *       uint8 tensor works).
+ *     For an allowed i, y_i is pem_tiled_mxv's fold restricted to the stored a_ij whose x_j is present: the same order (ascending j;
+ *       the fma chain under plus_times), the same start value (or the old y_i with accumulate = 1), the same arithmetic, no atomics --
+ *       bit for bit the plan product A*X with X the nx x 1 tiling storing exactly the present x_j (zero signs under min / max and NaN
+ *       payloads excepted, as for pem_tiled_mxv).  An absent x_j is never read: whatever bytes sit there cannot reach y.  An allowed i
+ *       that receives no term gets the start value (accumulate = 0) or is left untouched (accumulate = 1).  A disallowed i is never
+ *       written (a mask without replace).  dy_present[i] = 1 where i is allowed and at least one term entered its fold (structural: a
+ *       lor_land term that is false counts), else 0; all ny bytes are written.  plus_pair reads neither dx nor A's values: dx may be
+ *       NULL there.
+ *     PEM_E_INVALID, before the device is touched: the null, unknown-semiring, flag and value-type cases of pem_tiled_mxv;
+ *       mask_complement not 0 or 1; dy_present's bytes overlapping dy_mask, dx_present, dx or dy; x and y overlapping.  An empty
+ *       tiling and a 0-length y are legal.
+ *     Stream-ordered on the context's stream; never waits and reads nothing back.  With a dx_present the call keeps 2 bytes per 16
+ *       entries of x and 1 byte per 16 outputs in a grow-only scratch of the context, carved from its arena: a later call of the same
+ *       or a smaller size allocates nothing.  The column orientation builds pem_tiled_mxv's column schedule on first use.  Lines no
+ *       present x can reach, and lines without an allowed output, are skipped before their tile index is read; for a dense x without
+ *       a mask pem_tiled_mxv is the call to use.
+ *   pem_tiled_bfs  breadth-first search from `source` over the pattern of a square tiling: a stored entry (i, j), explicit zeros
+ *       included, is an edge i -> j (transpose = 1: j -> i).  d_level: A.rows int32 on the device, the least number of edges from
+ *       source to v, -1 where v is unreachable; *depth the largest level, *reached the number of vertices with a level.  Every level is
+ *       one pem_tiled_mxv_frontier under plus_pair (frontier = dx_present, visited = the complemented mask, next frontier = dy_present)
+ *       and one 4-byte read-back; no value is read.  Waits.  PEM_E_INVALID: a null argument, a tiling that is not square, source
+ *       outside [0, rows), transpose not 0 or 1. */
+pem_status pem_tiled_mxv_frontier(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, const double *dx, const uint8_t *dx_present,
+                                  double *dy, const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate);
+pem_status pem_tiled_mxv_frontier_f32(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, const float *dx, const uint8_t *dx_present,
+                                      float *dy, const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate);
+pem_status pem_tiled_bfs(pem_ctx *ctx, const pem_tiled *A, int64_t source, int transpose, int32_t *d_level, int32_t *depth, int64_t *reached);
+
 /* Sparse times dense block: a tiling times k dense device vectors at once under a semiring.
  *   pem_tiled_spmm  Y = A (+).(x) X  (transpose = 0: X is A.cols x k, Y is A.rows x k)
  *                   Y = A^T (+).(x) X  (transpose = 1: X is A.rows x k, Y is A.cols x k)

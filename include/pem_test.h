@@ -60,6 +60,11 @@ pem_status pem_debug_scan_i32(pem_ctx *ctx, const int32_t *in, int64_t n, int re
  * pem_last_error() -- from the next call that synchronises (pem_ctx_synchronize, the end of a pass, a conversion). */
 pem_status pem_debug_refused_launch(pem_ctx *ctx);
 
+/* The line flags of the context's last pem_tiled_mxv_frontier (its mark step): host_dst[L] = 1 exactly where output line L (16 rows
+ * for transpose = 0, 16 columns for transpose = 1) stores a tile whose x segment has a present entry.  nlines must be that call's
+ * number of lines.  Waits.  PEM_E_STATE if that call had dx_present == NULL (nothing is marked then) or there was none. */
+pem_status pem_test_frontier_line_flags(pem_ctx *ctx, uint8_t *host_dst, int64_t nlines);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_sddmm", "pem_tiled_set_values_sddmm_f32", "pem_tiled_sddmm", "pem_tiled_sddmm_f32",
     "pem_tiled_transpose", "pem_tiled_set_values_from_transpose", "pem_tiled_extract", "pem_tiled_extract_device",
     "pem_tiled_set_values_from_extract", "pem_tiled_assign", "pem_tiled_assign_device", "pem_tiled_set_values_from_assign",
+    "pem_tiled_mxv_frontier", "pem_tiled_mxv_frontier_f32", "pem_tiled_bfs", "pem_test_frontier_line_flags",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -480,6 +481,58 @@ class Tiled:
         fn = lib().pem_tiled_mxv_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, py, int(bool(accumulate))))
         return out
+
+    def _bytes(self, fn, name, v, n):
+        """the device pointer of a contiguous torch.bool / torch.uint8 tensor of n bytes on the context's device; None passes as NULL"""
+        if v is None:
+            return None
+        if (not hasattr(v, "data_ptr") or not v.is_cuda or v.device.index != self.ctx.device or v.numel() != n or v.dim() != 1
+                or not v.is_contiguous() or str(v.dtype) not in ("torch.bool", "torch.uint8")):
+            got = f"{v.dtype} of shape {tuple(v.shape)} on {v.device}" if hasattr(v, "data_ptr") else type(v).__name__
+            raise ValueError(f"{fn}: want a contiguous device tensor of {n} bool or uint8 values on cuda:{self.ctx.device} for {name}, got {got}")
+        return C.c_void_p(v.data_ptr() or 1)
+
+    def mxv_frontier(self, x, x_present=None, mask=None, mask_complement=False, semiring="plus_times", transpose=False, out=None,
+                     accumulate=False, out_present=None):
+        """mxv with a sparse input vector and an output mask.  x, out: as for mxv (x may be None under
+        plus_pair, which reads no value).  x_present: x_j takes part where its byte is nonzero (None: every x_j); mask: out_i may be
+        written where (mask_i != 0) != mask_complement (None: every out_i); out_present: set to 1 where out_i is allowed and got at
+        least one term, else 0.  The three are contiguous device torch.bool / torch.uint8 tensors of x's resp. out's length.  An
+        allowed out_i is mxv's fold over the entries whose x_j is present -- bit for bit CPlan(A, X) with X storing the present x_j --
+        and gets the start value, or stays with accumulate=True, when none is; an absent x_j is never read; a disallowed out_i is
+        never written.  Lines no present x_j can reach or without an allowed output are skipped before their entries are touched.
+        Ordered on the context's stream and never waits (see mxv).  Returns out."""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        nx, ny = (self.rows, self.cols) if transpose else (self.cols, self.rows)
+        px = None if x is None and semiring == "plus_pair" else self._vector("mxv_frontier", "x", x, nx)
+        pxp = self._bytes("mxv_frontier", "x_present", x_present, nx)
+        pm = self._bytes("mxv_frontier", "mask", mask, ny)
+        pyp = self._bytes("mxv_frontier", "out_present", out_present, ny)
+        like = next((t for t in (x, x_present, mask, out_present) if t is not None), None)
+        out, py = self._out("mxv_frontier", out, ny, like=like)
+        fn = lib().pem_tiled_mxv_frontier_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv_frontier
+        _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, pxp, py, pm, int(bool(mask_complement)), pyp,
+                  int(bool(accumulate))))
+        return out
+
+    def frontier_line_flags(self, transpose=False):
+        """test hook (pem_test.h): the line flags of the context's last mxv_frontier with an x_present, one byte per 16 outputs.  Waits."""
+        n = self.tile_cols if transpose else self.tile_rows
+        flags = np.zeros(n, np.uint8)
+        _check(lib().pem_test_frontier_line_flags(self.ctx._h, _p(flags, C.c_uint8), C.c_int64(n)))
+        return flags
+
+    def bfs(self, source, transpose=False):
+        """Breadth-first search over the pattern of a square tiling: a stored entry (i, j) is an edge
+        i -> j (transpose=True: j -> i).  Returns (levels, depth, reached): an int32 device torch tensor with the least number of
+        edges from source to every vertex (-1: unreachable), the largest level, and the number of vertices reached.  Waits."""
+        import torch
+        levels = torch.empty(self.rows, dtype=torch.int32, device=torch.device("cuda", self.ctx.device))
+        depth, reached = C.c_int32(), C.c_int64()
+        _check(lib().pem_tiled_bfs(self.ctx._h, self._h, C.c_int64(int(source)), int(bool(transpose)), C.c_void_p(levels.data_ptr() or 1),
+                                   C.byref(depth), C.byref(reached)))
+        return levels, depth.value, reached.value
 
     def _block(self, fn, name, v, n, k=None, dtype=None):
         """(k, ld) of a 2-D row-major device torch tensor of dtype (None: this tiling's) with n rows (and k columns): stride(1) == 1

@@ -194,6 +194,11 @@ struct pem_ctx {
     bool capturing = false;            // a warm pass is being captured into a hipGraph: no timing events, no syncs
     bool chain_events = false;         // pem_spgemm: steps run back to back, boundary events are shared
     pem::DevBuf tmp[12];               // step/convert temporaries, see call sites
+    // pem_tiled_mxv_frontier (frontier.hip): the presence words of x (uint16 per 16-entry segment) and, from fr_flags_off, the line
+    // flags (1 byte per output line) of the last call; fr_lines: that call's lines, -1 where it had no dx_present (or none yet)
+    pem::DevBuf fr_scratch;
+    size_t fr_flags_off = 0;
+    int64_t fr_lines = -1;
     int dbg_scan_force = 0;            // pem_debug_scan_i32: 0 automatic, 2 single-launch chained scan, 3 three-launch scan
     int dbg_scan_stall_ticket = -1;    // ... and the chained scan's block that stalls before it publishes
     // timing

@@ -454,6 +454,10 @@ int main(int argc, char *argv[])
     // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
     // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
     // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
+    // `--bfs SRC` runs a breadth-first search from the 1-based vertex SRC over the pattern of the final
+    // result (what --reduce would fold; it must be square) on the device (pem_tiled_bfs): a stored entry (i, j) is an edge i -> j.
+    // One line reports depth, reached and the time; --out then writes the levels (Matrix-Market `array integer general`, -1 for
+    // unreachable) instead of the matrix.  The CSV row describes the product.
     // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
     // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
     // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
@@ -474,6 +478,7 @@ int main(int argc, char *argv[])
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP
     const char *assign_paths[2] = {nullptr, nullptr};                  // --assign-rows I.mtx, --assign-cols J.mtx
     const char *reduce_spec = nullptr;   // --reduce rows|cols[:OP]
+    const char *bfs_spec = nullptr;      // --bfs SRC
     const char *spmm_path = nullptr;     // --spmm X.mtx
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;   // --sddmm X.mtx [--sddmm-y Y.mtx]
     static std::string standin_path;
@@ -506,6 +511,7 @@ int main(int argc, char *argv[])
             else if (!strcmp(argv[r], "--assign-cols") && r + 1 < argc) assign_paths[1] = argv[++r];
             else if (!strcmp(argv[r], "--assign-accum") && r + 1 < argc) assign_accum_name = argv[++r];
             else if (!strcmp(argv[r], "--reduce") && r + 1 < argc) reduce_spec = argv[++r];
+            else if (!strcmp(argv[r], "--bfs") && r + 1 < argc) bfs_spec = argv[++r];
             else if (!strcmp(argv[r], "--spmm") && r + 1 < argc) spmm_path = argv[++r];
             else if (!strcmp(argv[r], "--sddmm") && r + 1 < argc) sddmm_path = argv[++r];
             else if (!strcmp(argv[r], "--sddmm-y") && r + 1 < argc) sddmm_y_path = argv[++r];
@@ -741,6 +747,21 @@ int main(int argc, char *argv[])
                 printf("--reduce %s: unknown op %s (plus, times, min, max, lor, land). Exiting.\n", reduce_spec, colon + 1);
                 return 1;
             }
+        }
+    }
+    // --bfs: the 1-based source
+    long long bfs_src = 0;
+    if (bfs_spec) {
+        const char *clash = ngpu > 0 ? "--gpus" : power ? "--power" : reduce_spec ? "--reduce" : spmm_path ? "--spmm" : sddmm_path ? "--sddmm" : nullptr;
+        if (clash) {
+            printf("--bfs does not combine with %s. Exiting.\n", clash);
+            return 1;
+        }
+        char *end = nullptr;
+        bfs_src = strtoll(bfs_spec, &end, 10);
+        if (end == bfs_spec || *end != '\0' || bfs_src < 1) {
+            printf("--bfs %s: want a 1-based vertex number. Exiting.\n", bfs_spec);
+            return 1;
         }
     }
     if (ngpu > 0 && mask_path) {
@@ -1241,6 +1262,42 @@ int main(int argc, char *argv[])
         if (Ct) pem_tiled_destroy(ctx, Ct);
     }
 
+    std::vector<int32_t> bfs_levels;   // --bfs: the levels, on the host
+    if (bfs_spec) {
+        pem_tiled *Src = Last, *Ct = nullptr;
+        if (!Src) {
+            CHECK(pem_tiled_from_cplan(ctx, plan, 0, &Ct));
+            Src = Ct;
+        }
+        pem_tiled_info si;
+        CHECK(pem_tiled_get_info(Src, &si));
+        if (si.rows != si.cols || bfs_src > si.rows) {
+            if (si.rows != si.cols)
+                printf("--bfs %s: %s is %d x %d; a search needs a square matrix. Exiting.\n", bfs_spec, last_name, si.rows, si.cols);
+            else
+                printf("--bfs %s: %s has %d vertices. Exiting.\n", bfs_spec, last_name, si.rows);
+            if (Ct) pem_tiled_destroy(ctx, Ct);
+            return 1;
+        }
+        const size_t n = (size_t)si.rows;
+        int32_t *dl = nullptr;
+        if (hipMalloc((void **)&dl, 4 * n + 8) != hipSuccess) {
+            fprintf(stderr, "pemspgemm: --bfs: device allocation of %zu levels failed\n", n);
+            return 2;
+        }
+        CHECK(pem_ctx_synchronize(ctx));
+        int32_t depth = 0;
+        int64_t reached = 0;
+        auto b0 = std::chrono::high_resolution_clock::now();
+        CHECK(pem_tiled_bfs(ctx, Src, (int64_t)(bfs_src - 1), 0, dl, &depth, &reached));
+        const double bfs_ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - b0).count();
+        bfs_levels.resize(n);
+        if (hipMemcpy(bfs_levels.data(), dl, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+        (void)hipFree(dl);
+        printf("bfs: from %lld over %s: depth %d, reached %lld of %zu, bfs %.3fms\n", bfs_src, last_name, depth, (long long)reached, n, bfs_ms);
+        if (Ct) pem_tiled_destroy(ctx, Ct);
+    }
+
     std::vector<double> spmm_y;   // --spmm: Y, row-major, on the host
     int64_t spmm_ny = 0;
     if (spmm_path) {
@@ -1425,7 +1482,22 @@ int main(int argc, char *argv[])
                                                (assign_paths[0] ? std::string(" rows ") + assign_paths[0] : std::string()) +
                                                (assign_paths[1] ? std::string(" columns ") + assign_paths[1] : std::string()) +
                                                (assign_accum == PEM_ACCUM_NONE ? std::string() : std::string(" accum ") + add_op_names[assign_accum]);
-    if (out_path && spmm_path) {   // Y as a Matrix-Market dense array (R.rows x k, values column by column)
+    if (out_path && bfs_spec) {   // the levels as a Matrix-Market dense integer array (n x 1)
+        FILE *f = fopen(out_path, "w");
+        bool ok = f != nullptr;
+        if (ok) {
+            ok = fprintf(f, "%%%%MatrixMarket matrix array integer general\n%% bfs levels from %lld by pemspgemm (pem-spgemm_amd)\n%zu 1\n", bfs_src,
+                         bfs_levels.size()) > 0;
+            for (size_t i = 0; ok && i < bfs_levels.size(); ++i) ok = fprintf(f, "%d\n", bfs_levels[i]) > 0;
+            ok = fclose(f) == 0 && ok;
+        }
+        if (!ok) {
+            fprintf(stderr, "pemspgemm: --out %s: cannot write the levels\n", out_path);
+            rc = 2;
+        } else {
+            printf("levels written to %s\n", out_path);
+        }
+    } else if (out_path && spmm_path) {   // Y as a Matrix-Market dense array (R.rows x k, values column by column)
         FILE *f = fopen(out_path, "w");
         bool ok = f != nullptr;
         const int64_t ld = spmm_k > 1 ? spmm_k : 1;
