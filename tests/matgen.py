@@ -137,3 +137,52 @@ def step1_cases(rng):
     key = rng.permutation(np.unique(np.concatenate([I.astype(np.int64) * 33600 + J, extra_i.astype(np.int64) * 33600 + extra_j])))
     out["hub_tile_2100_AAt"] = (65536, 33600, (key // 33600).astype(np.int32), (key % 33600).astype(np.int32), _vals(rng, len(key)), True)
     return out
+
+
+BIGDIM_RUNGS = {20: 524_288, 22: 2_097_152, 24: 8_388_608, 27: 67_108_864}     # rung -> T; B = A^T has T + 1 tile columns
+
+
+def bigdim_case(rung):
+    """The recipe of k64_bins at R = 16 T + 5 rows, so that B = A^T has T + 1 > 2^(rung - 1) tile columns and step 1's tile-column
+    field takes `rung` bits: the bins whose index field no longer fits beside it in 32 bits sort real 64-bit keys.  Group counts
+    and hub rows populate every row list with pruning on and off (products per tile row of A*A^T = the sizes of the groups it has
+    an entry in; pruning keeps about 0.73 of them): the tiny bin (group 36: 30), the 512-key bin (260, 100), the 2048-key bin (700,
+    1500, the five-group hub), the 8192-key bin (the hub in groups 0..29: 7 800) and three rows above it (every group: 11 690),
+    which take the oversized-row path -- or the segments -- now that the 32768-key bin is dropped.  The last row R - 1 holds entries."""
+    T = BIGDIM_RUNGS[rung]
+    R = 16 * T + 5
+    rng = np.random.default_rng(1000 + rung)
+    counts = [260] * 36 + [30, 100, 700, 1500]
+    hubs = [(777_777, list(range(40))), (R // 2 + 3, list(range(40))), (R - 40, list(range(40))), (1_234_567, list(range(30))),
+            (42, [0, 1, 2, 3, 38]), (R - 1, [37, 39])]
+    return _grouped(rng, R, 40, counts, hubs)
+
+
+def bigdim_cases(rungs=(20, 22, 24)):
+    """name -> (rows, cols, I, J, V, transpose_B): the key-width ladder of tests/test_gpu_bigdims.py (not part of cases())"""
+    return {f"rung{r}": bigdim_case(r) for r in rungs}
+
+
+HYPER_N = 16 * 262_145 + 5
+
+
+def hypersparse(seed=777):
+    """(n, I, J, V, S): a square matrix of n = 4 194 325 rows whose tiling has more than 262 144 tile rows, tile columns and tiles
+    (the length at which the device scan leaves its single chained launch), with a product A*A that has so many entries and tiles
+    too.  S: 400 indices, among them both sides of tile line 262 143 | 262 144 and the first and last index, with 6 000 entries on
+    S x S (every pair of the eight pinned indices among them, so entries lie on, above and below the diagonals +-2^22); 300 000 scattered entries in distinct rows with columns drawn from that row set (so A*A is not empty); one dense 16 x 16
+    tile in tile row 262 144."""
+    n = HYPER_N
+    rng = np.random.default_rng(seed)
+    pinned = np.array([0, 15, 16, 4_194_303, 4_194_304, 4_194_319, 4_194_320, n - 1], np.int64)
+    S = np.unique(np.concatenate([pinned, rng.choice(n, size=400, replace=False)]))
+    S = np.sort(np.concatenate([pinned, rng.permutation(np.setdiff1d(S, pinned))[:400 - len(pinned)]]))
+    k = rng.choice(400 * 400, size=6000, replace=False)
+    ci, cj = S[k // 400], S[k % 400]
+    rows = rng.choice(n, size=300_000, replace=False).astype(np.int64)
+    cols = rows[rng.integers(0, len(rows), len(rows))]
+    di, dj = np.meshgrid(np.arange(16) + 16 * 262_144, np.arange(16) + 16 * 262_144, indexing="ij")
+    pi, pj = np.meshgrid(pinned, pinned, indexing="ij")
+    key = np.unique(np.concatenate([ci * n + cj, pi.ravel() * n + pj.ravel(), rows * n + cols, di.ravel().astype(np.int64) * n + dj.ravel()]))
+    key = rng.permutation(key)
+    return n, (key // n).astype(np.int32), (key % n).astype(np.int32), _vals(rng, len(key)), S.astype(np.int32)
