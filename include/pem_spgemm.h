@@ -413,6 +413,69 @@ pem_status pem_tiled_assign_device(pem_ctx *ctx, const pem_tiled *C, const pem_t
                                    int64_t nj, int accum, pem_tiled **out);
 pem_status pem_tiled_set_values_from_assign(pem_ctx *ctx, pem_tiled *t, const pem_tiled *C, const pem_tiled *A);
 
+/* Apply and scale (GraphBLAS GrB_apply and the diagonal products D*A, A*D): new values on an unchanged
+ * pattern, on the device.
+ *   pem_tiled_apply  a new tiling R of A's shape and value type, owning its arrays, that stores exactly the positions A stores with
+ *       the value f(x) of A's value x; f is op, for the binary ops bound to y = the thunk rounded once to the tiling's value type
+ *       ((float)thunk, to nearest, for fp32).
+ *   pem_tiled_scale  the same with z_ij = op(op(r_i, a_ij), c_j), evaluated left to right, op a pem_binop: PLUS, TIMES, MIN, MAX, LOR
+ *       and LAND under pem_tiled_ewise's arithmetic with alpha = beta = 1 (LOR / LAND give 1.0 / 0.0, NaN counts as != 0).  d_row holds
+ *       A.rows and d_col A.cols values of the tiling's value type, device arrays on the context's device (pem_tiled_scale for fp64
+ *       tilings, pem_tiled_scale_f32 for fp32 ones).  A null vector means that step is not performed at all (not "times 1"): with
+ *       both null R's values are A's bit for bit.  TIMES is D_r * A * D_c; PLUS is a_ij + h_i + g_j, the reweighting in front of
+ *       min_plus / max_plus products.  The vectors are read only at the indices of stored entries, never past rows - 1 / cols - 1.
+ *     Pattern.  Explicit zeros stay entries, and so do results that come out as 0, inf or NaN (the rule of pem_tiled_ewise and
+ *       pem_tiled_select): nothing is ever dropped.  An empty A gives a valid tiling with nnz = 0.  R equals the tiling
+ *       pem_tiled_from_coo builds from A's exported entries with the transformed values (every pem_tiled_info field but the two
+ *       timings, every pem_tiled_array) and works everywhere a tiling does (A, B, mask, save / load, set_values*, ewise, select,
+ *       extract, transpose, assign, mxv, spmm, sddmm, export, apply, scale).  Any tiling works as A.
+ *     Coordinates are those of the matrix the tiling represents (the matrix pem_tiled_export_csr returns): a tiling built with
+ *       transpose = 1 is its own matrix.
+ *     Arithmetic.  Everything is computed in the value type with one rounding per operation: no fma, no wider intermediate.  1 / x,
+ *       x / y and sqrt are IEEE correctly rounded in fp64 and fp32, subnormals kept.  MIN / MAX are C's fmin / fmax (a NaN side is
+ *       skipped; the sign of a zero result is not specified).  A NaN that arithmetic produces has an unspecified payload; IDENTITY,
+ *       ABS and AINV only touch the sign bit and keep payloads.  POWI: with the bits of k = 1 b_(m-1) .. b_0, p = x, then for b from
+ *       b_(m-1) down to b_0: p = p * p, and p = p * x if b is set; each product rounded once, so k = 1 copies x bit for bit and
+ *       k = 2 is x * x.  General pow, exp and log are not offered: no device implementation of them is correctly rounded.
+ *     Refusals, all checked before anything is returned (*out stays NULL, no handle changes).  PEM_E_INVALID: a null context, A or
+ *       out; an unknown op; a POWI thunk that is not an integer in 1 .. 64; the fp64 form of scale on an fp32 tiling or the reverse.
+ *       A NaN thunk is allowed, as in pem_tiled_select, and simply propagates.
+ *     A's values and the vectors are read as they are when the call is made (stream order); the call waits, and its allocations come
+ *       from the context's arena (a captured graph re-captures once).  R's structural arrays are device copies of A's.  Besides the
+ *       tiling's own arrays a scale result keeps an int32 per entry (its slot in vals_t) for its refresh.
+ *   pem_tiled_set_values_from_apply  recomputes t's vals and vals_t in place from A's current values with the op and thunk t was made
+ *       with, and bumps t's value version (plans on t turn stale until their step 3 runs, as after pem_tiled_set_values).
+ *       Stream-ordered, never waits, reads nothing back and allocates nothing, not even on the first call.
+ *   pem_tiled_set_values_from_scale  the same with the op t was made with; the vectors are given anew, and either may be null
+ *       whatever the build had.  It allocates nothing either (the build made what it needs).
+ *     Both return PEM_E_INVALID unless t was made by the matching build from exactly this A (the serial rule of
+ *       pem_tiled_set_values_from_ewise: a tiling recreated at a reused address is refused), and the scale form for the wrong value
+ *       type. */
+typedef enum {
+    /* unary: the thunk is ignored */
+    PEM_APPLY_IDENTITY = 0,  /* x, bit for bit (a copy of the tiling) */
+    PEM_APPLY_ABS = 1,       /* sign bit cleared; NaN stays NaN */
+    PEM_APPLY_AINV = 2,      /* -x (sign bit flipped) */
+    PEM_APPLY_MINV = 3,      /* 1 / x */
+    PEM_APPLY_SQRT = 4,      /* sqrt(x); x < 0 gives NaN */
+    PEM_APPLY_ONE = 5,       /* 1, whatever x is (NaN included); reads no values */
+    /* bound to y = the thunk rounded once to the tiling's value type */
+    PEM_APPLY_PLUS = 6,      /* x + y */
+    PEM_APPLY_TIMES = 7,     /* x * y */
+    PEM_APPLY_MIN = 8,       /* fmin(x, y) */
+    PEM_APPLY_MAX = 9,       /* fmax(x, y) */
+    PEM_APPLY_DIV = 10,      /* x / y */
+    PEM_APPLY_RDIV = 11,     /* y / x */
+    PEM_APPLY_RMINUS = 12,   /* y - x */
+    PEM_APPLY_POWI = 13      /* x^k, k = thunk, an integer in 1..64: the square-and-multiply chain above */
+} pem_apply_op;
+pem_status pem_tiled_apply(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out);
+pem_status pem_tiled_set_values_from_apply(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
+pem_status pem_tiled_scale(pem_ctx *ctx, const pem_tiled *A, int op, const double *d_row, const double *d_col, pem_tiled **out);
+pem_status pem_tiled_scale_f32(pem_ctx *ctx, const pem_tiled *A, int op, const float *d_row, const float *d_col, pem_tiled **out);
+pem_status pem_tiled_set_values_from_scale(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const double *d_row, const double *d_col);
+pem_status pem_tiled_set_values_from_scale_f32(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const float *d_row, const float *d_col);
+
 /* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
  * the fold of every row or column, on the device.
  *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)

@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "pem_tiled_transpose", "pem_tiled_set_values_from_transpose", "pem_tiled_extract", "pem_tiled_extract_device",
     "pem_tiled_set_values_from_extract", "pem_tiled_assign", "pem_tiled_assign_device", "pem_tiled_set_values_from_assign",
     "pem_tiled_mxv_frontier", "pem_tiled_mxv_frontier_f32", "pem_tiled_bfs", "pem_test_frontier_line_flags",
+    "pem_tiled_apply", "pem_tiled_set_values_from_apply", "pem_tiled_scale", "pem_tiled_scale_f32", "pem_tiled_set_values_from_scale",
+    "pem_tiled_set_values_from_scale_f32",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -66,6 +68,9 @@ ACCUM_NONE = -1   # PEM_ACCUM_NONE: Tiled.assign without an accum
 SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
               "value_gt", "value_ge", "abs_gt")
 POSITIONAL_SELECT_OPS = SELECT_OPS[:8]
+
+# enum pem_apply_op (include/pem_spgemm.h): Tiled.apply's ops, by value; the first six are unary
+APPLY_OPS = ("identity", "abs", "ainv", "minv", "sqrt", "one", "plus", "times", "min", "max", "div", "rdiv", "rminus", "powi")
 
 # enum pem_reduce_dim (include/pem_spgemm.h): Tiled.reduce folds every row or every column
 REDUCE_DIMS = dict(rows=0, cols=1)
@@ -347,6 +352,46 @@ class Tiled:
         """Refresh a tiling made by A.select(op, k) with a positional op from A's current values, in place.  Ordered on the context's
         stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
+
+    def apply(self, op, thunk=0):
+        """Apply: a new tiling of this one's pattern, shape and dtype whose values are op (one of APPLY_OPS)
+        of this one's -- unary (identity, abs, ainv, minv, sqrt, one), bound to the thunk rounded to the dtype (plus, times, min, max,
+        div, rdiv, rminus) or x^k for an integer k = thunk in 1..64 (powi).  Nothing is dropped: zeros, inf and NaN stay entries.
+        Waits."""
+        if op not in APPLY_OPS:
+            raise ValueError(f"unknown apply op {op!r}; one of {APPLY_OPS}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_apply(self.ctx._h, self._h, APPLY_OPS.index(op), C.c_double(float(thunk)), C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_apply(self, A):
+        """Refresh a tiling made by A.apply(op, thunk) from A's current values, in place.  Ordered on the context's stream; returns
+        without waiting and allocates nothing."""
+        _check(lib().pem_tiled_set_values_from_apply(self.ctx._h, self._h, A._h))
+
+    def _scale_vectors(self, fn, rows, cols):
+        return (None if rows is None else self._vector(fn, "rows", rows, self.rows),
+                None if cols is None else self._vector(fn, "cols", cols, self.cols))
+
+    def scale(self, rows=None, cols=None, op="times"):
+        """Scale: a new tiling of this one's pattern, shape and dtype with the values
+        op(op(rows[i], a_ij), cols[j]), op one of BINOPS -- "times" is D_r A D_c, "plus" a_ij + h_i + g_j.  rows, cols: contiguous
+        device torch tensors of the tiling's dtype with exactly self.rows / self.cols entries, or None: that step is then not
+        performed.  Waits."""
+        if op not in BINOPS:
+            raise ValueError(f"unknown scale op {op!r}; one of {sorted(BINOPS)}")
+        pr, pc = self._scale_vectors("scale", rows, cols)
+        fn = lib().pem_tiled_scale_f32 if self.value_bytes == 4 else lib().pem_tiled_scale
+        h = C.c_void_p()
+        _check(fn(self.ctx._h, self._h, BINOPS[op], pr, pc, C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_scale(self, A, rows=None, cols=None):
+        """Refresh a tiling made by A.scale(..., op) from A's current values and these vectors (either may be None, whatever the
+        build had), in place.  Ordered on the context's stream; returns without waiting and allocates nothing."""
+        pr, pc = self._scale_vectors("set_values_from_scale", rows, cols)
+        fn = lib().pem_tiled_set_values_from_scale_f32 if self.value_bytes == 4 else lib().pem_tiled_set_values_from_scale
+        _check(fn(self.ctx._h, self._h, A._h, pr, pc))
 
     def _index_list(self, name, L, dim, what="extract"):
         """one argument of extract or assign -> (kind, list, n): kind None (all), "host" (a C-contiguous int32 array) or "device" (a torch

@@ -310,9 +310,13 @@ uint64_t next_tiled_serial();
 //   ASSIGN  pem_tiled_assign (assign.hip)      src = C's and A's serials; op = accum (PEM_ACCUM_NONE or a pem_binop).  idx[0], idx[1]:
 //                                              the inverses of I and J (int32[C.rows], int32[C.cols]: p where I[p] == i, else -1;
 //                                              unallocated where the list was null).  map: as EWISE's, slots in C's and A's vals.
+//   APPLY   pem_tiled_apply (apply.hip)        src[0] = A's serial; op; p0 = thunk.  No map: the pattern is A's, so slot e of vals /
+//                                              vals_t is computed from slot e of A's vals / vals_t.
+//   SCALE   pem_tiled_scale (apply.hip)        src[0] = A's serial; op (a pem_binop).  No map: the entries are A's in A's order; the
+//                                              vectors are arguments of every refresh.  The tiling's own vmap_t is made by the build.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;

@@ -55,6 +55,9 @@ static const int add_ops[] = {PEM_BINOP_PLUS, PEM_BINOP_MIN, PEM_BINOP_MAX, PEM_
 static const char *const binop_names[] = {"plus", "times", "min", "max", "lor", "land"};                                    // by pem_binop
 static const char *const select_names[] = {"tril",     "triu",     "diag",     "offdiag",  "row_le",   "row_gt",   "col_le", "col_gt",
                                            "value_eq", "value_ne", "value_lt", "value_le", "value_gt", "value_ge", "abs_gt"};   // pem_select_op
+static const char *const apply_names[] = {"identity", "abs", "ainv", "minv", "sqrt", "one", "plus",
+                                          "times",    "min", "max",  "div",  "rdiv", "rminus", "powi"};   // pem_apply_op
+static const char *const scale_flags[2] = {"--row-scale", "--col-scale"};
 static const char *const extract_flags[2] = {"--extract-rows", "--extract-cols"};
 static const char *const assign_flags[2] = {"--assign-rows", "--assign-cols"};
 
@@ -82,6 +85,9 @@ struct Options {
     int power = 0;                                                  // --power K (0: off): see power_prologue
     const char *add_path = nullptr;                                 // --add D.mtx [--alpha x] [--beta y]: see add_stage
     double add_alpha = 1.0, add_beta = 1.0;
+    const char *apply_spec = nullptr;                               // --apply OP[:THUNK]: see apply_stage
+    const char *scale_paths[2] = {nullptr, nullptr};                // --row-scale r.mtx, --col-scale c.mtx [--scale-op OP]: see scale_stage
+    const char *scale_op_name = nullptr;
     const char *select_spec = nullptr;                              // --select OP[:THUNK]: see select_stage
     const char *extract_paths[2] = {nullptr, nullptr};              // --extract-rows I.mtx, --extract-cols J.mtx: see extract_stage
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP: see assign_stage
@@ -100,6 +106,10 @@ struct Options {
     int WARMUP = 1, REPEAT = 10;
     bool fastest = false, save = false, aat = false;
     int semiring = PEM_SEMIRING_PLUS_TIMES;
+    int apply_op = -1;
+    double apply_thunk = 0.0;
+    int scale_op = PEM_BINOP_TIMES;
+    std::vector<double> scale_vec[2];
     int select_op = -1;
     double select_thunk = 0.0;
     std::vector<int32_t> extract_idx[2], assign_idx[2];   // 0-based
@@ -122,7 +132,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--extract-rows", &o->extract_paths[0]}, {"--extract-cols", &o->extract_paths[1]}, {"--assign-into", &o->assign_into},
                   {"--assign-rows", &o->assign_paths[0]}, {"--assign-cols", &o->assign_paths[1]}, {"--assign-accum", &o->assign_accum_name},
                   {"--reduce", &o->reduce_spec}, {"--bfs", &o->bfs_spec}, {"--spmm", &o->spmm_path}, {"--sddmm", &o->sddmm_path},
-                  {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}};
+                  {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
+                  {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -163,6 +174,9 @@ static const struct ClashRule {
     {"--reduce", {"--gpus", "--power"}, ""},
     {"--bfs", {"--gpus", "--power", "--reduce", "--spmm", "--sddmm"}, ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
+    {"--apply", {"--gpus", "--power"}, ""},
+    {"--row-scale", {"--gpus", "--power"}, ""},
+    {"--col-scale", {"--gpus", "--power"}, ""},
 };
 
 // Prints the refusal and returns true when `flag` (which is present) meets something its rule refuses.
@@ -415,6 +429,55 @@ static int validate_vectors(Options *o)
     return 0;
 }
 
+// --apply: the op by name (pem_apply_op) and its thunk; --row-scale / --col-scale / --scale-op: the op by name (pem_binop) and the
+// vectors read up front, so that a bad option or file is refused before any work
+static int validate_apply(Options *o)
+{
+    if (o->apply_spec) {
+        if (clashes(*o, "--apply")) return 1;
+        const char *colon = strchr(o->apply_spec, ':');
+        const std::string name = colon ? std::string(o->apply_spec, (size_t)(colon - o->apply_spec)) : std::string(o->apply_spec);
+        o->apply_op = find_name(apply_names, 14, name);
+        if (o->apply_op < 0) {
+            printf("--apply %s: unknown op %s (identity, abs, ainv, minv, sqrt, one, plus, times, min, max, div, rdiv, rminus, powi). Exiting.\n",
+                   o->apply_spec, name.c_str());
+            return 1;
+        }
+        if (colon) {
+            char *end = nullptr;
+            o->apply_thunk = strtod(colon + 1, &end);
+            if (end == colon + 1 || *end != '\0') {
+                printf("--apply %s: the thunk %s does not parse as a number. Exiting.\n", o->apply_spec, colon + 1);
+                return 1;
+            }
+        }
+        if (o->apply_op == PEM_APPLY_POWI && !(std::floor(o->apply_thunk) == o->apply_thunk && o->apply_thunk >= 1.0 && o->apply_thunk <= 64.0)) {
+            printf("--apply %s: powi needs an integral thunk k in 1 .. 64. Exiting.\n", o->apply_spec);
+            return 1;
+        }
+    }
+    if (o->scale_op_name && !o->scale_paths[0] && !o->scale_paths[1]) {
+        printf("--scale-op needs --row-scale <r.mtx> or --col-scale <c.mtx>. Exiting.\n");
+        return 1;
+    }
+    for (int q = 0; q < 2; ++q)
+        if (o->scale_paths[q] && clashes(*o, scale_flags[q])) return 1;
+    if (o->scale_op_name && (o->scale_op = find_name(binop_names, 6, o->scale_op_name)) < 0) {
+        printf("--scale-op %s: unknown op (plus, times, min, max, lor, land). Exiting.\n", o->scale_op_name);
+        return 1;
+    }
+    for (int q = 0; q < 2; ++q) {
+        if (!o->scale_paths[q]) continue;
+        int64_t n = 0, k = 0;
+        if (read_dense_array(scale_flags[q], o->scale_paths[q], &n, &k, &o->scale_vec[q])) return 1;
+        if (k != 1) {
+            printf("%s %s: an array of %lld columns, not of one. Exiting.\n", scale_flags[q], o->scale_paths[q], (long long)k);
+            return 1;
+        }
+    }
+    return 0;
+}
+
 // Checks the options against each other and reads the files that can be refused before any work (index lists, X, Y).  Returns 0
 // to go on, else the exit code after the refusal; the order of the checks decides which refusal a command with two faults gets.
 static int validate(Options *o)
@@ -428,7 +491,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -1024,7 +1087,7 @@ struct Operands {
 struct Result {
     Tiled L_own;              // --power: A^(K-1), the last product's left operand
     pem_tiled *L = nullptr;   // A otherwise
-    Tiled sum, sel, ext, asg, sd;       // what --add, --select, --extract-*, --assign-into and --sddmm made
+    Tiled sum, app, scl, sel, ext, asg, sd;   // what --add, --apply, --row/col-scale, --select, --extract-*, --assign-into and --sddmm made
     Plan plan;
     pem_cplan_info ci;
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
@@ -1292,6 +1355,61 @@ static int add_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     return 0;
 }
 
+// `--apply OP[:THUNK]` changes the values of the final result (C, or the sum of --add) on the device
+// (pem_tiled_apply), the pattern kept: OP one of identity abs ainv minv sqrt one (THUNK ignored), plus times min max div rdiv rminus
+// (bound to THUNK) or powi (THUNK an integer k in 1..64); THUNK defaults to 0.  Every later stage sees the new tiling.  The CSV row
+// describes the product.
+static int apply_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    auto a0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    CHECK(pem_tiled_apply(ctx, src.t, o.apply_op, o.apply_thunk, out(ctx, r->app)));
+    const double app_total_ms = ms_since(a0);
+    pem_tiled_info ai;
+    CHECK(pem_tiled_get_info(r->app.get(), &ai));
+    printf("apply: %s:%g of %s: apply %.2fms, total %.2fms, nnz %lld\n", apply_names[o.apply_op], o.apply_thunk, r->last_name, ai.conv_ms, app_total_ms,
+           (long long)ai.nnz);
+    r->now_last(r->app, "the applied matrix");
+    return 0;
+}
+
+// `--row-scale r.mtx` / `--col-scale c.mtx`, either or both, with `--scale-op OP` (a binop, default
+// times): the final result R becomes op(op(r_i, R_ij), c_j) on the device (pem_tiled_scale), the pattern kept.  Each file is a
+// Matrix-Market `array real general` file of one column with R.rows resp. R.cols values (read as float with --fp32).  Every later
+// stage sees the new tiling.  The CSV row describes the product.
+static int scale_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    auto s0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    const int dims[2] = {src.info.rows, src.info.cols};
+    DevBuf dv[2];
+    for (int q = 0; q < 2; ++q) {
+        if (!o.scale_paths[q]) continue;
+        if ((long long)o.scale_vec[q].size() != dims[q]) {
+            printf("%s %s: the vector has %zu values; the result has %d %s. Exiting.\n", scale_flags[q], o.scale_paths[q], o.scale_vec[q].size(), dims[q],
+                   q ? "columns" : "rows");
+            return 1;
+        }
+        if (!dv[q].upload(o.scale_vec[q], o.scale_vec[q].size(), o.fp32)) {
+            fprintf(stderr, "pemspgemm: %s: device allocation failed\n", scale_flags[q]);
+            return 2;
+        }
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    CHECK(o.fp32 ? pem_tiled_scale_f32(ctx, src.t, o.scale_op, (const float *)dv[0].p, (const float *)dv[1].p, out(ctx, r->scl))
+                 : pem_tiled_scale(ctx, src.t, o.scale_op, (const double *)dv[0].p, (const double *)dv[1].p, out(ctx, r->scl)));
+    const double scl_total_ms = ms_since(s0);
+    pem_tiled_info si;
+    CHECK(pem_tiled_get_info(r->scl.get(), &si));
+    printf("scale: %s of %s by %s%s%s: scale %.2fms, total %.2fms, nnz %lld\n", binop_names[o.scale_op], r->last_name, o.scale_paths[0] ? "rows" : "",
+           o.scale_paths[0] && o.scale_paths[1] ? " and " : "", o.scale_paths[1] ? "columns" : "", si.conv_ms, scl_total_ms, (long long)si.nnz);
+    r->now_last(r->scl, "the scaled matrix");
+    return 0;
+}
+
 // `--select OP[:THUNK]` keeps the entries of the final result (C, or the sum of --add) that satisfy
 // OP, one of tril triu diag offdiag row_le row_gt col_le col_gt (THUNK an integer k) or value_eq value_ne value_lt value_le
 // value_gt value_ge abs_gt (THUNK a value); THUNK defaults to 0.  The result becomes a tiling (pem_tiled_from_cplan, or the
@@ -1533,6 +1651,10 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
 {
     const char *const semiring = semiring_names[o.semiring];
     std::string how;   // of a matrix: what --select, --extract-* and --assign-into did to it
+    if (r->app) how += std::string(", apply ") + o.apply_spec;
+    if (r->scl)
+        how += std::string(", scale ") + binop_names[o.scale_op] + (o.scale_paths[0] ? std::string(" rows ") + o.scale_paths[0] : std::string()) +
+               (o.scale_paths[1] ? std::string(" columns ") + o.scale_paths[1] : std::string());
     if (r->sel) how += std::string(r->sd ? ", C after select " : ", select ") + o.select_spec;
     if (r->ext)
         how += std::string(", extract ") + (o.extract_paths[0] ? std::string("rows ") + o.extract_paths[0] : std::string()) +
@@ -1588,6 +1710,8 @@ int main(int argc, char *argv[])
     if (!rc) rc = power_prologue(o, ctx, &in, &r);
     if (!rc) rc = timed_product(o, ctx, in, &r);
     if (!rc && in.Dt) rc = add_stage(o, ctx, in, &r);
+    if (!rc && o.apply_op >= 0) rc = apply_stage(o, ctx, &r);
+    if (!rc && (o.scale_paths[0] || o.scale_paths[1])) rc = scale_stage(o, ctx, &r);
     if (!rc && o.select_op >= 0) rc = select_stage(o, ctx, &r);
     if (!rc && (o.extract_paths[0] || o.extract_paths[1])) rc = extract_stage(o, ctx, &r);
     if (!rc && in.Into) rc = assign_stage(o, ctx, in, &r);
