@@ -476,6 +476,32 @@ pem_status pem_tiled_scale_f32(pem_ctx *ctx, const pem_tiled *A, int op, const f
 pem_status pem_tiled_set_values_from_scale(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const double *d_row, const double *d_col);
 pem_status pem_tiled_set_values_from_scale_f32(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const float *d_row, const float *d_col);
 
+/* Kronecker product (GraphBLAS GrB_kronecker): R = A (x) B under a binary op, on the device.
+ *   pem_tiled_kron  a new tiling R, owning its arrays, of A.rows * B.rows rows, A.cols * B.cols columns and A's value type.  A and B
+ *       must have the same value type; they may be the same handle, and either may be any tiling (converted, loaded, transpose-built,
+ *       derived -- another pem_tiled_kron result included).
+ *     Pattern.  Position (i * B.rows + k, j * B.cols + l) is stored exactly where A stores (i, j) and B stores (k, l), so
+ *       nnz(R) = nnz(A) * nnz(B).  Explicit zeros and results that come out as 0 stay entries (the rule of sections 3f / 3g); tiles
+ *       without entries are not in R (1..256 entries per tile).  An empty operand gives a valid tiling with nnz = 0.
+ *     Values.  op(a, b) in the value type, rounded once, no fma and no wider intermediate; op is a pem_binop with exactly
+ *       pem_tiled_ewise's both-stored arithmetic (alpha = beta = 1).  PEM_BINOP_TIMES is the Kronecker product proper; PLUS, MIN, MAX,
+ *       LOR and LAND are GraphBLAS's kronecker with a binary op.  For MIN / MAX a NaN side is skipped and the sign of a zero result is
+ *       not specified; a NaN that arithmetic produces has an unspecified payload.
+ *     R equals the tiling pem_tiled_from_coo builds from those entries (every pem_tiled_info field but the two timings, every
+ *       pem_tiled_array) and works everywhere a tiling does (A, B, mask, save / load, set_values*, flop count, split, ewise, select,
+ *       extract, transpose, assign, apply, scale, mxv, spmm, sddmm, export, kron).
+ *     Refusals, all before anything is launched or allocated unless noted.  PEM_E_INVALID: a null argument, an unknown op, different
+ *       value types.  PEM_E_OVERFLOW: A.rows * B.rows or A.cols * B.cols exceeds INT32_MAX, or nnz(A) * nnz(B) does not fit an int32
+ *       (all three computed in 64 bits on the host); and, after the tile stage has run, a tile count beyond the int32 range.
+ *     A's and B's values are read as they are when the call is made (stream order); the call waits, and its allocations come from the
+ *       context's arena (a captured graph re-captures once).  No entry is sorted: the only sort is over the result's candidate tiles.
+ *   pem_tiled_set_values_from_kron  recomputes t's values (vals and vals_t) in place from the current values of A and B with the op t
+ *       was made with, and bumps t's value version.  Stream-ordered, never waits, reads nothing back; only the first call allocates
+ *       (an int32 pair per entry: where its operand values sit in A and in B).  PEM_E_INVALID unless t was made by pem_tiled_kron from
+ *       exactly this A and this B in this order (the serial rule of pem_tiled_set_values_from_ewise). */
+pem_status pem_tiled_kron(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled **out);
+pem_status pem_tiled_set_values_from_kron(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B);
+
 /* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
  * the fold of every row or column, on the device.
  *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)

@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_from_extract", "pem_tiled_assign", "pem_tiled_assign_device", "pem_tiled_set_values_from_assign",
     "pem_tiled_mxv_frontier", "pem_tiled_mxv_frontier_f32", "pem_tiled_bfs", "pem_test_frontier_line_flags",
     "pem_tiled_apply", "pem_tiled_set_values_from_apply", "pem_tiled_scale", "pem_tiled_scale_f32", "pem_tiled_set_values_from_scale",
-    "pem_tiled_set_values_from_scale_f32",
+    "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -337,6 +337,22 @@ class Tiled:
         """Refresh a tiling made by ewise(A, B, ...) from A's and B's current values, in place.  Ordered on the context's stream;
         returns without waiting."""
         _check(lib().pem_tiled_set_values_from_ewise(self.ctx._h, self._h, A._h, B._h))
+
+    @classmethod
+    def kron(cls, A, B, op="times"):
+        """Kronecker product: a new tiling of A.rows * B.rows by A.cols * B.cols in A's dtype that stores
+        (i * B.rows + k, j * B.cols + l) with the value op(a_ij, b_kl) wherever A stores (i, j) and B stores (k, l).  op: one of BINOPS
+        ("times" is the Kronecker product proper).  A and B may be the same tiling.  Waits."""
+        if op not in BINOPS:
+            raise ValueError(f"unknown op {op!r}; one of {sorted(BINOPS)}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_kron(A.ctx._h, A._h, B._h, BINOPS[op], C.byref(h)))
+        return cls(A.ctx, h)
+
+    def set_values_from_kron(self, A, B):
+        """Refresh a tiling made by kron(A, B, ...) from A's and B's current values, in place.  Ordered on the context's stream;
+        returns without waiting."""
+        _check(lib().pem_tiled_set_values_from_kron(self.ctx._h, self._h, A._h, B._h))
 
     def select(self, op, thunk=0):
         """Select: a new tiling of this one's shape and dtype holding exactly the stored entries that satisfy

@@ -314,9 +314,11 @@ uint64_t next_tiled_serial();
 //                                              vals_t is computed from slot e of A's vals / vals_t.
 //   SCALE   pem_tiled_scale (apply.hip)        src[0] = A's serial; op (a pem_binop).  No map: the entries are A's in A's order; the
 //                                              vectors are arguments of every refresh.  The tiling's own vmap_t is made by the build.
+//   KRON    pem_tiled_kron (kron.hip)          src = A's and B's serials; op (a pem_binop).  map: as EWISE's, slots in A's and B's vals
+//                                              (both always stored).
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;

@@ -92,6 +92,7 @@ struct Options {
     const char *extract_paths[2] = {nullptr, nullptr};              // --extract-rows I.mtx, --extract-cols J.mtx: see extract_stage
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP: see assign_stage
     const char *assign_paths[2] = {nullptr, nullptr};               // --assign-rows I.mtx, --assign-cols J.mtx
+    const char *kron_path = nullptr, *kron_op_name = nullptr;       // --kron K.mtx [--kron-op OP]: see kron_stage
     const char *reduce_spec = nullptr;                              // --reduce rows|cols[:OP]: see reduce_stage
     const char *bfs_spec = nullptr;                                 // --bfs SRC: see bfs_stage
     const char *spmm_path = nullptr;                                // --spmm X.mtx: see spmm_stage
@@ -114,6 +115,7 @@ struct Options {
     double select_thunk = 0.0;
     std::vector<int32_t> extract_idx[2], assign_idx[2];   // 0-based
     int assign_accum = PEM_ACCUM_NONE;
+    int kron_op = PEM_BINOP_TIMES;
     int64_t spmm_rows = 0, spmm_k = 0, sddmm_xrows = 0, sddmm_yrows = 0, sddmm_k = 0;
     std::vector<double> spmm_x, sddmm_x, sddmm_y;         // row-major
     int reduce_dim = -1, reduce_op = -1;
@@ -133,7 +135,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--assign-rows", &o->assign_paths[0]}, {"--assign-cols", &o->assign_paths[1]}, {"--assign-accum", &o->assign_accum_name},
                   {"--reduce", &o->reduce_spec}, {"--bfs", &o->bfs_spec}, {"--spmm", &o->spmm_path}, {"--sddmm", &o->sddmm_path},
                   {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
-                  {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name}};
+                  {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
+                  {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -177,6 +180,7 @@ static const struct ClashRule {
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
     {"--col-scale", {"--gpus", "--power"}, ""},
+    {"--kron", {"--gpus"}, ""},
 };
 
 // Prints the refusal and returns true when `flag` (which is present) meets something its rule refuses.
@@ -478,6 +482,21 @@ static int validate_apply(Options *o)
     return 0;
 }
 
+// --kron / --kron-op: the op by name (pem_binop); K itself is read with the operands
+static int validate_kron(Options *o)
+{
+    if (!o->kron_path) {
+        if (o->kron_op_name) printf("--kron-op needs --kron <K.mtx>. Exiting.\n");
+        return o->kron_op_name ? 1 : 0;
+    }
+    if (clashes(*o, "--kron")) return 1;
+    if (o->kron_op_name && (o->kron_op = find_name(binop_names, 6, o->kron_op_name)) < 0) {
+        printf("--kron-op %s: unknown op (plus, times, min, max, lor, land). Exiting.\n", o->kron_op_name);
+        return 1;
+    }
+    return 0;
+}
+
 // Checks the options against each other and reads the files that can be refused before any work (index lists, X, Y).  Returns 0
 // to go on, else the exit code after the refusal; the order of the checks decides which refusal a command with two faults gets.
 static int validate(Options *o)
@@ -491,7 +510,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -1078,7 +1097,7 @@ static int run_gpus(const Options &o)
 // The single-device path: the operands, then one function per stage, each leaving what it made in Result.
 // ------------------------------------------------------------------------------------------------------------------
 struct Operands {
-    Tiled A, B_own, Mt, Dt, Into;   // B_own: B when it is a tiling of its own; Mt the mask, Dt --add's D, Into --assign-into's D
+    Tiled A, B_own, Mt, Dt, Into, Kt;   // B_own: B when it is a tiling of its own; Mt the mask, Dt --add's D, Into --assign-into's D, Kt --kron's K
     pem_tiled *B = nullptr;
     pem_tiled_info ia, ib;
     double conv_ms = 0.0;
@@ -1087,7 +1106,7 @@ struct Operands {
 struct Result {
     Tiled L_own;              // --power: A^(K-1), the last product's left operand
     pem_tiled *L = nullptr;   // A otherwise
-    Tiled sum, app, scl, sel, ext, asg, sd;   // what --add, --apply, --row/col-scale, --select, --extract-*, --assign-into and --sddmm made
+    Tiled sum, app, scl, sel, ext, asg, krn, sd;   // what --add, --apply, --row/col-scale, --select, --extract-*, --assign-into, --kron and --sddmm made
     Plan plan;
     pem_cplan_info ci;
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
@@ -1163,7 +1182,7 @@ static int make_tiling(const Options &o, pem_ctx *ctx, Source &src, int transpos
     return 0;
 }
 
-// A, B, the mask and the D of --add and of --assign-into, the header lines, and the conversion time
+// A, B, the mask, the D of --add and of --assign-into and the K of --kron, the header lines, and the conversion time
 static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
 {
     auto conv_start = Clock::now();   // spgemm.cu:760: the clock starts before the file is read
@@ -1185,7 +1204,7 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
             printf("input is rectangular. Only AAt is possible. Exiting.\n");   // spgemm.cu:782-786
         return 1;
     }
-    Coo cm, cd, cinto;
+    Coo cm, cd, cinto, ck;
     if (o.mask_path) {   // M's structure (its values are never read, so it is converted as fp64 whatever --fp32 says)
         if (read_input(o, o.mask_path, &cm) != 0) return 1;
         if (cm.rows != ia.rows || cm.cols != ib.cols) {
@@ -1207,6 +1226,10 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
         const int dims[2] = {cinto.rows, cinto.cols};
         if (!lists_in_range(assign_flags, o.assign_paths, o.assign_idx, dims, o.assign_into)) return 1;
         if (int rc = convert_or_refuse(ctx, o.assign_into, cinto, o.fp32, 0, &in->Into)) return rc;
+    }
+    if (o.kron_path) {   // K, in the value type of A
+        if (read_input(o, o.kron_path, &ck) != 0) return 1;
+        if (int rc = convert_or_refuse(ctx, o.kron_path, ck, o.fp32, 0, &in->Kt)) return rc;
     }
     if (o.fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", o.input(), ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
@@ -1488,6 +1511,33 @@ static int assign_stage(const Options &o, pem_ctx *ctx, const Operands &in, Resu
     return 0;
 }
 
+// `--kron K.mtx [--kron-op OP]`: after the product and every stage above, the final result R becomes
+// R (x) K on the device (pem_tiled_kron): R.rows * K.rows by R.cols * K.cols, entry (i * K.rows + k, j * K.cols + l) = OP(r_ij, k_kl)
+// with OP one of plus times min max lor land (default times, the Kronecker product proper).  K is read with --fp32 like A.
+// --reduce, --bfs, --spmm, --sddmm, --out and the sorted COO files then see that tiling.  A result whose dimensions or entries leave
+// the int32 range is refused with the library's message.  The CSV row describes the product.
+static int kron_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
+{
+    auto k0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_status s = pem_tiled_kron(ctx, src.t, in.Kt.get(), o.kron_op, out(ctx, r->krn));
+    if (s == PEM_E_OVERFLOW) {
+        printf("--kron %s: %s. Exiting.\n", o.kron_path, pem_last_error());
+        return 1;
+    }
+    CHECK(s);
+    const double krn_total_ms = ms_since(k0);
+    pem_tiled_info ki, kk;
+    CHECK(pem_tiled_get_info(r->krn.get(), &ki));
+    CHECK(pem_tiled_get_info(in.Kt.get(), &kk));
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    printf("kron: %s (x) %s under %s: kron %.2fms, total %.2fms, %d x %d, nnz %lld (the result %lld, K %lld)\n", r->last_name, o.kron_path,
+           binop_names[o.kron_op], ki.conv_ms, krn_total_ms, ki.rows, ki.cols, (long long)ki.nnz, (long long)src.info.nnz, (long long)kk.nnz);
+    r->now_last(r->krn, "the Kronecker product");
+    return 0;
+}
+
 // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
 // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
 // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
@@ -1621,17 +1671,17 @@ static int sddmm_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// The sorted COO files of the 2nd argument: the sampled product's or the assigned matrix's entries when there is one (their CSR
-// export is the sorted (row, column) order), else the plan's C as the reference writes it.
+// The sorted COO files of the 2nd argument: the sampled product's, the Kronecker product's or the assigned matrix's entries when
+// there is one (their CSR export is the sorted (row, column) order), else the plan's C as the reference writes it.
 static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
 {
     if (!o.save) {
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
     } else if (r->sd) {
         r->rc = save_result_files(r->sd_csr.rp, r->sd_csr.ci, r->sd_csr.v);
-    } else if (r->asg) {
+    } else if (r->krn || r->asg) {
         Csr c;
-        CHECK(export_csr(ctx, r->asg.get(), o.fp32, &c));
+        CHECK(export_csr(ctx, r->krn ? r->krn.get() : r->asg.get(), o.fp32, &c));
         r->rc = save_result_files(c.rp, c.ci, c.v);
     } else {
         Csr c;   // as COO
@@ -1663,6 +1713,7 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
         how += std::string(", assigned into ") + o.assign_into + (o.assign_paths[0] ? std::string(" rows ") + o.assign_paths[0] : std::string()) +
                (o.assign_paths[1] ? std::string(" columns ") + o.assign_paths[1] : std::string()) +
                (o.assign_accum == PEM_ACCUM_NONE ? std::string() : std::string(" accum ") + binop_names[o.assign_accum]);
+    if (r->krn) how += std::string(", kron ") + binop_names[o.kron_op] + " with " + o.kron_path;
     how += " by pemspgemm (pem-spgemm_amd)";
     int rc = 0;
     if (o.bfs_spec) {
@@ -1715,6 +1766,7 @@ int main(int argc, char *argv[])
     if (!rc && o.select_op >= 0) rc = select_stage(o, ctx, &r);
     if (!rc && (o.extract_paths[0] || o.extract_paths[1])) rc = extract_stage(o, ctx, &r);
     if (!rc && in.Into) rc = assign_stage(o, ctx, in, &r);
+    if (!rc && in.Kt) rc = kron_stage(o, ctx, in, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
