@@ -334,6 +334,34 @@ typedef enum {
 pem_status pem_tiled_select(pem_ctx *ctx, const pem_tiled *A, int op, double thunk, pem_tiled **out);
 pem_status pem_tiled_set_values_from_select(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A);
 
+/* Select top-k: the first k entries of every row or column of a tiling in rank order, on the device.
+ *   pem_tiled_select_topk  a new tiling R of A's shape and value type, owning its arrays, holding of every line of A the first
+ *       min(k, entries of the line) entries in the line's rank order and nothing else; values are copied bit for bit.  dim is a
+ *       pem_reduce_dim: PEM_REDUCE_ROWS, a line is a matrix row and the index inside it is the column; PEM_REDUCE_COLS, a line is a
+ *       matrix column and the index inside it is the row.  Untyped, like pem_tiled_select: one entry point serves fp64 and fp32.
+ *     Rank order of a line.
+ *       1. Entries whose value is not a NaN come before entries whose value is a NaN, under all three orders.
+ *       2. Among numbers, PEM_TOPK_LARGEST ranks by x descending, PEM_TOPK_SMALLEST by x ascending, PEM_TOPK_ABS_LARGEST by |x|
+ *          descending.  Comparisons are IEEE in the tiling's value type: -0.0 and 0.0 are equal, subnormals are compared as they
+ *          are (no flush), +-inf are ordinary extremes.
+ *       3. Equal entries, and NaNs among themselves, rank by ascending index inside the line: the lower column for rows, the lower
+ *          row for columns.
+ *       This is a total order, so the result is unique: every line of R has exactly min(k, n_line) entries, two calls give identical
+ *       arrays, no NaN is kept while a number of the same line is dropped, and a NaN is kept only to fill a line that has fewer
+ *       than k numbers.
+ *     Coordinates are those of the matrix the tiling represents (the matrix pem_tiled_export_csr returns): a tiling built with
+ *       transpose = 1 is its own matrix.
+ *     k = 0 gives a valid tiling with nnz = 0; k at or above the longest line gives A's arrays again; an empty A gives an empty R.
+ *       Tiles left without entries are not in R.  R equals the tiling pem_tiled_from_coo builds from the kept triples (every
+ *       pem_tiled_info field but the two timings, every pem_tiled_array) and works everywhere a tiling does.
+ *     PEM_E_INVALID, before anything is launched or allocated (*out stays NULL): a null context, A or out; an unknown order or dim;
+ *       k < 0.  A's values are read as they are when the call is made (stream order); the call waits, and its allocations come from
+ *       the context's arena.  With dim = PEM_REDUCE_COLS the first call on a tiling may build the column schedule of pem_tiled_mxv,
+ *       which stays with the tiling.
+ *     No refresh: the pattern depends on the values, so select again; pem_tiled_set_values_from_select refuses R. */
+typedef enum { PEM_TOPK_LARGEST = 0, PEM_TOPK_SMALLEST = 1, PEM_TOPK_ABS_LARGEST = 2 } pem_topk_order;
+pem_status pem_tiled_select_topk(pem_ctx *ctx, const pem_tiled *A, int order, int dim, int64_t k, pem_tiled **out);
+
 /* Extract and transpose (GraphBLAS GrB_extract / GrB_transpose): the operations that re-index a tiling, on
  * the device.  None is typed: values are only copied, so one entry point serves fp64 and fp32 tilings, as pem_tiled_select does.
  *   pem_tiled_extract  a new tiling R = A(I, J) of ni x nj and A's value type, owning its arrays: R stores (p, q) exactly where A

@@ -7,6 +7,7 @@ compute entry point raises.  The directory name carries a hyphen (it mirrors the
 repo's name), so import it through `__graft_entry__.load_package()`.
 """
 import ctypes as C
+import numbers
 import os
 import subprocess
 
@@ -56,7 +57,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_from_extract", "pem_tiled_assign", "pem_tiled_assign_device", "pem_tiled_set_values_from_assign",
     "pem_tiled_mxv_frontier", "pem_tiled_mxv_frontier_f32", "pem_tiled_bfs", "pem_test_frontier_line_flags",
     "pem_tiled_apply", "pem_tiled_set_values_from_apply", "pem_tiled_scale", "pem_tiled_scale_f32", "pem_tiled_set_values_from_scale",
-    "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron",
+    "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron", "pem_tiled_select_topk",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -68,6 +69,9 @@ ACCUM_NONE = -1   # PEM_ACCUM_NONE: Tiled.assign without an accum
 SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
               "value_gt", "value_ge", "abs_gt")
 POSITIONAL_SELECT_OPS = SELECT_OPS[:8]
+
+# enum pem_topk_order (include/pem_spgemm.h): Tiled.select_topk's rank orders, by value
+TOPK_ORDERS = ("largest", "smallest", "abs_largest")
 
 # enum pem_apply_op (include/pem_spgemm.h): Tiled.apply's ops, by value; the first six are unary
 APPLY_OPS = ("identity", "abs", "ainv", "minv", "sqrt", "one", "plus", "times", "min", "max", "div", "rdiv", "rminus", "powi")
@@ -368,6 +372,20 @@ class Tiled:
         """Refresh a tiling made by A.select(op, k) with a positional op from A's current values, in place.  Ordered on the context's
         stream; returns without waiting."""
         _check(lib().pem_tiled_set_values_from_select(self.ctx._h, self._h, A._h))
+
+    def select_topk(self, k, order="largest", dim="rows"):
+        """Select top-k: a new tiling of this one's shape and dtype holding, of every row (dim "rows") or
+        column ("cols"), the first min(k, entries of the line) entries in rank order -- order one of TOPK_ORDERS; NaNs rank last, equal
+        entries by ascending index inside the line.  Values are copied bit for bit.  Waits.  There is no refresh: select again."""
+        if order not in TOPK_ORDERS:
+            raise ValueError(f"unknown top-k order {order!r}; one of {TOPK_ORDERS}")
+        if dim not in REDUCE_DIMS:
+            raise ValueError(f"unknown dim {dim!r}; one of {sorted(REDUCE_DIMS)}")
+        if isinstance(k, bool) or not isinstance(k, numbers.Real) or k != k or k < 0 or k >= 2 ** 63 or int(k) != k:
+            raise ValueError(f"k must be an integer >= 0 (below 2^63), not {k!r}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_select_topk(self.ctx._h, self._h, TOPK_ORDERS.index(order), REDUCE_DIMS[dim], C.c_int64(int(k)), C.byref(h)))
+        return Tiled(self.ctx, h)
 
     def apply(self, op, thunk=0):
         """Apply: a new tiling of this one's pattern, shape and dtype whose values are op (one of APPLY_OPS)

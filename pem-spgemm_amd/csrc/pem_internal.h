@@ -316,9 +316,11 @@ uint64_t next_tiled_serial();
 //                                              vectors are arguments of every refresh.  The tiling's own vmap_t is made by the build.
 //   KRON    pem_tiled_kron (kron.hip)          src = A's and B's serials; op (a pem_binop).  map: as EWISE's, slots in A's and B's vals
 //                                              (both always stored).
+//   TOPK    pem_tiled_select_topk (topk.hip)   src[0] = A's serial; op = order; pattern = dim; p0 = k.  src_tiles as SELECT's.  No
+//                                              refresh: the pattern depends on A's values.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;

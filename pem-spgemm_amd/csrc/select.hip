@@ -340,6 +340,12 @@ pem_status pem::drop_region(pem_ctx *ctx, const pem_tiled *C, const uint16_t *ro
     return C->value_bytes == 4 ? region_build<float>(ctx, C, rowbits, colbits, R, fn) : region_build<double>(ctx, C, rowbits, colbits, R, fn);
 }
 
+pem_status pem::select_by_masks(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, const char *fn,
+                                const std::function<void(uint32_t *, int *, int *)> &masks)
+{
+    return A->value_bytes == 4 ? select_route<float>(ctx, A, R, fn, masks) : select_route<double>(ctx, A, R, fn, masks);
+}
+
 static bool select_args_ok(int op, double thunk, const char *fn)
 {
     if (op < PEM_SELECT_TRIL || op > PEM_SELECT_ABS_GT) {

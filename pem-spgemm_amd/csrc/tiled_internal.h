@@ -1,10 +1,11 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.
 #pragma once
 #include "pem_internal.h"
 #include <chrono>
+#include <functional>
 #include <memory>
 
 namespace pem {
@@ -45,6 +46,11 @@ pem_status scatter_tiling(pem_ctx *ctx, const pem_tiled *A, const int *inv_i, in
 // R = C without its entries in the region: select's positional route with the predicate "not (row in I and column in J)"
 // (select.hip).  rowbits[P] / colbits[Q]: bit r set where row 16P + r / column 16Q + r is in the list (null: every one is).
 pem_status drop_region(pem_ctx *ctx, const pem_tiled *C, const uint16_t *rowbits, const uint16_t *colbits, pem_tiled *R, const char *fn);
+// R = the entries of A that a mask stage keeps: select's route around any kernel that writes, per A tile, the new row masks
+// (nm: uint32[8T], word q = row 2q | row 2q+1 << 16), the kept count (roff) and a non-empty flag (rid) (select.hip; topk.hip).
+// The caller sets R's provenance.  Synchronises.
+pem_status select_by_masks(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, const char *fn,
+                           const std::function<void(uint32_t *nm, int *roff, int *rid)> &masks);
 // R = op(A, B) over the union of the patterns, alpha = beta = 1: pem_tiled_ewise's build under the caller's name (ewise.hip).
 // R's provenance is ewise's; the caller may replace it.
 pem_status union_tiling(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled *R, const char *fn);

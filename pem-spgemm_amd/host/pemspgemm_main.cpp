@@ -12,6 +12,7 @@
 #include <atomic>
 #include <chrono>
 #include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <condition_variable>
 #include <memory>
@@ -57,6 +58,8 @@ static const char *const select_names[] = {"tril",     "triu",     "diag",     "
                                            "value_eq", "value_ne", "value_lt", "value_le", "value_gt", "value_ge", "abs_gt"};   // pem_select_op
 static const char *const apply_names[] = {"identity", "abs", "ainv", "minv", "sqrt", "one", "plus",
                                           "times",    "min", "max",  "div",  "rdiv", "rminus", "powi"};   // pem_apply_op
+static const char *const topk_names[] = {"largest", "smallest", "abs_largest"};   // pem_topk_order
+static const char *const dim_names[] = {"rows", "cols"};                           // pem_reduce_dim
 static const char *const scale_flags[2] = {"--row-scale", "--col-scale"};
 static const char *const extract_flags[2] = {"--extract-rows", "--extract-cols"};
 static const char *const assign_flags[2] = {"--assign-rows", "--assign-cols"};
@@ -89,6 +92,7 @@ struct Options {
     const char *scale_paths[2] = {nullptr, nullptr};                // --row-scale r.mtx, --col-scale c.mtx [--scale-op OP]: see scale_stage
     const char *scale_op_name = nullptr;
     const char *select_spec = nullptr;                              // --select OP[:THUNK]: see select_stage
+    const char *topk_spec = nullptr;                                // --topk DIM:ORDER:K: see topk_stage
     const char *extract_paths[2] = {nullptr, nullptr};              // --extract-rows I.mtx, --extract-cols J.mtx: see extract_stage
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP: see assign_stage
     const char *assign_paths[2] = {nullptr, nullptr};               // --assign-rows I.mtx, --assign-cols J.mtx
@@ -113,6 +117,8 @@ struct Options {
     std::vector<double> scale_vec[2];
     int select_op = -1;
     double select_thunk = 0.0;
+    int topk_dim = -1, topk_order = -1;
+    long long topk_k = 0;
     std::vector<int32_t> extract_idx[2], assign_idx[2];   // 0-based
     int assign_accum = PEM_ACCUM_NONE;
     int kron_op = PEM_BINOP_TIMES;
@@ -136,7 +142,7 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--reduce", &o->reduce_spec}, {"--bfs", &o->bfs_spec}, {"--spmm", &o->spmm_path}, {"--sddmm", &o->sddmm_path},
                   {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
-                  {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}};
+                  {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -181,6 +187,7 @@ static const struct ClashRule {
     {"--row-scale", {"--gpus", "--power"}, ""},
     {"--col-scale", {"--gpus", "--power"}, ""},
     {"--kron", {"--gpus"}, ""},
+    {"--topk", {"--gpus", "--power"}, ""},
 };
 
 // Prints the refusal and returns true when `flag` (which is present) meets something its rule refuses.
@@ -497,6 +504,33 @@ static int validate_kron(Options *o)
     return 0;
 }
 
+// --topk DIM:ORDER:K: the dimension (pem_reduce_dim) and the order (pem_topk_order) by name, K an integer >= 0
+static int validate_topk(Options *o)
+{
+    if (!o->topk_spec) return 0;
+    if (clashes(*o, "--topk")) return 1;
+    const std::string spec = o->topk_spec;
+    const size_t c1 = spec.find(':'), c2 = c1 == std::string::npos ? c1 : spec.find(':', c1 + 1);
+    const std::string dim = spec.substr(0, c1), order = c1 == std::string::npos ? std::string() : spec.substr(c1 + 1, c2 - c1 - 1),
+                      kstr = c2 == std::string::npos ? std::string() : spec.substr(c2 + 1);
+    if ((o->topk_dim = find_name(dim_names, 2, dim)) < 0) {
+        printf("--topk %s: unknown dimension %s (rows, cols); the form is DIM:ORDER:K. Exiting.\n", o->topk_spec, dim.c_str());
+        return 1;
+    }
+    if ((o->topk_order = find_name(topk_names, 3, order)) < 0) {
+        printf("--topk %s: unknown order %s (largest, smallest, abs_largest); the form is DIM:ORDER:K. Exiting.\n", o->topk_spec, order.c_str());
+        return 1;
+    }
+    char *end = nullptr;
+    errno = 0;
+    o->topk_k = strtoll(kstr.c_str(), &end, 10);
+    if (kstr.empty() || !isdigit((unsigned char)kstr[0]) || *end != '\0' || errno != 0) {
+        printf("--topk %s: K must be an integer >= 0, not %s. Exiting.\n", o->topk_spec, kstr.c_str());
+        return 1;
+    }
+    return 0;
+}
+
 // Checks the options against each other and reads the files that can be refused before any work (index lists, X, Y).  Returns 0
 // to go on, else the exit code after the refusal; the order of the checks decides which refusal a command with two faults gets.
 static int validate(Options *o)
@@ -510,7 +544,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -1106,7 +1140,7 @@ struct Operands {
 struct Result {
     Tiled L_own;              // --power: A^(K-1), the last product's left operand
     pem_tiled *L = nullptr;   // A otherwise
-    Tiled sum, app, scl, sel, ext, asg, krn, sd;   // what --add, --apply, --row/col-scale, --select, --extract-*, --assign-into, --kron and --sddmm made
+    Tiled sum, app, scl, sel, top, ext, asg, krn, sd;   // what --add, --apply, --row/col-scale, --select, --topk, --extract-*, --assign-into, --kron and --sddmm made
     Plan plan;
     pem_cplan_info ci;
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
@@ -1453,6 +1487,26 @@ static int select_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--topk DIM:ORDER:K` keeps, of every row (DIM rows) or column (cols) of the final result (C, the sum
+// of --add, what --apply / --row/col-scale changed or --select kept), the first K entries in rank order: ORDER one of largest
+// smallest abs_largest, NaNs last, ties by ascending index (pem_tiled_select_topk).  Every later stage sees the new tiling.  The
+// CSV row describes the product.
+static int topk_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    auto s0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    CHECK(pem_tiled_select_topk(ctx, src.t, o.topk_order, o.topk_dim, (int64_t)o.topk_k, out(ctx, r->top)));
+    const double top_total_ms = ms_since(s0);
+    pem_tiled_info ti;
+    CHECK(pem_tiled_get_info(r->top.get(), &ti));
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    printf("topk: %s:%s:%lld of %s: topk %.2fms, total %.2fms, nnz %lld of %lld kept\n", dim_names[o.topk_dim], topk_names[o.topk_order], o.topk_k,
+           r->last_name, ti.conv_ms, top_total_ms, (long long)ti.nnz, (long long)src.info.nnz);
+    r->now_last(r->top, "the top-k selection");
+    return 0;
+}
+
 // `--extract-rows I.mtx` / `--extract-cols J.mtx`, either or both: the final result R (C, the sum of
 // --add, or what --select kept) becomes R(I, J) on the device (pem_tiled_extract).  Each file is a Matrix-Market `array` file of
 // one column holding 1-based indices (`integer`, or `real` with integral values), in any order, repeats allowed.  --reduce,
@@ -1706,6 +1760,7 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
         how += std::string(", scale ") + binop_names[o.scale_op] + (o.scale_paths[0] ? std::string(" rows ") + o.scale_paths[0] : std::string()) +
                (o.scale_paths[1] ? std::string(" columns ") + o.scale_paths[1] : std::string());
     if (r->sel) how += std::string(r->sd ? ", C after select " : ", select ") + o.select_spec;
+    if (r->top) how += std::string(", topk ") + o.topk_spec;
     if (r->ext)
         how += std::string(", extract ") + (o.extract_paths[0] ? std::string("rows ") + o.extract_paths[0] : std::string()) +
                (o.extract_paths[0] && o.extract_paths[1] ? ", " : "") + (o.extract_paths[1] ? std::string("columns ") + o.extract_paths[1] : std::string());
@@ -1764,6 +1819,7 @@ int main(int argc, char *argv[])
     if (!rc && o.apply_op >= 0) rc = apply_stage(o, ctx, &r);
     if (!rc && (o.scale_paths[0] || o.scale_paths[1])) rc = scale_stage(o, ctx, &r);
     if (!rc && o.select_op >= 0) rc = select_stage(o, ctx, &r);
+    if (!rc && o.topk_order >= 0) rc = topk_stage(o, ctx, &r);
     if (!rc && (o.extract_paths[0] || o.extract_paths[1])) rc = extract_stage(o, ctx, &r);
     if (!rc && in.Into) rc = assign_stage(o, ctx, in, &r);
     if (!rc && in.Kt) rc = kron_stage(o, ctx, in, &r);
