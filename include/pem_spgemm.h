@@ -530,6 +530,43 @@ pem_status pem_tiled_set_values_from_scale_f32(pem_ctx *ctx, pem_tiled *t, const
 pem_status pem_tiled_kron(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled **out);
 pem_status pem_tiled_set_values_from_kron(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B);
 
+/* Build from triplets that may repeat a position (GraphBLAS GrB_Matrix_build with a dup operator): the
+ * duplicates of every (row, col) are folded on the device and the result is an ordinary tiling.
+ *   pem_tiled_build / _device  nnz_in triplets (I, J, V) in any order -- host arrays, or device arrays read on the context's stream --
+ *       become a tiling of rows x cols (transpose = 1: of the transposed matrix, as pem_tiled_from_coo) whose nnz is the number of
+ *       DISTINCT positions.  pem_tiled_from_coo's argument rules hold for nnz_in: PEM_E_OVERFLOW beyond the int32 range,
+ *       PEM_E_INVALID with "index out of range for a %d x %d matrix".  nnz_in = 0 and an input without duplicates are valid; the
+ *       latter gives pem_tiled_from_coo_device's tiling, array for array.
+ *     dup.  A pem_binop (0 .. 5), PEM_DUP_FIRST or PEM_DUP_SECOND; anything else is PEM_E_INVALID.  The duplicates of a position are
+ *       folded IN INPUT ORDER, ((v0 op v1) op v2) ..., each step pem_tiled_ewise's both-stored arithmetic in the value type (MIN /
+ *       MAX are fmin / fmax, LOR / LAND test != 0; a position given once keeps its value as it is under every op).  FIRST keeps the
+ *       value that came first in the input, SECOND the one that came last, bit for bit.
+ *     Fold order.  A position with at most PEM_BUILD_INORDER_MAX triplets is folded strictly left to right.  A longer run keeps the
+ *       input order but may be regrouped: consecutive segments are folded on their own and the partial results combined in order
+ *       (which rounds PLUS and TIMES differently, and nothing else).  No atomics: the same input gives the same bits every time.
+ *     flags.  PEM_BUILD_KEEP_MAP keeps what pem_tiled_set_values_from_build needs (4 bytes per triplet, 4 per entry).  Without it
+ *       the tiling holds exactly what pem_tiled_from_coo's tiling of the folded entries holds.
+ *     The tiling works everywhere a tiling does (operand, mask, save / load, every set_values*, export, every derived route).
+ *   pem_tiled_set_values_from_build  new values for the SAME triplet list (dV: nnz_in device values in the input order of the build):
+ *       t's values become bit for bit what a fresh build of (I, J, dV) holds; the value version is bumped.  Stream-ordered, never
+ *       waits, reads nothing back; only the first call allocates.  PEM_E_INVALID unless t was made with PEM_BUILD_KEEP_MAP from
+ *       nnz_in triplets.
+ *   PEM_BUILD_INORDER in the environment (a measurement knob, read when a tiling is built): an integer above PEM_BUILD_INORDER_MAX
+ *       raises the run length folded strictly left to right; smaller values are ignored.  A refresh folds as its tiling's build did. */
+enum { PEM_DUP_FIRST = 6, PEM_DUP_SECOND = 7 };   /* otherwise a pem_binop */
+#define PEM_BUILD_KEEP_MAP 1
+#define PEM_BUILD_INORDER_MAX 32
+pem_status pem_tiled_build(pem_ctx *ctx, int rows, int cols, int64_t nnz_in, const int32_t *I, const int32_t *J, const double *V,
+                           int transpose, int dup, int flags, pem_tiled **out);
+pem_status pem_tiled_build_device(pem_ctx *ctx, int rows, int cols, int64_t nnz_in, const int32_t *dI, const int32_t *dJ,
+                                  const double *dV, int transpose, int dup, int flags, pem_tiled **out);
+pem_status pem_tiled_build_f32(pem_ctx *ctx, int rows, int cols, int64_t nnz_in, const int32_t *I, const int32_t *J, const float *V,
+                               int transpose, int dup, int flags, pem_tiled **out);
+pem_status pem_tiled_build_device_f32(pem_ctx *ctx, int rows, int cols, int64_t nnz_in, const int32_t *dI, const int32_t *dJ,
+                                      const float *dV, int transpose, int dup, int flags, pem_tiled **out);
+pem_status pem_tiled_set_values_from_build(pem_ctx *ctx, pem_tiled *t, const double *dV, int64_t nnz_in);
+pem_status pem_tiled_set_values_from_build_f32(pem_ctx *ctx, pem_tiled *t, const float *dV, int64_t nnz_in);
+
 /* Matrix-vector products and reductions: a tiling times a dense device vector under a semiring, and
  * the fold of every row or column, on the device.
  *   pem_tiled_mxv  y = A (+).(x) x  (transpose = 0: x has A.cols entries, y has A.rows)

@@ -58,12 +58,20 @@ ABI_SYMBOLS = [
     "pem_tiled_mxv_frontier", "pem_tiled_mxv_frontier_f32", "pem_tiled_bfs", "pem_test_frontier_line_flags",
     "pem_tiled_apply", "pem_tiled_set_values_from_apply", "pem_tiled_scale", "pem_tiled_scale_f32", "pem_tiled_set_values_from_scale",
     "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron", "pem_tiled_select_topk",
+    "pem_tiled_build", "pem_tiled_build_f32", "pem_tiled_build_device", "pem_tiled_build_device_f32", "pem_tiled_set_values_from_build",
+    "pem_tiled_set_values_from_build_f32",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
 EWISE_PATTERNS = dict(union=0, intersect=1)
 BINOPS = dict(plus=0, times=1, min=2, max=3, lor=4, land=5)
 ACCUM_NONE = -1   # PEM_ACCUM_NONE: Tiled.assign without an accum
+
+# Tiled.build's dup operators, by value (include/pem_spgemm.h): the pem_binop values, then PEM_DUP_FIRST and
+# PEM_DUP_SECOND; PEM_BUILD_KEEP_MAP; and PEM_BUILD_INORDER_MAX, the longest run of duplicates that is folded strictly left to right
+DUP_OPS = ("plus", "times", "min", "max", "lor", "land", "first", "second")
+BUILD_KEEP_MAP = 1
+BUILD_INORDER_MAX = 32
 
 # enum pem_select_op (include/pem_spgemm.h): Tiled.select's ops, by value; the first eight are positional
 SELECT_OPS = ("tril", "triu", "diag", "offdiag", "row_le", "row_gt", "col_le", "col_gt", "value_eq", "value_ne", "value_lt", "value_le",
@@ -282,6 +290,56 @@ class Tiled:
         _check(fn(ctx._h, int(rows), int(cols), _p(rowptr, C.c_int32), _p(colidx, C.c_int32), _p(V, C.c_float if f32 else C.c_double),
                   C.byref(h)))
         return cls(ctx, h)
+
+    @staticmethod
+    def _dup(dup):
+        if dup not in DUP_OPS:
+            raise ValueError(f"unknown dup op {dup!r}; one of {DUP_OPS}")
+        return DUP_OPS.index(dup)
+
+    @classmethod
+    def build(cls, ctx, rows, cols, I, J, V, dup="plus", transpose=False, dtype=np.float64, keep_map=False):
+        """Build from triplets that may repeat a position: the duplicates of every (row, col) are folded
+        on the device in input order, ((v0 op v1) op v2) ..., under dup (one of DUP_OPS; "first" / "second" keep the value that came
+        first / last).  The result is an ordinary tiling whose nnz counts the distinct positions.  Runs of at most BUILD_INORDER_MAX
+        duplicates are folded strictly left to right.  keep_map=True keeps what set_values_from_build needs.  Waits."""
+        dup = cls._dup(dup)
+        f32 = np.dtype(dtype) == np.float32
+        I = np.ascontiguousarray(I, dtype=np.int32)
+        J = np.ascontiguousarray(J, dtype=np.int32)
+        V = np.ascontiguousarray(V, dtype=np.float32 if f32 else np.float64)
+        if not (len(I) == len(J) == len(V)):
+            raise ValueError("I, J, V lengths differ")
+        h = C.c_void_p()
+        fn = lib().pem_tiled_build_f32 if f32 else lib().pem_tiled_build
+        _check(fn(ctx._h, int(rows), int(cols), C.c_int64(len(I)), _p(I, C.c_int32), _p(J, C.c_int32), _p(V, C.c_float if f32 else C.c_double),
+                  int(bool(transpose)), dup, BUILD_KEEP_MAP if keep_map else 0, C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def build_device(cls, ctx, rows, cols, nnz_in, dI, dJ, dV, dup="plus", transpose=False, dtype=np.float64, keep_map=False):
+        """build from device memory: dI/dJ/dV are device pointers (ints), e.g. torch tensors' data_ptr(), to nnz_in int32 indices and
+        `dtype` values, read on the context's stream.  Waits."""
+        dup = cls._dup(dup)
+        h = C.c_void_p()
+        fn = lib().pem_tiled_build_device_f32 if np.dtype(dtype) == np.float32 else lib().pem_tiled_build_device
+        _check(fn(ctx._h, int(rows), int(cols), C.c_int64(nnz_in), C.c_void_p(dI), C.c_void_p(dJ), C.c_void_p(dV), int(bool(transpose)),
+                  dup, BUILD_KEEP_MAP if keep_map else 0, C.byref(h)))
+        return cls(ctx, h)
+
+    def set_values_from_build(self, dV, nnz_in=None):
+        """Refresh a tiling made by build(..., keep_map=True) from new values of the same triplet list, in the list's order: the values
+        become bit for bit what a fresh build holds.  dV: a contiguous device torch tensor of the tiling's dtype (nnz_in = its length),
+        or a device pointer (int) with nnz_in given.  Ordered on the context's stream; returns without waiting."""
+        if hasattr(dV, "data_ptr"):
+            if not dV.is_cuda or not dV.is_contiguous() or str(dV.dtype) != f"torch.{self.dtype.name}" or nnz_in not in (None, dV.numel()):
+                raise ValueError(f"set_values_from_build: want a contiguous device tensor of {self.dtype.name} values, one per triplet, "
+                                 f"got {dV.dtype} x {dV.numel()} on {dV.device}")
+            nnz_in, dV = dV.numel(), dV.data_ptr()
+        if nnz_in is None:
+            raise ValueError("set_values_from_build: a device pointer needs nnz_in")
+        fn = lib().pem_tiled_set_values_from_build_f32 if self.value_bytes == 4 else lib().pem_tiled_set_values_from_build
+        _check(fn(self.ctx._h, self._h, C.c_void_p(int(dV)), C.c_int64(int(nnz_in))))
 
     def _order(self, order):
         if order not in VALUE_ORDERS:

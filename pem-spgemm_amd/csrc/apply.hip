@@ -89,20 +89,6 @@ __device__ __forceinline__ VT ap_value(int op, VT x, VT y, int k)
     }
 }
 
-// pem_tiled_ewise's arithmetic at alpha = beta = 1 (ew_value, ewise.hip)
-template <typename VT>
-__device__ __forceinline__ VT sc_binop(int op, VT a, VT b)
-{
-    switch (op) {
-    case PEM_BINOP_PLUS: return a + b;
-    case PEM_BINOP_TIMES: return a * b;
-    case PEM_BINOP_MIN: return pem_fmin(a, b);
-    case PEM_BINOP_MAX: return pem_fmax(a, b);
-    case PEM_BINOP_LOR: return (a != VT(0) || b != VT(0)) ? VT(1) : VT(0);
-    default: return (a != VT(0) && b != VT(0)) ? VT(1) : VT(0);   // PEM_BINOP_LAND
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // apply: dst[e] = f(src[e]) over vals (blockIdx.y = 0) and vals_t (1), four entries per lane.  Both arrays start 256-byte aligned
 // (arena blocks); the last nnz & 3 entries go one by one, so nothing past slot nnz - 1 is read or written.  ONE reads no values.
@@ -175,8 +161,8 @@ __global__ void __launch_bounds__(256) scale_kernel(const long long *__restrict_
         if (el >= e_end) continue;
         const unsigned rc = rci[e];
         VT z = a_vals[e];
-        if (d_row) z = sc_binop<VT>(op, d_row[16 * tr + (int)(rc >> 4)], z);
-        if (d_col) z = sc_binop<VT>(op, z, d_col[16 * tc + (int)(rc & 15u)]);
+        if (d_row) z = pem_binop_value<VT>(op, d_row[16 * tr + (int)(rc >> 4)], z);
+        if (d_col) z = pem_binop_value<VT>(op, z, d_col[16 * tc + (int)(rc & 15u)]);
         vals[e] = z;
         vals_t[map_t[e]] = z;
     }

@@ -573,6 +573,12 @@ pem_status pem::derive_tiled(pem_ctx *ctx, pem_tiled *T, const int *headx, int b
     return PEM_OK;
 }
 
+void pem::coo_sort_keys(pem_ctx *ctx, const pem_tiled *T, const int *dI, const int *dJ, size_t n, int transpose, int bits_tc, uint64_t *keys,
+                        uint32_t *perm)
+{
+    PEM_LAUNCH(ctx, conv_make_keys_kernel, grid_for(n, 256), 256, dI, dJ, n, T->rows, T->cols, transpose, bits_tc, keys, perm, ctx->d_flags);
+}
+
 // keys/perm already filled in k0/v0 (nnz entries); V = device values in input order.
 static pem_status build_tiled(pem_ctx *ctx, pem_tiled *T, DevBuf &k0, DevBuf &k1, DevBuf &v0, DevBuf &v1, const void *dV,
                               int bits_tr, int bits_tc)
@@ -653,8 +659,7 @@ static pem_status tiled_from_device(pem_ctx *ctx, int rows, int cols, int64_t nn
                 PEM_LAUNCH(ctx, conv_csr_keys_kernel, grid_for((size_t)rows, 256), 256, d_rowptr, dJ, rows, cols, bits_tc, k0.as<uint64_t>(),
                            v0.as<uint32_t>(), ctx->d_flags);
             else
-                PEM_LAUNCH(ctx, conv_make_keys_kernel, grid_for(n, 256), 256, dI, dJ, n, T->rows, T->cols, transpose, bits_tc,
-                           k0.as<uint64_t>(), v0.as<uint32_t>(), ctx->d_flags);
+                coo_sort_keys(ctx, T, dI, dJ, n, transpose, bits_tc, k0.as<uint64_t>(), v0.as<uint32_t>());
         }
         if (s == PEM_OK) s = build_tiled(ctx, T, k0, k1, v0, v1, dV, bits_tr, bits_tc);
         (void)hipStreamSynchronize(ctx->stream);

@@ -42,14 +42,7 @@ __device__ __forceinline__ VT ew_value(const EwParams &p, bool has_a, VT a, bool
     if (has_b && p.beta != 1.0) b = (VT)p.beta * b;
     if (!has_b) return a;
     if (!has_a) return b;
-    switch (p.op) {
-    case PEM_BINOP_PLUS: return a + b;
-    case PEM_BINOP_TIMES: return a * b;
-    case PEM_BINOP_MIN: return pem_fmin(a, b);
-    case PEM_BINOP_MAX: return pem_fmax(a, b);
-    case PEM_BINOP_LOR: return (a != VT(0) || b != VT(0)) ? VT(1) : VT(0);
-    default: return (a != VT(0) && b != VT(0)) ? VT(1) : VT(0);   // PEM_BINOP_LAND
-    }
+    return pem_binop_value<VT>(p.op, a, b);
 }
 
 __device__ __forceinline__ unsigned ew_tile_and(const uint16_t *__restrict__ ma, const uint16_t *__restrict__ mb, long long ta, long long tb)

@@ -48,20 +48,6 @@ struct KrSide {
     int rows, cols;
 };
 
-// pem_tiled_ewise's arithmetic where both are stored, alpha = beta = 1 (ew_value, ewise.hip)
-template <typename VT>
-__device__ __forceinline__ VT kr_binop(int op, VT a, VT b)
-{
-    switch (op) {
-    case PEM_BINOP_PLUS: return a + b;
-    case PEM_BINOP_TIMES: return a * b;
-    case PEM_BINOP_MIN: return pem_fmin(a, b);
-    case PEM_BINOP_MAX: return pem_fmax(a, b);
-    case PEM_BINOP_LOR: return (a != VT(0) || b != VT(0)) ? VT(1) : VT(0);
-    default: return (a != VT(0) && b != VT(0)) ? VT(1) : VT(0);   // PEM_BINOP_LAND
-    }
-}
-
 // One lane per (A entry ea, B tile tb), x = ea * tb_count + tb.  The pair's block of R is rows i*mB + 16K .. (clipped at B's last
 // row) and columns j*nB + 16L .. alike: 1 or 2 tile rows times 1 or 2 tile columns.  coff == null: cnt[x] = that count.  Else:
 // the keys at coff[x] .. (coff = the scanned counts).
@@ -170,7 +156,7 @@ __device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, co
                 if (e < e_end) {   // (the masks and the offsets come from the same counts; never write past the tile)
                     rowcolidx[e] = (uint8_t)((r << 4) | (int)(place + b));
                     headx[e] = e == e0 ? tile : tile + 1;
-                    vals[e] = kr_binop<VT>(op, a, b_vals[kr_slot(sb, sh + b)]);
+                    vals[e] = pem_binop_value<VT>(op, a, b_vals[kr_slot(sb, sh + b)]);
                 }
                 ++e;
             }

@@ -318,9 +318,14 @@ uint64_t next_tiled_serial();
 //                                              (both always stored).
 //   TOPK    pem_tiled_select_topk (topk.hip)   src[0] = A's serial; op = order; pattern = dim; p0 = k.  src_tiles as SELECT's.  No
 //                                              refresh: the pattern depends on A's values.
+//   BUILD   pem_tiled_build* with PEM_BUILD_KEEP_MAP (build.hip)   op = dup; p0 = nnz_in; pattern = the longest run the build folded
+//                                              strictly left to right (the refresh groups the runs the same way).  map: uint32[nnz_in], the sort's
+//                                              permutation (sorted position -> input index), kept by the build.  idx[0]: int32[nnz + 1],
+//                                              run_start -- entry s folds the sorted positions run_start[s] .. run_start[s + 1] - 1.
+//                                              No source tiling: the values are an argument of every refresh.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK, BUILD } kind = NONE;
     uint64_t src[2] = {0, 0};
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;

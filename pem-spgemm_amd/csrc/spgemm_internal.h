@@ -64,6 +64,19 @@ __device__ __forceinline__ float pem_fma(float a, float b, float c) { return __b
 template <typename VT> __device__ __forceinline__ VT pem_inf() { return sizeof(VT) == 8 ? (VT)__builtin_huge_val() : (VT)__builtin_huge_valf(); }
 template <typename VT> __device__ __forceinline__ VT pem_fmin(VT x, VT y) { if constexpr (sizeof(VT) == 8) return __builtin_fmin(x, y); else return __builtin_fminf(x, y); }
 template <typename VT> __device__ __forceinline__ VT pem_fmax(VT x, VT y) { if constexpr (sizeof(VT) == 8) return __builtin_fmax(x, y); else return __builtin_fmaxf(x, y); }
+// a pem_binop on two stored values in the value type, rounded once (pem_tiled_ewise's both-stored arithmetic at alpha = beta = 1):
+// what ewise.hip, apply.hip's scale, kron.hip and build.hip's fold of duplicates compute
+template <typename VT> __device__ __forceinline__ VT pem_binop_value(int op, VT a, VT b)
+{
+    switch (op) {
+    case PEM_BINOP_PLUS: return a + b;
+    case PEM_BINOP_TIMES: return a * b;
+    case PEM_BINOP_MIN: return pem_fmin(a, b);
+    case PEM_BINOP_MAX: return pem_fmax(a, b);
+    case PEM_BINOP_LOR: return (a != VT(0) || b != VT(0)) ? VT(1) : VT(0);
+    default: return (a != VT(0) && b != VT(0)) ? VT(1) : VT(0);   // PEM_BINOP_LAND
+    }
+}
 struct SrPlusTimes {
     static constexpr bool vals = true;
     template <typename VT> static __device__ __forceinline__ VT start() { return VT(0); }

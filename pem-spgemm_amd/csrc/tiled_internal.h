@@ -1,7 +1,9 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
-// provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.
+// provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.  build.hip shares the
+// HEAD of pem_tiled_from_coo* (coo_sort_keys, then the radix sort) and this tail; its payload kernel is its own, because it compacts the
+// sorted positions to entries where convert.hip's conv_fill_kernel writes one value per position.
 #pragma once
 #include "pem_internal.h"
 #include <chrono>
@@ -12,6 +14,11 @@ namespace pem {
 
 // value_bytes, rows, cols and the tile grid (tile_rows, tile_cols); nnz and ntiles are the caller's (convert.hip)
 void set_tiled_shape(pem_tiled *T, int value_bytes, int rows, int cols);
+// keys[e] = (tile row | tile column | r << 4 | c) of triplet e, perm[e] = e: the sort key whose order IS the tiled storage order.  n > 0;
+// an index outside T's rows x cols raises FLAG_RANGE.  T's shape is the tiling's (already transposed); transpose swaps I and J.
+// The head of pem_tiled_from_coo* and of pem_tiled_build* (convert.hip)
+void coo_sort_keys(pem_ctx *ctx, const pem_tiled *T, const int *dI, const int *dJ, size_t n, int transpose, int bits_tc, uint64_t *keys,
+                   uint32_t *perm);
 // sizing phase "tiles" of a tiling whose rows, cols, nnz, ntiles and value_bytes are set: every per-tile array (and the
 // nnz-sized payload) in one driver allocation
 pem_status reserve_tile_arrays(pem_ctx *ctx, pem_tiled *T);

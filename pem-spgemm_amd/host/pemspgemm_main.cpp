@@ -54,6 +54,7 @@ static double ms_since(Clock::time_point t0) { return std::chrono::duration<doub
 static const char *const semiring_names[] = {"plus_times", "min_plus", "max_plus", "max_times", "plus_pair", "lor_land"};   // pem_semiring
 static const int add_ops[] = {PEM_BINOP_PLUS, PEM_BINOP_MIN, PEM_BINOP_MAX, PEM_BINOP_MAX, PEM_BINOP_PLUS, PEM_BINOP_LOR};   // by pem_semiring
 static const char *const binop_names[] = {"plus", "times", "min", "max", "lor", "land"};                                    // by pem_binop
+static const char *const dup_names[] = {"plus", "times", "min", "max", "lor", "land", "first", "second"};   // pem_binop, PEM_DUP_FIRST, PEM_DUP_SECOND
 static const char *const select_names[] = {"tril",     "triu",     "diag",     "offdiag",  "row_le",   "row_gt",   "col_le", "col_gt",
                                            "value_eq", "value_ne", "value_lt", "value_le", "value_gt", "value_ge", "abs_gt"};   // pem_select_op
 static const char *const apply_names[] = {"identity", "abs", "ainv", "minv", "sqrt", "one", "plus",
@@ -97,6 +98,7 @@ struct Options {
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP: see assign_stage
     const char *assign_paths[2] = {nullptr, nullptr};               // --assign-rows I.mtx, --assign-cols J.mtx
     const char *kron_path = nullptr, *kron_op_name = nullptr;       // --kron K.mtx [--kron-op OP]: see kron_stage
+    const char *dup_name = nullptr;                                 // --dup OP: see tiling_from_coo
     const char *reduce_spec = nullptr;                              // --reduce rows|cols[:OP]: see reduce_stage
     const char *bfs_spec = nullptr;                                 // --bfs SRC: see bfs_stage
     const char *spmm_path = nullptr;                                // --spmm X.mtx: see spmm_stage
@@ -122,6 +124,7 @@ struct Options {
     std::vector<int32_t> extract_idx[2], assign_idx[2];   // 0-based
     int assign_accum = PEM_ACCUM_NONE;
     int kron_op = PEM_BINOP_TIMES;
+    int dup = -1;                                         // -1: no --dup, duplicates are refused
     int64_t spmm_rows = 0, spmm_k = 0, sddmm_xrows = 0, sddmm_yrows = 0, sddmm_k = 0;
     std::vector<double> spmm_x, sddmm_x, sddmm_y;         // row-major
     int reduce_dim = -1, reduce_op = -1;
@@ -142,7 +145,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--reduce", &o->reduce_spec}, {"--bfs", &o->bfs_spec}, {"--spmm", &o->spmm_path}, {"--sddmm", &o->sddmm_path},
                   {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
-                  {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec}};
+                  {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
+                  {"--dup", &o->dup_name}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -188,6 +192,7 @@ static const struct ClashRule {
     {"--col-scale", {"--gpus", "--power"}, ""},
     {"--kron", {"--gpus"}, ""},
     {"--topk", {"--gpus", "--power"}, ""},
+    {"--dup", {"--gpus", "--cache"}, ""},   // (a cached tiling would depend on the op, which its key does not carry)
 };
 
 // Prints the refusal and returns true when `flag` (which is present) meets something its rule refuses.
@@ -198,7 +203,8 @@ static bool clashes(const Options &o, const char *flag)
         bool present;
     } given[] = {{"--gpus", o.ngpu > 0},       {"--mask", o.mask_path != nullptr}, {"--power", o.power != 0},
                  {"--B", o.b_path != nullptr}, {"the A*A^T argument", o.aat},      {"--reduce", o.reduce_spec != nullptr},
-                 {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr}};
+                 {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr},
+                 {"--cache", o.cache_dir != nullptr}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -531,6 +537,17 @@ static int validate_topk(Options *o)
     return 0;
 }
 
+// --dup OP: the op by name (a pem_binop, first or second) under which every Matrix-Market operand's duplicates are folded
+static int validate_dup(Options *o)
+{
+    if (!o->dup_name) return 0;
+    if ((o->dup = find_name(dup_names, 8, o->dup_name)) < 0) {
+        printf("--dup %s: unknown op (plus, times, min, max, lor, land, first, second). Exiting.\n", o->dup_name);
+        return 1;
+    }
+    return clashes(*o, "--dup") ? 1 : 0;
+}
+
 // Checks the options against each other and reads the files that can be refused before any work (index lists, X, Y).  Returns 0
 // to go on, else the exit code after the refusal; the order of the checks decides which refusal a command with two faults gets.
 static int validate(Options *o)
@@ -544,7 +561,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk, validate_dup})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -616,19 +633,23 @@ static void append_csv_row(const Options &o, pem_csv_record rec, const char *ext
     if (pem_csv_append(csv, &rec, extra) != 0) fprintf(stderr, "pemspgemm: %s\n", pem_host_last_error());
 }
 
-// COO -> tiling; under fp32 the values are rounded to float first
-static pem_status tiling_from_coo(pem_ctx *ctx, const pem_coo &m, bool fp32, int transpose, Tiled *t)
+// COO -> tiling; under fp32 the values are rounded to float first.  dup < 0: a repeated (row, col) is refused (pem_tiled_from_coo);
+// else `--dup OP`: the repeats -- a symmetric file's expansion may add some -- are folded under it in file order (pem_tiled_build)
+static pem_status tiling_from_coo(pem_ctx *ctx, const pem_coo &m, bool fp32, int transpose, int dup, Tiled *t)
 {
-    if (!fp32) return pem_tiled_from_coo(ctx, m.rows, m.cols, m.nnz, m.I, m.J, m.V, transpose, out(ctx, *t));
+    if (!fp32)
+        return dup < 0 ? pem_tiled_from_coo(ctx, m.rows, m.cols, m.nnz, m.I, m.J, m.V, transpose, out(ctx, *t))
+                       : pem_tiled_build(ctx, m.rows, m.cols, m.nnz, m.I, m.J, m.V, transpose, dup, 0, out(ctx, *t));
     std::vector<float> vf((size_t)m.nnz);
     for (int64_t e = 0; e < m.nnz; ++e) vf[(size_t)e] = (float)m.V[e];
-    return pem_tiled_from_coo_f32(ctx, m.rows, m.cols, m.nnz, m.I, m.J, vf.data(), transpose, out(ctx, *t));
+    return dup < 0 ? pem_tiled_from_coo_f32(ctx, m.rows, m.cols, m.nnz, m.I, m.J, vf.data(), transpose, out(ctx, *t))
+                   : pem_tiled_build_f32(ctx, m.rows, m.cols, m.nnz, m.I, m.J, vf.data(), transpose, dup, 0, out(ctx, *t));
 }
 
 // the same with the refusal: 0, or 2 after the message
-static int convert_or_refuse(pem_ctx *ctx, const char *path, const pem_coo &m, bool fp32, int transpose, Tiled *t)
+static int convert_or_refuse(pem_ctx *ctx, const char *path, const pem_coo &m, bool fp32, int transpose, int dup, Tiled *t)
 {
-    if (tiling_from_coo(ctx, m, fp32, transpose, t) == PEM_OK) return 0;
+    if (tiling_from_coo(ctx, m, fp32, transpose, dup, t) == PEM_OK) return 0;
     fprintf(stderr, "pemspgemm: conversion of %s failed: %s\n", path, pem_last_error());
     return 2;
 }
@@ -1210,7 +1231,7 @@ static int make_tiling(const Options &o, pem_ctx *ctx, Source &src, int transpos
         if (read_input(o, src.path, &src.coo) != 0) return 1;
         src.read = true;
     }
-    if (int rc = convert_or_refuse(ctx, src.path, src.coo, o.fp32, transpose, t)) return rc;
+    if (int rc = convert_or_refuse(ctx, src.path, src.coo, o.fp32, transpose, o.dup, t)) return rc;
     if (keyed && pem_tiled_save(ctx, t->get(), cpath.c_str(), &key) != PEM_OK)
         fprintf(stderr, "pemspgemm: cache not written: %s\n", pem_last_error());   // not fatal
     return 0;
@@ -1245,7 +1266,7 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
             printf("mask %s is %d x %d but C = A*B%s is %d x %d. Exiting.\n", o.mask_path, cm.rows, cm.cols, o.aat ? "^T" : "", ia.rows, ib.cols);
             return 1;
         }
-        if (int rc = convert_or_refuse(ctx, o.mask_path, cm, false, 0, &in->Mt)) return rc;
+        if (int rc = convert_or_refuse(ctx, o.mask_path, cm, false, 0, o.dup, &in->Mt)) return rc;
     }
     if (o.add_path) {   // D, in the value type of A
         if (read_input(o, o.add_path, &cd) != 0) return 1;
@@ -1253,17 +1274,17 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
             printf("--add %s is %d x %d but C = A*B%s is %d x %d. Exiting.\n", o.add_path, cd.rows, cd.cols, o.aat ? "^T" : "", ia.rows, ib.cols);
             return 1;
         }
-        if (int rc = convert_or_refuse(ctx, o.add_path, cd, o.fp32, 0, &in->Dt)) return rc;
+        if (int rc = convert_or_refuse(ctx, o.add_path, cd, o.fp32, 0, o.dup, &in->Dt)) return rc;
     }
     if (o.assign_into) {   // D, in the value type of A
         if (read_input(o, o.assign_into, &cinto) != 0) return 1;
         const int dims[2] = {cinto.rows, cinto.cols};
         if (!lists_in_range(assign_flags, o.assign_paths, o.assign_idx, dims, o.assign_into)) return 1;
-        if (int rc = convert_or_refuse(ctx, o.assign_into, cinto, o.fp32, 0, &in->Into)) return rc;
+        if (int rc = convert_or_refuse(ctx, o.assign_into, cinto, o.fp32, 0, o.dup, &in->Into)) return rc;
     }
     if (o.kron_path) {   // K, in the value type of A
         if (read_input(o, o.kron_path, &ck) != 0) return 1;
-        if (int rc = convert_or_refuse(ctx, o.kron_path, ck, o.fp32, 0, &in->Kt)) return rc;
+        if (int rc = convert_or_refuse(ctx, o.kron_path, ck, o.fp32, 0, o.dup, &in->Kt)) return rc;
     }
     if (o.fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", o.input(), ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
