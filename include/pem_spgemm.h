@@ -530,6 +530,33 @@ pem_status pem_tiled_set_values_from_scale_f32(pem_ctx *ctx, pem_tiled *t, const
 pem_status pem_tiled_kron(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled **out);
 pem_status pem_tiled_set_values_from_kron(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B);
 
+/* Concat (GraphBLAS GxB_Matrix_concat): block assembly R = [[B00, B01, ..], [B10, ..], ..], on the device.
+ *   pem_tiled_concat  a new tiling R, owning its arrays, from a grid of grid_rows x grid_cols tilings.  blocks is row-major with
+ *       grid_rows * grid_cols entries; a null entry is an all-empty block.  row_sizes[a] and col_sizes[b] are always given: a non-null
+ *       block at (a, b) is exactly row_sizes[a] x col_sizes[b].  A size of 0 is allowed (the strip contributes nothing), and so is a
+ *       grid row or column of nulls only.  The same tiling may sit in several cells; a block may be any tiling (converted, loaded,
+ *       derived -- another pem_tiled_concat result included); blocks without entries are ordinary blocks.
+ *     R is sum(row_sizes) x sum(col_sizes) in the blocks' value type and stores (ro_a + i, co_b + j) exactly where block (a, b)
+ *       stores (i, j), ro / co the exclusive prefix sums of the sizes; the value is copied bit for bit, explicit zeros stay entries.
+ *       nnz(R) = the sum of the blocks' nnz (a tiling counted once per cell it sits in).  R equals the tiling pem_tiled_from_coo
+ *       builds from those entries (every pem_tiled_info field but the two timings, every pem_tiled_array) and works everywhere a
+ *       tiling does.  A 1 x 1 grid is a copy: R's arrays equal the block's.  The inverse is pem_tiled_extract with ranges.
+ *     Refusals, all before anything is launched or allocated.  PEM_E_INVALID: a null argument, grid_rows or grid_cols < 1, a negative
+ *       size, a block of the wrong shape, blocks of different value types, a block made on another context, a grid without any
+ *       non-null block (there is no value type then).  PEM_E_OVERFLOW: a sum of sizes above INT32_MAX, or blocks whose entries
+ *       together do not fit an int32 (both computed in 64 bits on the host).
+ *     The blocks' values are read as they are when the call is made (stream order); the call waits, and its allocations come from the
+ *       context's arena.  No entry is sorted: the only sort is over the result's candidate tiles.
+ *   pem_tiled_set_values_from_concat  copies the blocks' current values into t (vals and vals_t) in place and bumps t's value
+ *       version.  blocks is the grid again, nblocks = grid_rows * grid_cols entries with nulls where the build had nulls.
+ *       Stream-ordered, never waits, reads nothing back; only the first call allocates (an int32 pair per entry: its cell and its slot
+ *       in that block's values, and a pointer per cell).  PEM_E_INVALID unless t was made by pem_tiled_concat from exactly these
+ *       tilings in these cells (the serial rule of pem_tiled_set_values_from_ewise): a wrong count, a swapped or foreign block and a
+ *       null where the build had a block (or a block where it had a null) are refused. */
+pem_status pem_tiled_concat(pem_ctx *ctx, int grid_rows, int grid_cols, const pem_tiled *const *blocks, const int64_t *row_sizes,
+                            const int64_t *col_sizes, pem_tiled **out);
+pem_status pem_tiled_set_values_from_concat(pem_ctx *ctx, pem_tiled *t, int nblocks, const pem_tiled *const *blocks);
+
 /* Build from triplets that may repeat a position (GraphBLAS GrB_Matrix_build with a dup operator): the
  * duplicates of every (row, col) are folded on the device and the result is an ordinary tiling.
  *   pem_tiled_build / _device  nnz_in triplets (I, J, V) in any order -- host arrays, or device arrays read on the context's stream --

@@ -59,7 +59,7 @@ ABI_SYMBOLS = [
     "pem_tiled_apply", "pem_tiled_set_values_from_apply", "pem_tiled_scale", "pem_tiled_scale_f32", "pem_tiled_set_values_from_scale",
     "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron", "pem_tiled_select_topk",
     "pem_tiled_build", "pem_tiled_build_f32", "pem_tiled_build_device", "pem_tiled_build_device_f32", "pem_tiled_set_values_from_build",
-    "pem_tiled_set_values_from_build_f32",
+    "pem_tiled_set_values_from_build_f32", "pem_tiled_concat", "pem_tiled_set_values_from_concat",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -415,6 +415,88 @@ class Tiled:
         """Refresh a tiling made by kron(A, B, ...) from A's and B's current values, in place.  Ordered on the context's stream;
         returns without waiting."""
         _check(lib().pem_tiled_set_values_from_kron(self.ctx._h, self._h, A._h, B._h))
+
+    @staticmethod
+    def _concat_grid(blocks, row_sizes=None, col_sizes=None):
+        """concat's checks, none of which touches the device -> (grid_rows, grid_cols, the blocks row-major, row sizes, column sizes)"""
+        if not isinstance(blocks, (list, tuple)) or not blocks or not all(isinstance(row, (list, tuple)) for row in blocks):
+            raise ValueError("concat: blocks must be a non-empty list of lists")
+        gr, gc = len(blocks), len(blocks[0])
+        if gc == 0 or any(len(row) != gc for row in blocks):
+            raise ValueError(f"concat: blocks must be rectangular, rows of {[len(row) for row in blocks]} cells are not")
+        flat = [b for row in blocks for b in row]
+        if not all(b is None or isinstance(b, Tiled) for b in flat):
+            raise ValueError("concat: every block must be a Tiled or None")
+        some = [b for b in flat if b is not None]
+        if not some:
+            raise ValueError("concat: every block is None: the result would have no dtype")
+        if any(b.value_bytes != some[0].value_bytes for b in some):
+            raise ValueError("concat: the blocks hold different dtypes")
+        if any(b.ctx is not some[0].ctx for b in some):
+            raise ValueError("concat: the blocks belong to different contexts")
+        sizes = []
+        for name, given, n, dim, line in (("row_sizes", row_sizes, gr, "rows", lambda k: blocks[k]),
+                                          ("col_sizes", col_sizes, gc, "cols", lambda k: [row[k] for row in blocks])):
+            if given is not None:
+                given = [int(x) for x in given]
+                if len(given) != n or any(x < 0 for x in given):
+                    raise ValueError(f"concat: {name} must hold {n} sizes >= 0, not {given}")
+            out = []
+            for k in range(n):
+                have = sorted({getattr(b, dim) for b in line(k) if b is not None})
+                if len(have) > 1:
+                    raise ValueError(f"concat: the blocks of grid {dim[:-1]} {k} have {have} {dim}")
+                if given is None and not have:
+                    raise ValueError(f"concat: grid {dim[:-1]} {k} holds only None: give {name}")
+                if given is not None and have and have[0] != given[k]:
+                    raise ValueError(f"concat: {name}[{k}] = {given[k]}, but a block there has {have[0]} {dim}")
+                out.append(given[k] if given is not None else have[0])
+            sizes.append(out)
+        return gr, gc, flat, sizes[0], sizes[1]
+
+    @classmethod
+    def concat(cls, blocks, row_sizes=None, col_sizes=None):
+        """Concat: the block matrix [[B00, B01, ..], [B10, ..], ..] as a new tiling built on the device.
+        blocks: a rectangular list of lists of Tiled or None (an all-empty block); the blocks of one grid row have the same rows, of
+        one grid column the same cols, and all one dtype.  row_sizes / col_sizes default to the sizes of the non-null blocks of each
+        grid row / column; a strip of only None needs its size given (0 is allowed).  The result stores (ro_a + i, co_b + j) where
+        block (a, b) stores (i, j), values copied bit for bit.  The same tiling may sit in several cells.  ValueError (before the
+        device is touched) for a ragged grid, a size that cannot be determined or contradicts a block, mixed dtypes.  Waits."""
+        gr, gc, flat, rs, cs = cls._concat_grid(blocks, row_sizes, col_sizes)
+        ctx = next(b for b in flat if b is not None).ctx
+        hs = (C.c_void_p * len(flat))(*[None if b is None else b._h for b in flat])
+        h = C.c_void_p()
+        _check(lib().pem_tiled_concat(ctx._h, gr, gc, hs, (C.c_int64 * gr)(*rs), (C.c_int64 * gc)(*cs), C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def hstack(cls, blocks):
+        """[B0 B1 ..]: concat of one grid row"""
+        return cls.concat([list(blocks)])
+
+    @classmethod
+    def vstack(cls, blocks):
+        """[B0; B1; ..]: concat of one grid column"""
+        return cls.concat([[b] for b in blocks])
+
+    def set_values_from_concat(self, blocks):
+        """Refresh a tiling made by concat(blocks, ...) from the blocks' current values, in place: the same grid again (a list of
+        lists), None where the build had None.  Ordered on the context's stream; returns without waiting."""
+        flat = [b for row in blocks for b in row]
+        hs = (C.c_void_p * max(len(flat), 1))(*[None if b is None else b._h for b in flat])
+        _check(lib().pem_tiled_set_values_from_concat(self.ctx._h, self._h, len(flat), hs))
+
+    def split(self, row_sizes, col_sizes):
+        """The inverse of concat: a list of lists of new tilings, piece (a, b) = rows ro_a .. ro_a + row_sizes[a] - 1 and columns
+        co_b .. co_b + col_sizes[b] - 1 of this one.  Built on extract with slices -- one extract per piece, no kernel of its own.
+        The sizes are integers >= 1 (a tiling has at least one row and one column) and sum to the shape.  Waits."""
+        rs, cs = [int(x) for x in row_sizes], [int(x) for x in col_sizes]
+        for name, s, dim in (("row_sizes", rs, self.rows), ("col_sizes", cs, self.cols)):
+            if not s or any(x < 1 for x in s) or sum(s) != dim:
+                raise ValueError(f"split: {name} must be sizes >= 1 that sum to {dim}, not {s}")
+        ro, co = np.concatenate([[0], np.cumsum(rs)]), np.concatenate([[0], np.cumsum(cs)])
+        return [[self.extract(slice(int(ro[a]), int(ro[a + 1])), slice(int(co[b]), int(co[b + 1]))) for b in range(len(cs))]
+                for a in range(len(rs))]
 
     def select(self, op, thunk=0):
         """Select: a new tiling of this one's shape and dtype holding exactly the stored entries that satisfy

@@ -40,13 +40,8 @@ using namespace pem;
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
-// what the walks read of an operand
-struct KrSide {
-    const int *rowptr, *colidx;   // tile CSR
-    const int *ptr;               // tile_nnz_ptr
-    const uint32_t *rec;          // tile_rec: row mask | entries of the rows above << 16
-    int rows, cols;
-};
+// (what the walks read of an operand is a TileSide; a row's 32 columns from a tile column on come from row_seg / seg_slot:
+// tiled_internal.h, shared with concat.hip)
 
 // One lane per (A entry ea, B tile tb), x = ea * tb_count + tb.  The pair's block of R is rows i*mB + 16K .. (clipped at B's last
 // row) and columns j*nB + 16L .. alike: 1 or 2 tile rows times 1 or 2 tile columns.  coff == null: cnt[x] = that count.  Else:
@@ -83,40 +78,10 @@ __global__ void __launch_bounds__(256) kr_cand_kernel(const long long *__restric
         for (long long Q = Q0; Q <= Q1; ++Q) *out++ = ((uint64_t)P << bits_tc) | (uint64_t)Q;
 }
 
-// the 32 columns of row `row` of a tiling that start at tile column tc: the row's masks there (bit b = column 16 tc + b) and, for
-// the value slots, the two tiles' tile_rec words and first entries
-struct KrSeg {
-    uint32_t m, rec0, rec1;
-    int off0, off1;
-};
-__device__ __forceinline__ KrSeg kr_seg(const KrSide &S, const int row, const int tc)
-{
-    const int tr = row >> 4, r = row & 15;
-    KrSeg s = {0u, 0u, 0u, 0, 0};
-    int t = tile_lower_bound(S.rowptr, S.colidx, tr, tc);
-    const int end = S.rowptr[tr + 1];
-    if (t < end && S.colidx[t] == tc) {
-        s.rec0 = S.rec[16 * (size_t)t + r];
-        s.off0 = S.ptr[t];
-        ++t;
-    }
-    if (t < end && S.colidx[t] == tc + 1) {
-        s.rec1 = S.rec[16 * (size_t)t + r];
-        s.off1 = S.ptr[t];
-    }
-    s.m = (s.rec0 & 0xFFFFu) | (s.rec1 << 16);
-    return s;
-}
-// the slot in the tiling's vals of the segment's stored column b (0 .. 31)
-__device__ __forceinline__ int kr_slot(const KrSeg &s, const unsigned b)
-{
-    return b < 16u ? src_slot(s.off0, s.rec0, b) : src_slot(s.off1, s.rec1, b - 16u);
-}
-
 // Row p of R in the tile column Q: the walk over the stored A(i, j) whose block reaches the tile and, for each, over B's row k there.
 // Returns the row's 16-bit mask.  FILL: also writes the row's entries from slot e on, never at or past e_end.
 template <bool FILL, typename VT>
-__device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, const long long p, const long long Q, const int r, const int op,
+__device__ __forceinline__ unsigned kr_walk(const TileSide &A, const TileSide &B, const long long p, const long long Q, const int r, const int op,
                                             const VT *__restrict__ a_vals, const VT *__restrict__ b_vals, int e, const int e0, const int e_end,
                                             const int tile, uint8_t *__restrict__ rowcolidx, int *__restrict__ headx, VT *__restrict__ vals)
 {
@@ -127,10 +92,10 @@ __device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, co
     const long long q1 = q0 + 15 < qn ? q0 + 15 : qn;
     const int jlo = (int)((unsigned)q0 / nB), jhi = (int)((unsigned)q1 / nB);   // jhi - jlo <= 15, jhi < A.cols
     const int abase = jlo >> 4;
-    const KrSeg sa = kr_seg(A, (int)i, abase);
+    const RowSeg sa = row_seg(A, (int)i, abase);
     unsigned rowmask = 0u;
     int bc = -1;
-    KrSeg sb = {0u, 0u, 0u, 0, 0};
+    RowSeg sb = {0u, 0u, 0u, 0, 0};
     for (int j = jlo; j <= jhi; ++j) {
         const unsigned ab = (unsigned)(j - 16 * abase);   // <= 15 + 15
         if (!((sa.m >> ab) & 1u)) continue;
@@ -139,7 +104,7 @@ __device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, co
         const long long lhi = 15 - off < (long long)nB - 1 ? 15 - off : (long long)nB - 1;   // llo <= lhi <= llo + 15
         const int c = (int)(llo >> 4);
         if (c != bc) {
-            sb = kr_seg(B, (int)k, c);
+            sb = row_seg(B, (int)k, c);
             bc = c;
         }
         const unsigned sh = (unsigned)(llo - 16 * (long long)c);           // B's column llo in the segment: 0 .. 15
@@ -149,14 +114,14 @@ __device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, co
         rowmask |= bits << place;
         if constexpr (FILL) {
             if (!bits) continue;
-            const VT a = a_vals[kr_slot(sa, ab)];
+            const VT a = a_vals[seg_slot(sa, ab)];
             while (bits) {
                 const unsigned b = (unsigned)__builtin_ctz(bits);
                 bits &= bits - 1u;
                 if (e < e_end) {   // (the masks and the offsets come from the same counts; never write past the tile)
                     rowcolidx[e] = (uint8_t)((r << 4) | (int)(place + b));
                     headx[e] = e == e0 ? tile : tile + 1;
-                    vals[e] = pem_binop_value<VT>(op, a, b_vals[kr_slot(sb, sh + b)]);
+                    vals[e] = pem_binop_value<VT>(op, a, b_vals[seg_slot(sb, sh + b)]);
                 }
                 ++e;
             }
@@ -167,7 +132,7 @@ __device__ __forceinline__ unsigned kr_walk(const KrSide &A, const KrSide &B, co
 
 // 16 lanes per candidate c, lane = local row r: rmask[16c + r] = the row's mask, cnt[c] = the tile's entries, flag[c] = it has any.
 // A candidate equal to the one before it is a duplicate and has none.
-__global__ void __launch_bounds__(256) kr_count_kernel(const uint64_t *__restrict__ keys, long long ncand, KrSide A, KrSide B, long long r_rows,
+__global__ void __launch_bounds__(256) kr_count_kernel(const uint64_t *__restrict__ keys, long long ncand, TileSide A, TileSide B, long long r_rows,
                                                        int bits_tc, uint16_t *__restrict__ rmask, int *__restrict__ cnt, int *__restrict__ flag)
 {
     const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -193,7 +158,7 @@ __global__ void __launch_bounds__(256) kr_count_kernel(const uint64_t *__restric
 // 16 lanes per candidate, lane = local row r.  roff / rid = the scanned counts / flags (ncand + 1 values each: roff[ncand] = the
 // result's entries, rid[ncand] = its tiles).
 template <typename VT>
-__global__ void __launch_bounds__(256) kr_fill_kernel(const uint64_t *__restrict__ keys, long long ncand, KrSide A, KrSide B, int bits_tc, int op,
+__global__ void __launch_bounds__(256) kr_fill_kernel(const uint64_t *__restrict__ keys, long long ncand, TileSide A, TileSide B, int bits_tc, int op,
                                                       const VT *__restrict__ a_vals, const VT *__restrict__ b_vals,
                                                       const uint16_t *__restrict__ rmask, const int *__restrict__ roff, const int *__restrict__ rid,
                                                       long long *__restrict__ tile_keys, int *__restrict__ tile_nnz_ptr,
@@ -231,7 +196,7 @@ __global__ void __launch_bounds__(256) kr_fill_kernel(const uint64_t *__restrict
 // the refresh map, once: one wave per chunk of 64 consecutive R tiles, one entry of R per lane (ex_map_kernel's shape).  Entry
 // (p, q) of R is A(p / mB, q / nB) op B(p % mB, q % nB): each operand's tile by mask_find_tile, its slot by src_slot.
 __global__ void __launch_bounds__(256) kr_map_kernel(const long long *__restrict__ r_keys, long long nt, const int *__restrict__ r_ptr,
-                                                     const uint8_t *__restrict__ r_rci, KrSide A, KrSide B, int2 *__restrict__ map)
+                                                     const uint8_t *__restrict__ r_rci, TileSide A, TileSide B, int2 *__restrict__ map)
 {
     const int lane = threadIdx.x & 63;
     const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
@@ -263,9 +228,9 @@ __global__ void __launch_bounds__(256) kr_map_kernel(const long long *__restrict
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static KrSide side_of(const pem_tiled *T)
+static TileSide side_of(const pem_tiled *T)
 {
-    return KrSide{T->tile_rowptr.as<int>(), T->tile_colidx.as<int>(), T->tile_nnz_ptr.as<int>(), T->tile_rec.as<uint32_t>(), T->rows, T->cols};
+    return TileSide{T->tile_rowptr.as<int>(), T->tile_colidx.as<int>(), T->tile_nnz_ptr.as<int>(), T->tile_rec.as<uint32_t>(), T->rows, T->cols};
 }
 
 // the arguments were checked (kron_sizes_ok): the dimensions and nnz(A) * nnz(B) fit an int32

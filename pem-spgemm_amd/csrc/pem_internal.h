@@ -323,10 +323,17 @@ uint64_t next_tiled_serial();
 //                                              permutation (sorted position -> input index), kept by the build.  idx[0]: int32[nnz + 1],
 //                                              run_start -- entry s folds the sorted positions run_start[s] .. run_start[s + 1] - 1.
 //                                              No source tiling: the values are an argument of every refresh.
+//   CONCAT  pem_tiled_concat (concat.hip)      srcs = the grid's serials, row-major (0: a null cell); op = grid_rows, pattern =
+//                                              grid_cols.  idx[0]: int64[grid_rows + 1 + grid_cols + 1], the exclusive prefix sums of
+//                                              the row sizes, then of the column sizes.  src_tiles: the cell table (CcCell per cell)
+//                                              of the build, which the first refresh's map kernel reads again.  idx[1] (first
+//                                              refresh): a pointer per cell, the blocks' vals, rewritten by every refresh.
+//                                              map: int2[nnz], every entry's (cell, slot in that block's vals).
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK, BUILD } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK, BUILD, CONCAT } kind = NONE;
     uint64_t src[2] = {0, 0};
+    std::vector<uint64_t> srcs;   // CONCAT: one serial per grid cell
     int op = 0, pattern = 0;
     double p0 = 0.0, p1 = 0.0;
     DevBuf src_tiles, map, idx[2];

@@ -1,5 +1,5 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.  build.hip shares the
 // HEAD of pem_tiled_from_coo* (coo_sort_keys, then the radix sort) and this tail; its payload kernel is its own, because it compacts the
@@ -174,6 +174,45 @@ __device__ __forceinline__ uint4 row_prefixes(const unsigned w[8])
 __device__ __forceinline__ int src_slot(const int off, const uint32_t rec, const unsigned c)
 {
     return off + (int)(rec >> 16) + __popc(rec & ((1u << c) - 1u));
+}
+
+// ---- device: a row of a tiling read as masks, 32 columns at a time (kron.hip, concat.hip) ----
+// what such a walk reads of a tiling
+struct TileSide {
+    const int *rowptr, *colidx;   // tile CSR
+    const int *ptr;               // tile_nnz_ptr
+    const uint32_t *rec;          // tile_rec: row mask | entries of the rows above << 16
+    int rows, cols;
+};
+
+// the 32 columns of row `row` of a tiling that start at tile column tc: the row's masks there (bit b = column 16 tc + b) and, for
+// the value slots, the two tiles' tile_rec words and first entries
+struct RowSeg {
+    uint32_t m, rec0, rec1;
+    int off0, off1;
+};
+__device__ __forceinline__ RowSeg row_seg(const TileSide &S, const int row, const int tc)
+{
+    const int tr = row >> 4, r = row & 15;
+    RowSeg s = {0u, 0u, 0u, 0, 0};
+    int t = tile_lower_bound(S.rowptr, S.colidx, tr, tc);
+    const int end = S.rowptr[tr + 1];
+    if (t < end && S.colidx[t] == tc) {
+        s.rec0 = S.rec[16 * (size_t)t + r];
+        s.off0 = S.ptr[t];
+        ++t;
+    }
+    if (t < end && S.colidx[t] == tc + 1) {
+        s.rec1 = S.rec[16 * (size_t)t + r];
+        s.off1 = S.ptr[t];
+    }
+    s.m = (s.rec0 & 0xFFFFu) | (s.rec1 << 16);
+    return s;
+}
+// the slot in the tiling's vals of the segment's stored column b (0 .. 31)
+__device__ __forceinline__ int seg_slot(const RowSeg &s, const unsigned b)
+{
+    return b < 16u ? src_slot(s.off0, s.rec0, b) : src_slot(s.off1, s.rec1, b - 16u);
 }
 
 }  // namespace pem

@@ -64,6 +64,7 @@ static const char *const dim_names[] = {"rows", "cols"};                        
 static const char *const scale_flags[2] = {"--row-scale", "--col-scale"};
 static const char *const extract_flags[2] = {"--extract-rows", "--extract-cols"};
 static const char *const assign_flags[2] = {"--assign-rows", "--assign-cols"};
+static const char *const stack_flags[2] = {"--hstack", "--vstack"};
 
 struct Options {
     // Beyond the reference: `--B <file.mtx>` multiplies by a second matrix instead of A itself,
@@ -98,6 +99,7 @@ struct Options {
     const char *assign_into = nullptr, *assign_accum_name = nullptr;   // --assign-into D.mtx, --assign-accum OP: see assign_stage
     const char *assign_paths[2] = {nullptr, nullptr};               // --assign-rows I.mtx, --assign-cols J.mtx
     const char *kron_path = nullptr, *kron_op_name = nullptr;       // --kron K.mtx [--kron-op OP]: see kron_stage
+    const char *stack_paths[2] = {nullptr, nullptr};                // --hstack F.mtx, --vstack F.mtx: see stack_stage
     const char *dup_name = nullptr;                                 // --dup OP: see tiling_from_coo
     const char *reduce_spec = nullptr;                              // --reduce rows|cols[:OP]: see reduce_stage
     const char *bfs_spec = nullptr;                                 // --bfs SRC: see bfs_stage
@@ -146,7 +148,7 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
-                  {"--dup", &o->dup_name}};
+                  {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -192,6 +194,8 @@ static const struct ClashRule {
     {"--col-scale", {"--gpus", "--power"}, ""},
     {"--kron", {"--gpus"}, ""},
     {"--topk", {"--gpus", "--power"}, ""},
+    {"--hstack", {"--gpus", "--vstack"}, ""},
+    {"--vstack", {"--gpus"}, ""},
     {"--dup", {"--gpus", "--cache"}, ""},   // (a cached tiling would depend on the op, which its key does not carry)
 };
 
@@ -204,7 +208,7 @@ static bool clashes(const Options &o, const char *flag)
     } given[] = {{"--gpus", o.ngpu > 0},       {"--mask", o.mask_path != nullptr}, {"--power", o.power != 0},
                  {"--B", o.b_path != nullptr}, {"the A*A^T argument", o.aat},      {"--reduce", o.reduce_spec != nullptr},
                  {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr},
-                 {"--cache", o.cache_dir != nullptr}};
+                 {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -510,6 +514,14 @@ static int validate_kron(Options *o)
     return 0;
 }
 
+// --hstack / --vstack: one of the two, on one device; the file itself is read with the operands
+static int validate_stack(Options *o)
+{
+    for (int k = 0; k < 2; ++k)
+        if (o->stack_paths[k] && clashes(*o, stack_flags[k])) return 1;
+    return 0;
+}
+
 // --topk DIM:ORDER:K: the dimension (pem_reduce_dim) and the order (pem_topk_order) by name, K an integer >= 0
 static int validate_topk(Options *o)
 {
@@ -561,7 +573,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk, validate_dup})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk, validate_dup, validate_stack})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -1152,7 +1164,7 @@ static int run_gpus(const Options &o)
 // The single-device path: the operands, then one function per stage, each leaving what it made in Result.
 // ------------------------------------------------------------------------------------------------------------------
 struct Operands {
-    Tiled A, B_own, Mt, Dt, Into, Kt;   // B_own: B when it is a tiling of its own; Mt the mask, Dt --add's D, Into --assign-into's D, Kt --kron's K
+    Tiled A, B_own, Mt, Dt, Into, Kt, St;   // B_own: B when it is a tiling of its own; Mt the mask, Dt --add's D, Into --assign-into's D, Kt --kron's K, St --hstack's / --vstack's F
     pem_tiled *B = nullptr;
     pem_tiled_info ia, ib;
     double conv_ms = 0.0;
@@ -1161,7 +1173,7 @@ struct Operands {
 struct Result {
     Tiled L_own;              // --power: A^(K-1), the last product's left operand
     pem_tiled *L = nullptr;   // A otherwise
-    Tiled sum, app, scl, sel, top, ext, asg, krn, sd;   // what --add, --apply, --row/col-scale, --select, --topk, --extract-*, --assign-into, --kron and --sddmm made
+    Tiled sum, app, scl, sel, top, ext, asg, krn, stk, sd;   // what --add, --apply, --row/col-scale, --select, --topk, --extract-*, --assign-into, --kron, --hstack / --vstack and --sddmm made
     Plan plan;
     pem_cplan_info ci;
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
@@ -1237,7 +1249,8 @@ static int make_tiling(const Options &o, pem_ctx *ctx, Source &src, int transpos
     return 0;
 }
 
-// A, B, the mask, the D of --add and of --assign-into and the K of --kron, the header lines, and the conversion time
+// A, B, the mask, the D of --add and of --assign-into, the K of --kron and the F of --hstack / --vstack, the header lines, and the
+// conversion time
 static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
 {
     auto conv_start = Clock::now();   // spgemm.cu:760: the clock starts before the file is read
@@ -1259,7 +1272,7 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
             printf("input is rectangular. Only AAt is possible. Exiting.\n");   // spgemm.cu:782-786
         return 1;
     }
-    Coo cm, cd, cinto, ck;
+    Coo cm, cd, cinto, ck, cs;
     if (o.mask_path) {   // M's structure (its values are never read, so it is converted as fp64 whatever --fp32 says)
         if (read_input(o, o.mask_path, &cm) != 0) return 1;
         if (cm.rows != ia.rows || cm.cols != ib.cols) {
@@ -1285,6 +1298,10 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
     if (o.kron_path) {   // K, in the value type of A
         if (read_input(o, o.kron_path, &ck) != 0) return 1;
         if (int rc = convert_or_refuse(ctx, o.kron_path, ck, o.fp32, 0, o.dup, &in->Kt)) return rc;
+    }
+    if (const char *path = o.stack_paths[0] ? o.stack_paths[0] : o.stack_paths[1]) {   // F, in the value type of A
+        if (read_input(o, path, &cs) != 0) return 1;
+        if (int rc = convert_or_refuse(ctx, path, cs, o.fp32, 0, o.dup, &in->St)) return rc;
     }
     if (o.fp32) printf("value type: fp32 (the reference computes in fp64)\n");
     printf("MATRIX A\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", o.input(), ia.rows, ia.cols, (long long)ia.nnz);   // spgemm.cu:794-806
@@ -1613,6 +1630,42 @@ static int kron_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result
     return 0;
 }
 
+// `--hstack F.mtx` / `--vstack F.mtx`: after the product and every stage above, the final result R becomes
+// [R F] resp. [R; F] on the device (pem_tiled_concat, a 1 x 2 resp. 2 x 1 grid).  F is read with --fp32 like A and must have R's row
+// resp. column count.  --reduce, --bfs, --spmm, --sddmm, --out and the sorted COO files then see that tiling.  The CSV row describes
+// the product.
+static int stack_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
+{
+    const int v = o.stack_paths[1] ? 1 : 0;
+    auto s0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    pem_tiled_info fi;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    CHECK(pem_tiled_get_info(in.St.get(), &fi));
+    if (v ? fi.cols != src.info.cols : fi.rows != src.info.rows) {
+        printf("%s %s is %d x %d but %s is %d x %d: the %s counts differ. Exiting.\n", stack_flags[v], o.stack_paths[v], fi.rows, fi.cols,
+               r->last_name, src.info.rows, src.info.cols, v ? "column" : "row");
+        return 1;
+    }
+    const pem_tiled *const blocks[2] = {src.t, in.St.get()};
+    const int64_t own_rows[2] = {src.info.rows, fi.rows}, own_cols[2] = {src.info.cols, fi.cols};
+    const pem_status s = v ? pem_tiled_concat(ctx, 2, 1, blocks, own_rows, own_cols, out(ctx, r->stk))
+                           : pem_tiled_concat(ctx, 1, 2, blocks, own_rows, own_cols, out(ctx, r->stk));
+    if (s == PEM_E_OVERFLOW) {
+        printf("%s %s: %s. Exiting.\n", stack_flags[v], o.stack_paths[v], pem_last_error());
+        return 1;
+    }
+    CHECK(s);
+    const double stk_total_ms = ms_since(s0);
+    pem_tiled_info si;
+    CHECK(pem_tiled_get_info(r->stk.get(), &si));
+    printf("%s: [%s%s %s]: concat %.2fms, total %.2fms, %d x %d, nnz %lld (the result %lld, F %lld)\n", stack_flags[v] + 2, r->last_name, v ? ";" : "",
+           o.stack_paths[v], si.conv_ms, stk_total_ms, si.rows, si.cols, (long long)si.nnz, (long long)src.info.nnz, (long long)fi.nnz);
+    r->now_last(r->stk, "the stacked matrix");
+    return 0;
+}
+
 // `--reduce rows|cols[:OP]` folds every row or column of the final result (C, the sum of --add, or
 // what --select kept) on the device (pem_tiled_reduce); OP is one of plus times min max lor land and defaults to the semiring's
 // additive op.  --out then writes the vector (Matrix-Market array) instead of the matrix.  The CSV row describes the product.
@@ -1746,7 +1799,7 @@ static int sddmm_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// The sorted COO files of the 2nd argument: the sampled product's, the Kronecker product's or the assigned matrix's entries when
+// The sorted COO files of the 2nd argument: the sampled product's, the stacked matrix's, the Kronecker product's or the assigned matrix's entries when
 // there is one (their CSR export is the sorted (row, column) order), else the plan's C as the reference writes it.
 static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
 {
@@ -1754,9 +1807,9 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
         printf("Not saving results. Exiting.\n");   // spgemm.cu:1487
     } else if (r->sd) {
         r->rc = save_result_files(r->sd_csr.rp, r->sd_csr.ci, r->sd_csr.v);
-    } else if (r->krn || r->asg) {
+    } else if (r->stk || r->krn || r->asg) {
         Csr c;
-        CHECK(export_csr(ctx, r->krn ? r->krn.get() : r->asg.get(), o.fp32, &c));
+        CHECK(export_csr(ctx, r->stk ? r->stk.get() : r->krn ? r->krn.get() : r->asg.get(), o.fp32, &c));
         r->rc = save_result_files(c.rp, c.ci, c.v);
     } else {
         Csr c;   // as COO
@@ -1790,6 +1843,7 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
                (o.assign_paths[1] ? std::string(" columns ") + o.assign_paths[1] : std::string()) +
                (o.assign_accum == PEM_ACCUM_NONE ? std::string() : std::string(" accum ") + binop_names[o.assign_accum]);
     if (r->krn) how += std::string(", kron ") + binop_names[o.kron_op] + " with " + o.kron_path;
+    if (r->stk) how += std::string(o.stack_paths[1] ? ", vstack with " : ", hstack with ") + o.stack_paths[o.stack_paths[1] ? 1 : 0];
     how += " by pemspgemm (pem-spgemm_amd)";
     int rc = 0;
     if (o.bfs_spec) {
@@ -1844,6 +1898,7 @@ int main(int argc, char *argv[])
     if (!rc && (o.extract_paths[0] || o.extract_paths[1])) rc = extract_stage(o, ctx, &r);
     if (!rc && in.Into) rc = assign_stage(o, ctx, in, &r);
     if (!rc && in.Kt) rc = kron_stage(o, ctx, in, &r);
+    if (!rc && in.St) rc = stack_stage(o, ctx, in, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
