@@ -663,6 +663,59 @@ pem_status pem_tiled_mxv_frontier_f32(pem_ctx *ctx, const pem_tiled *A, int semi
                                       float *dy, const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate);
 pem_status pem_tiled_bfs(pem_ctx *ctx, const pem_tiled *A, int64_t source, int transpose, int32_t *d_level, int32_t *depth, int64_t *reached);
 
+/* Arg folds: where the minimum or maximum of a row's or column's fold was attained, next to -- or instead
+ * of -- its value, and the breadth-first tree built on that.
+ *   pem_tiled_mxv_arg  orientation, lengths, coordinates, dx_present, dy_mask / mask_complement, dy_present, stream ordering and scratch
+ *       exactly as pem_tiled_mxv_frontier; dx_present = NULL and dy_mask = NULL give the dense case.  d_idx: ny int32 on the device.
+ *       An entry (i, j) ENTERS the fold of an allowed output when its x is present.  Its x-index is the index into x: the column j
+ *       for transpose = 0, the row i of the represented matrix for transpose = 1.  kind is a pem_arg_kind:
+ *         PEM_ARG_MIN_PLUS   term a_ij + x_j, fold min;   PEM_ARG_MAX_PLUS   term a_ij + x_j, fold max;
+ *         PEM_ARG_MAX_TIMES  term a_ij * x_j, fold max    (the value kinds: each term rounded once in the value type);
+ *         PEM_ARG_MIN_INDEX  the smallest, PEM_ARG_MAX_INDEX the largest x-index of an entering entry (the index kinds: neither A's
+ *                            values nor x are read).
+ *     Value kinds, which terms win.  With accumulate = 0 every non-NaN term wins.  With accumulate = 1 a term t wins over the old y_i
+ *       when the old y_i is NaN or t < y_i (the max kinds: t > y_i).  A NaN term never wins (fmin / fmax skip NaN).
+ *     Value kinds, what an allowed output gets.  Where some term wins, y_i is the best winning term and idx_i the SMALLEST x-index
+ *       among the terms that compare equal (==) to it: +0 and -0 tie and the lower index is reported.  Where no term wins: with
+ *       accumulate = 0 y_i is the start value (+inf / -inf) and idx_i = -1; with accumulate = 1 y_i keeps the old value up to the sign
+ *       of a zero and idx_i is not written.  The value written is what pem_tiled_mxv_frontier writes under the semiring of the same
+ *       name for the same arguments, bit for bit (zero signs and NaN payloads excepted, as stated there).
+ *     Index kinds.  dx and dy are neither read nor written; both may be NULL.  idx_i is the min (max) x-index over the entering
+ *       entries; explicit zeros and NaN are entries like any other.  With accumulate = 1 the old idx_i takes part when it is >= 0.
+ *       With no entering entry idx_i = -1 (accumulate = 0) or stays untouched (accumulate = 1).
+ *     A disallowed output never has y, idx or anything else written.  dy_present follows pem_tiled_mxv_frontier's rule (structural: a
+ *       NaN term counts).  An absent x_j is never read.  A's entries are read once per call; no atomics and no dependence on order:
+ *       two calls give identical bits.
+ *   pem_tiled_reduce_arg  per row (dim = PEM_REDUCE_ROWS) or column (PEM_REDUCE_COLS) the min (op = PEM_BINOP_MIN) or max
+ *       (PEM_BINOP_MAX) stored value, and the smallest index inside the line where a stored value equals it; an empty line, or one
+ *       whose values are all NaN, gets the identity and -1.  The values equal pem_tiled_reduce(MIN | MAX); the whole result equals
+ *       pem_tiled_mxv_arg(MIN_PLUS | MAX_PLUS) with x = 0 and the same orientation (no x is allocated or read).
+ *   PEM_E_INVALID, before the device is touched: the null, flag, value-type and overlap cases of pem_tiled_mxv_frontier; an unknown
+ *     kind, op (only MIN and MAX have an arg) or dim; a null d_idx; under a value kind a null dy where y has entries or a null dx
+ *     where x has entries; d_idx's bytes overlapping any other argument's (dx and dy do not count under an index kind).  An empty
+ *     tiling and a 0-length output are legal.
+ *   pem_tiled_bfs_parents  pem_tiled_bfs with the breadth-first tree: the argument checks and level semantics of pem_tiled_bfs, and
+ *       d_level, *depth and *reached identical to its.  d_parent: A.rows int32 on the device, not overlapping d_level (else
+ *       PEM_E_INVALID): d_parent[source] = source, -1 where v is unreachable, otherwise the smallest-numbered u of the previous level
+ *       with an edge u -> v, which is deterministic.  Every level is one arg walk under PEM_ARG_MIN_INDEX (frontier = dx_present,
+ *       visited = the complemented mask, the index written straight into d_parent, next frontier = dy_present) and one 4-byte
+ *       read-back; no value is read.  Waits. */
+typedef enum {
+    PEM_ARG_MIN_PLUS = 0,
+    PEM_ARG_MAX_PLUS = 1,
+    PEM_ARG_MAX_TIMES = 2,
+    PEM_ARG_MIN_INDEX = 3,
+    PEM_ARG_MAX_INDEX = 4
+} pem_arg_kind;
+pem_status pem_tiled_mxv_arg(pem_ctx *ctx, const pem_tiled *A, int kind, int transpose, const double *dx, const uint8_t *dx_present, double *dy,
+                             int32_t *d_idx, const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate);
+pem_status pem_tiled_mxv_arg_f32(pem_ctx *ctx, const pem_tiled *A, int kind, int transpose, const float *dx, const uint8_t *dx_present, float *dy,
+                                 int32_t *d_idx, const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate);
+pem_status pem_tiled_reduce_arg(pem_ctx *ctx, const pem_tiled *A, int op, int dim, double *dy, int32_t *d_idx);
+pem_status pem_tiled_reduce_arg_f32(pem_ctx *ctx, const pem_tiled *A, int op, int dim, float *dy, int32_t *d_idx);
+pem_status pem_tiled_bfs_parents(pem_ctx *ctx, const pem_tiled *A, int64_t source, int transpose, int32_t *d_level, int32_t *d_parent,
+                                 int32_t *depth, int64_t *reached);
+
 /* Sparse times dense block: a tiling times k dense device vectors at once under a semiring.
  *   pem_tiled_spmm  Y = A (+).(x) X  (transpose = 0: X is A.cols x k, Y is A.rows x k)
  *                   Y = A^T (+).(x) X  (transpose = 1: X is A.rows x k, Y is A.cols x k)

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_from_scale_f32", "pem_tiled_kron", "pem_tiled_set_values_from_kron", "pem_tiled_select_topk",
     "pem_tiled_build", "pem_tiled_build_f32", "pem_tiled_build_device", "pem_tiled_build_device_f32", "pem_tiled_set_values_from_build",
     "pem_tiled_set_values_from_build_f32", "pem_tiled_concat", "pem_tiled_set_values_from_concat",
+    "pem_tiled_mxv_arg", "pem_tiled_mxv_arg_f32", "pem_tiled_reduce_arg", "pem_tiled_reduce_arg_f32", "pem_tiled_bfs_parents",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -86,6 +87,10 @@ APPLY_OPS = ("identity", "abs", "ainv", "minv", "sqrt", "one", "plus", "times", 
 
 # enum pem_reduce_dim (include/pem_spgemm.h): Tiled.reduce folds every row or every column
 REDUCE_DIMS = dict(rows=0, cols=1)
+
+# enum pem_arg_kind (include/pem_spgemm.h): Tiled.mxv_arg's kinds, by value; the last two read no value
+ARG_KINDS = ("min_plus", "max_plus", "max_times", "min_index", "max_index")
+INDEX_ARG_KINDS = ARG_KINDS[3:]
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
 VALUE_ORDERS = dict(row=0, col=1)
@@ -752,6 +757,78 @@ class Tiled:
         _check(lib().pem_tiled_bfs(self.ctx._h, self._h, C.c_int64(int(source)), int(bool(transpose)), C.c_void_p(levels.data_ptr() or 1),
                                    C.byref(depth), C.byref(reached)))
         return levels, depth.value, reached.value
+
+    def _index_out(self, fn, name, out, n, like=None):
+        """(tensor, device pointer) of a contiguous torch.int32 tensor of n entries on the context's device, allocated when None"""
+        import torch
+        if out is None:
+            dev = like.device if like is not None else torch.device("cuda", self.ctx.device)
+            out = torch.empty(n, dtype=torch.int32, device=dev)
+        if (not hasattr(out, "data_ptr") or not out.is_cuda or out.device.index != self.ctx.device or out.numel() != n or out.dim() != 1
+                or not out.is_contiguous() or out.dtype != torch.int32):
+            got = f"{out.dtype} of shape {tuple(out.shape)} on {out.device}" if hasattr(out, "data_ptr") else type(out).__name__
+            raise ValueError(f"{fn}: want a contiguous device tensor of {n} int32 values on cuda:{self.ctx.device} for {name}, got {got}")
+        return out, C.c_void_p(out.data_ptr() or 1)
+
+    def mxv_arg(self, x, kind="min_plus", transpose=False, x_present=None, mask=None, mask_complement=False, out=None, out_index=None,
+                out_present=None, accumulate=False):
+        """Arg fold: mxv_frontier under min_plus / max_plus / max_times that also says where the minimum
+        (maximum) was attained, or -- kind "min_index" / "max_index" -- only the smallest (largest) index into x of an entry that
+        enters the fold.  x, x_present, mask, mask_complement, out, out_present, transpose and accumulate: as for mxv_frontier (no
+        x_present and no mask: the dense case).  out_index: a contiguous device torch.int32 tensor of out's length, allocated when
+        None.  Returns (out, out_index).  Under a value kind out is what mxv_frontier writes and out_index[i] the smallest index j
+        whose term equals it -- ties go to the lower index, +0 == -0 -- or -1 where no term won (accumulate=True: left as it was, and
+        a term wins only where it is strictly better than the old out[i] or that is NaN).  Under an index kind x may be None, no value
+        is read, out is None, and with accumulate=True an old out_index[i] >= 0 takes part.  A disallowed output has nothing written.
+        Ordered on the context's stream and never waits (see mxv)."""
+        if kind not in ARG_KINDS:
+            raise ValueError(f"unknown kind {kind!r}; one of {list(ARG_KINDS)}")
+        values = kind not in INDEX_ARG_KINDS
+        nx, ny = (self.rows, self.cols) if transpose else (self.cols, self.rows)
+        px = self._vector("mxv_arg", "x", x, nx) if values or x is not None else None
+        pxp = self._bytes("mxv_arg", "x_present", x_present, nx)
+        pm = self._bytes("mxv_arg", "mask", mask, ny)
+        pyp = self._bytes("mxv_arg", "out_present", out_present, ny)
+        like = next((t for t in (x, x_present, mask, out_present, out_index) if t is not None), None)
+        py = None
+        if values:
+            out, py = self._out("mxv_arg", out, ny, like=like)
+        elif out is not None:
+            raise ValueError(f"mxv_arg: kind {kind!r} writes no value; out must be None")
+        out_index, pi = self._index_out("mxv_arg", "out_index", out_index, ny, like=like)
+        fn = lib().pem_tiled_mxv_arg_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv_arg
+        _check(fn(self.ctx._h, self._h, ARG_KINDS.index(kind), int(bool(transpose)), px if values else None, pxp, py, pi, pm,
+                  int(bool(mask_complement)), pyp, int(bool(accumulate))))
+        return out, out_index
+
+    def reduce_arg(self, op="max", dim="rows"):
+        """Arg reduction: (y, idx) with y[i] the min (op="min") or max of row i's (dim="cols": column
+        i's) stored values -- A.reduce(op, dim)'s values -- and idx[i], torch.int32, the smallest index inside the line where a stored
+        value equals it; an empty or all-NaN line gives the identity and -1.  Ordered on the context's stream and never waits."""
+        if op not in ("min", "max"):
+            raise ValueError(f"unknown op {op!r}; 'min' or 'max'")
+        if dim not in REDUCE_DIMS:
+            raise ValueError(f"unknown dim {dim!r}; one of {sorted(REDUCE_DIMS)}")
+        n = self.cols if dim == "cols" else self.rows
+        out, py = self._out("reduce_arg", None, n)
+        idx, pi = self._index_out("reduce_arg", "idx", None, n)
+        fn = lib().pem_tiled_reduce_arg_f32 if self.value_bytes == 4 else lib().pem_tiled_reduce_arg
+        _check(fn(self.ctx._h, self._h, BINOPS[op], REDUCE_DIMS[dim], py, pi))
+        return out, idx
+
+    def bfs_parents(self, source, transpose=False):
+        """bfs with the breadth-first tree.  Returns (levels, parents, depth, reached): levels, depth and
+        reached are bfs's; parents is an int32 device torch tensor with parents[source] = source, -1 where a vertex is unreachable,
+        and otherwise the smallest-numbered vertex of the previous level with an edge to it.  Waits."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        levels = torch.empty(self.rows, dtype=torch.int32, device=dev)
+        parents = torch.empty(self.rows, dtype=torch.int32, device=dev)
+        depth, reached = C.c_int32(), C.c_int64()
+        _check(lib().pem_tiled_bfs_parents(self.ctx._h, self._h, C.c_int64(int(source)), int(bool(transpose)),
+                                           C.c_void_p(levels.data_ptr() or 1), C.c_void_p(parents.data_ptr() or 1), C.byref(depth),
+                                           C.byref(reached)))
+        return levels, parents, depth.value, reached.value
 
     def _block(self, fn, name, v, n, k=None, dtype=None):
         """(k, ld) of a 2-D row-major device torch tensor of dtype (None: this tiling's) with n rows (and k columns): stride(1) == 1

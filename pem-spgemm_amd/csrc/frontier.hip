@@ -69,13 +69,6 @@ __global__ void __launch_bounds__(256) fr_mark_kernel(const uint16_t *__restrict
 // ------------------------------------------------------------------------------------------
 // the walk (mxv_kernel's, mxv.hip, with the dead entries left out)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void fr_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // mxv_kernel's arguments, and: words[tile's minor index] the x segment's presence word, line_flag[L] (both unread under ALLX);
 // mask / complement: the allowed outputs (null: all); ypres: 1 where an allowed output got a term, else 0 (null: not wanted)
 template <typename VT, int K, bool COL, bool ALLX>
@@ -152,7 +145,7 @@ __global__ void __launch_bounds__(256) frontier_kernel(const int *__restrict__ l
                     }
                     run += n;
                 }
-                fr_wave_sync();   // the previous staged chunk's chain has read the staging area
+                mx_wave_sync();   // the previous staged chunk's chain has read the staging area
                 if (major < 16) {
                     if constexpr (Op::pair) {
                         my_t[slot] = a;
@@ -161,7 +154,7 @@ __global__ void __launch_bounds__(256) frontier_kernel(const int *__restrict__ l
                         my_t[slot] = Op::template term<VT>(a, xv);
                     }
                 }
-                fr_wave_sync();
+                mx_wave_sync();
                 touched |= my_cnt;
                 const VT *pt = my_t + my_first;
                 const VT *px = my_x + (Op::pair ? my_first : 0);
@@ -197,6 +190,39 @@ __global__ void __launch_bounds__(256) frontier_kernel(const int *__restrict__ l
     {FR_NAMES(vt, "plus_times"), FR_NAMES(vt, "min_plus"), FR_NAMES(vt, "max_plus"), FR_NAMES(vt, "max_times"), FR_NAMES(vt, "plus_pair"), \
      FR_NAMES(vt, "lor_land")}
 static const char *const kFrNames[2][6][2][2] = {FR_NAMES_VT("float"), FR_NAMES_VT("double")};
+
+pem_status pem::fr_prepare(pem_ctx *ctx, const pem_tiled *A, bool col, const uint8_t *xpres, const uint16_t **words_out, const uint8_t **flags_out)
+{
+    const long long nx = col ? A->rows : A->cols;
+    const long long nlines = col ? A->tile_cols : A->tile_rows;
+    const long long nseg = (nx + 15) / 16;   // the other orientation's lines
+    ctx->fr_lines = xpres ? nlines : -1;
+    *words_out = nullptr;
+    *flags_out = nullptr;
+    if (col) PEM_TRY(ensure_mx_cols(ctx, A));
+    if (!xpres) return PEM_OK;
+    const size_t wbytes = ((size_t)nseg * 2 + 255) & ~size_t(255);
+    PEM_TRY(ctx->fr_scratch.reserve(wbytes + (size_t)nlines));
+    uint16_t *words = ctx->fr_scratch.as<uint16_t>();
+    uint8_t *flags = ctx->fr_scratch.as<uint8_t>() + wbytes;
+    ctx->fr_flags_off = wbytes;
+    PEM_HIP(hipMemsetAsync(flags, 0, (size_t)nlines, ctx->stream));
+    if (nseg) {
+        const int vec = ((uintptr_t)xpres & 15u) == 0;
+        PEM_LAUNCH(ctx, fr_pack_kernel, grid_for((size_t)nseg, 256), 256, xpres, nx, nseg, vec, words);
+        if (A->ntiles) {
+            if (col)
+                PEM_LAUNCH(ctx, fr_mark_kernel, grid_for((size_t)nseg * 16, 256), 256, words, nseg, A->tile_rowptr.as<int>(),
+                           A->tile_colidx.as<int>(), flags, nlines);
+            else
+                PEM_LAUNCH(ctx, fr_mark_kernel, grid_for((size_t)nseg * 16, 256), 256, words, nseg, A->tile_colptr.as<int>(),
+                           A->tile_rowidx.as<int>(), flags, nlines);
+        }
+    }
+    *words_out = words;
+    *flags_out = flags;
+    return PEM_OK;
+}
 
 namespace {
 
@@ -241,38 +267,16 @@ void fr_launch(pem_ctx *ctx, const pem_tiled *A, bool col, const FrArgs &f, cons
     }
 }
 
-// the call for checked arguments, inside PEM_ENTER: scratch, pack, mark, walk.  Stream-ordered, no read-back.
+// the call for checked arguments, inside PEM_ENTER: scratch, pack, mark (fr_prepare), walk.  Stream-ordered, no read-back.
 template <typename VT>
 pem_status fr_run(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const FrArgs &f)
 {
-    const long long nx = col ? A->rows : A->cols;
     const long long nlines = col ? A->tile_cols : A->tile_rows;
-    const long long nseg = (nx + 15) / 16;   // the other orientation's lines
     ctx->fr_lines = f.xpres ? nlines : -1;
     if (nlines == 0) return PEM_OK;   // no output
-    if (col) PEM_TRY(ensure_mx_cols(ctx, A));
-    uint16_t *words = nullptr;
-    uint8_t *flags = nullptr;
-    if (f.xpres) {
-        const size_t wbytes = ((size_t)nseg * 2 + 255) & ~size_t(255);
-        PEM_TRY(ctx->fr_scratch.reserve(wbytes + (size_t)nlines));
-        words = ctx->fr_scratch.as<uint16_t>();
-        flags = ctx->fr_scratch.as<uint8_t>() + wbytes;
-        ctx->fr_flags_off = wbytes;
-        PEM_HIP(hipMemsetAsync(flags, 0, (size_t)nlines, ctx->stream));
-        if (nseg) {
-            const int vec = ((uintptr_t)f.xpres & 15u) == 0;
-            PEM_LAUNCH(ctx, fr_pack_kernel, grid_for((size_t)nseg, 256), 256, f.xpres, nx, nseg, vec, words);
-            if (A->ntiles) {
-                if (col)
-                    PEM_LAUNCH(ctx, fr_mark_kernel, grid_for((size_t)nseg * 16, 256), 256, words, nseg, A->tile_rowptr.as<int>(),
-                               A->tile_colidx.as<int>(), flags, nlines);
-                else
-                    PEM_LAUNCH(ctx, fr_mark_kernel, grid_for((size_t)nseg * 16, 256), 256, words, nseg, A->tile_colptr.as<int>(),
-                               A->tile_rowidx.as<int>(), flags, nlines);
-            }
-        }
-    }
+    const uint16_t *words = nullptr;
+    const uint8_t *flags = nullptr;
+    PEM_TRY(fr_prepare(ctx, A, col, f.xpres, &words, &flags));
     switch (semiring) {
     case 0: fr_launch<VT, 0>(ctx, A, col, f, words, flags); break;
     case 1: fr_launch<VT, 1>(ctx, A, col, f, words, flags); break;
@@ -283,14 +287,6 @@ pem_status fr_run(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, cons
     }
     return PEM_OK;
 }
-
-bool fr_flag_ok(int v) { return v == 0 || v == 1; }
-
-struct Span {
-    const char *lo, *hi;
-    Span(const void *p, size_t bytes) : lo((const char *)p), hi((const char *)p + (p ? bytes : 0)) {}
-    bool meets(const Span &o) const { return lo < hi && o.lo < o.hi && lo < o.hi && o.lo < hi; }
-};
 
 pem_status fr_common(pem_ctx *ctx, const pem_tiled *A, int semiring, int transpose, const void *dx, const uint8_t *dx_present, void *dy,
                      const uint8_t *dy_mask, int mask_complement, uint8_t *dy_present, int accumulate, int vb, const char *fn)

@@ -1,5 +1,6 @@
-// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip, sddmm.hip): the folds of the
-// matrix-vector products and reductions, the column-walk schedule, and the span of a dense row-major block.  SpMM folds with the
+// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip, sddmm.hip, frontier.hip, argmxv.hip):
+// the folds of the matrix-vector products and reductions, the wave sync around the staging area, the column-walk schedule, the
+// frontier's pack and mark, and the span of a dense row-major block.  SpMM folds with the
 // very functions mxv folds with, so column c of A (+).(x) X is bit for bit mxv of X's column c; SDDMM folds its chains with them too.
 #pragma once
 #include "spgemm_internal.h"
@@ -67,6 +68,14 @@ struct MxOp {
     }
 };
 
+// the wave-level fence around a wave's own LDS staging area: what the lanes stored before it is visible to every lane after it
+__device__ __forceinline__ void mx_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // The column walk's schedule, built on the first column-orientation call and kept with the tiling (mxv.hip): per CSC position the
 // entry offset in column-walk order (mx_csc_off) and the tile's first slot in vals_t (mx_csc_base), per vals_t slot the entry's
 // (c << 4) | r (mx_rci_t).  Allocates from the context's arena the first time only; stream-ordered.
@@ -76,6 +85,21 @@ pem_status ensure_mx_cols(pem_ctx *ctx, const pem_tiled *A);
 // the tiling's value type.  Builds the column schedule on first use; stream-ordered.
 pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const float *x, float *y, int accumulate);
 pem_status mxv_semiring(pem_ctx *ctx, const pem_tiled *A, int semiring, bool col, const double *x, double *y, int accumulate);
+
+// The frontier's pack and mark for checked arguments (frontier.hip): with an xpres, the presence word of every 16-entry segment of
+// x and the flag of every line a present x can reach, in the context's grow-only scratch; without one both come back null (the
+// walk's ALLX variant reads neither).  Builds the column schedule for col; records the call for pem_test_frontier_line_flags.
+// Stream-ordered.  The caller has returned already where the orientation has no line.
+pem_status fr_prepare(pem_ctx *ctx, const pem_tiled *A, bool col, const uint8_t *xpres, const uint16_t **words, const uint8_t **flags);
+
+// the argument checks the frontier calls share
+inline bool fr_flag_ok(int v) { return v == 0 || v == 1; }
+
+struct Span {
+    const char *lo, *hi;
+    Span(const void *p, size_t bytes) : lo((const char *)p), hi((const char *)p + (p ? bytes : 0)) {}
+    bool meets(const Span &o) const { return lo < hi && o.lo < o.hi && lo < o.hi && o.lo < hi; }
+};
 
 // the bytes [lo, hi) a row-major n x k block with row stride ld spans (empty when n or k is 0); false when n * ld overflows int64
 // (the argument checks of spmm.hip and sddmm.hip)

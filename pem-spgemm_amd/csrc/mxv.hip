@@ -29,13 +29,6 @@ using namespace pem;
 
 // the folds (MxOp, mx_internal.h): K < 6 is a pem_semiring (mxv), K = 6 + op a pem_binop (reduce)
 
-__device__ __forceinline__ void mx_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ------------------------------------------------------------------------------------------
 // the walk: one wave per line, one entry per lane (header comment)
 // ------------------------------------------------------------------------------------------

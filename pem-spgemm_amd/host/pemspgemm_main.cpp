@@ -5,7 +5,7 @@
 // to ./pemspgemm_benchmark_result.csv and, when the 2nd argument is non-zero, writes the
 // sorted COO result to /tmp/SPGEMM_RESULT_{NNZ,ROWS,COLS,VALS}.txt.
 // Host C++ over the C ABI of libpemspgemm_hip.so.  The only HIP calls in this file are those of DevBuf: the dense device
-// vectors that --reduce, --bfs, --spmm and --sddmm hand to the library.
+// vectors that --reduce, --argreduce, --bfs, --bfs-parents, --spmm and --sddmm hand to the library.
 // Layout: Options (parse_args, validate), the helpers every stage shares, --gpus, then one function per stage; main() at the
 // end of the file is the table of contents.
 #include <algorithm>
@@ -103,6 +103,8 @@ struct Options {
     const char *dup_name = nullptr;                                 // --dup OP: see tiling_from_coo
     const char *reduce_spec = nullptr;                              // --reduce rows|cols[:OP]: see reduce_stage
     const char *bfs_spec = nullptr;                                 // --bfs SRC: see bfs_stage
+    const char *argreduce_spec = nullptr;                           // --argreduce rows|cols:min|max: see argreduce_stage
+    const char *bfs_parents_spec = nullptr;                         // --bfs-parents SRC: see bfs_parents_stage
     const char *spmm_path = nullptr;                                // --spmm X.mtx: see spmm_stage
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;      // --sddmm X.mtx [--sddmm-y Y.mtx]: see sddmm_stage
 
@@ -131,6 +133,8 @@ struct Options {
     std::vector<double> spmm_x, sddmm_x, sddmm_y;         // row-major
     int reduce_dim = -1, reduce_op = -1;
     long long bfs_src = 0;                                // 1-based
+    int argreduce_dim = -1, argreduce_op = -1;
+    long long bfs_parents_src = 0;                        // 1-based
 };
 
 // Strips the flags above out of argv; what is not one of them (or is one without its value) stays positional.
@@ -148,7 +152,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--sddmm-y", &o->sddmm_y_path}, {"--chunks", &chunks}, {"--apply", &o->apply_spec},
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
-                  {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]}};
+                  {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
+                  {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -176,7 +181,7 @@ static void parse_args(int argc, char *argv[], Options *o)
 
 // The clash rules: a flag and what it refuses, the first one present being the one named.
 static const struct ClashRule {
-    const char *flag, *refused[5], *why;
+    const char *flag, *refused[8], *why;
 } clash_rules[] = {
     {"--power", {"--gpus", "--mask", "--B", "the A*A^T argument"}, " (A^K multiplies A by itself on one device)"},
     {"--add", {"--gpus", "--mask", "--power"}, ""},
@@ -188,6 +193,8 @@ static const struct ClashRule {
     {"--sddmm", {"--gpus", "--power", "--reduce", "--spmm"}, ""},
     {"--reduce", {"--gpus", "--power"}, ""},
     {"--bfs", {"--gpus", "--power", "--reduce", "--spmm", "--sddmm"}, ""},
+    {"--argreduce", {"--gpus", "--power", "--reduce", "--bfs", "--spmm", "--sddmm"}, ""},
+    {"--bfs-parents", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
@@ -208,7 +215,8 @@ static bool clashes(const Options &o, const char *flag)
     } given[] = {{"--gpus", o.ngpu > 0},       {"--mask", o.mask_path != nullptr}, {"--power", o.power != 0},
                  {"--B", o.b_path != nullptr}, {"the A*A^T argument", o.aat},      {"--reduce", o.reduce_spec != nullptr},
                  {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr},
-                 {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr}};
+                 {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr},
+                 {"--bfs", o.bfs_spec != nullptr}, {"--argreduce", o.argreduce_spec != nullptr}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -420,7 +428,8 @@ static int validate_dense(Options *o)
     return 0;
 }
 
-// --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source
+// --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source; --argreduce:
+// the dimension and min or max; --bfs-parents: the 1-based source
 static int validate_vectors(Options *o)
 {
     o->reduce_op = add_ops[o->semiring];
@@ -444,6 +453,31 @@ static int validate_vectors(Options *o)
         o->bfs_src = strtoll(o->bfs_spec, &end, 10);
         if (end == o->bfs_spec || *end != '\0' || o->bfs_src < 1) {
             printf("--bfs %s: want a 1-based vertex number. Exiting.\n", o->bfs_spec);
+            return 1;
+        }
+    }
+    if (o->argreduce_spec) {
+        if (clashes(*o, "--argreduce")) return 1;
+        const char *colon = strchr(o->argreduce_spec, ':');
+        const std::string dim = colon ? std::string(o->argreduce_spec, (size_t)(colon - o->argreduce_spec)) : std::string(o->argreduce_spec);
+        o->argreduce_dim = dim == "rows" ? PEM_REDUCE_ROWS : dim == "cols" ? PEM_REDUCE_COLS : -1;
+        if (o->argreduce_dim < 0) {
+            printf("--argreduce %s: unknown dimension %s (rows, cols). Exiting.\n", o->argreduce_spec, dim.c_str());
+            return 1;
+        }
+        const std::string op = colon ? colon + 1 : "";
+        o->argreduce_op = op == "min" ? PEM_BINOP_MIN : op == "max" ? PEM_BINOP_MAX : -1;
+        if (o->argreduce_op < 0) {
+            printf("--argreduce %s: want rows|cols:min|max; unknown op %s (min, max). Exiting.\n", o->argreduce_spec, op.c_str());
+            return 1;
+        }
+    }
+    if (o->bfs_parents_spec) {
+        if (clashes(*o, "--bfs-parents")) return 1;
+        char *end = nullptr;
+        o->bfs_parents_src = strtoll(o->bfs_parents_spec, &end, 10);
+        if (end == o->bfs_parents_spec || *end != '\0' || o->bfs_parents_src < 1) {
+            printf("--bfs-parents %s: want a 1-based vertex number. Exiting.\n", o->bfs_parents_spec);
             return 1;
         }
     }
@@ -1179,6 +1213,7 @@ struct Result {
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
     const char *last_name = "C";        // ... and what the report lines call it
     std::vector<double> red, bfs_levels, spmm_y;   // --reduce's vector, --bfs' levels, --spmm's Y (row-major), on the host
+    std::vector<double> arg_idx, bfs_parents;      // --argreduce's indices, --bfs-parents' parents: 1-based, 0 for none
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
     int rc = 0;               // 2 once a result file could not be written (the run still finishes)
@@ -1729,6 +1764,78 @@ static int bfs_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--argreduce rows|cols:min|max` finds, for every row or column of the final result (what --reduce
+// would fold), where its minimum or maximum sits, on the device (pem_tiled_reduce_arg): the smallest index inside the line whose
+// stored value equals the fold.  One line reports the time; --out then writes the indices (Matrix-Market `array integer general`,
+// 1-based, 0 where the line has no non-NaN entry) instead of the matrix.  The CSV row describes the product.
+static int argreduce_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    const size_t n = (size_t)(o.argreduce_dim == PEM_REDUCE_COLS ? src.info.cols : src.info.rows);
+    DevBuf dy, di;
+    if (!dy.alloc(n, o.fp32 ? 4 : 8) || !di.alloc(n, 4)) {
+        fprintf(stderr, "pemspgemm: --argreduce: device allocation of %zu values and indices failed\n", n);
+        return 2;
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    auto r0 = Clock::now();
+    CHECK(o.fp32 ? pem_tiled_reduce_arg_f32(ctx, src.t, o.argreduce_op, o.argreduce_dim, (float *)dy.p, (int32_t *)di.p)
+                 : pem_tiled_reduce_arg(ctx, src.t, o.argreduce_op, o.argreduce_dim, (double *)dy.p, (int32_t *)di.p));
+    CHECK(pem_ctx_synchronize(ctx));
+    const double arg_ms = ms_since(r0);
+    std::vector<int32_t> idx(n);
+    if (n && hipMemcpy(idx.data(), di.p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    r->arg_idx.resize(n);
+    size_t found = 0;
+    for (size_t i = 0; i < n; ++i) {
+        r->arg_idx[i] = (double)(idx[i] + 1);
+        found += idx[i] >= 0;
+    }
+    printf("argreduce: %s %s of %s: argreduce %.3fms, %zu indices, %zu lines with one\n", o.argreduce_dim == PEM_REDUCE_COLS ? "cols" : "rows",
+           binop_names[o.argreduce_op], r->last_name, arg_ms, n, found);
+    return 0;
+}
+
+// `--bfs-parents SRC` is --bfs with the breadth-first tree (pem_tiled_bfs_parents): the line --bfs
+// prints, and --out writes the parents (Matrix-Market `array integer general`, 1-based, SRC its own parent, 0 where the vertex is
+// unreachable) instead of the matrix.  The CSV row describes the product.
+static int bfs_parents_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("--bfs-parents %s: %s is %d x %d; a search needs a square matrix. Exiting.\n", o.bfs_parents_spec, r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    if (o.bfs_parents_src > si.rows) {
+        printf("--bfs-parents %s: %s has %d vertices. Exiting.\n", o.bfs_parents_spec, r->last_name, si.rows);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    DevBuf dl, dp;
+    if (!dl.alloc(n, 4) || !dp.alloc(n, 4)) {
+        fprintf(stderr, "pemspgemm: --bfs-parents: device allocation of %zu levels and parents failed\n", n);
+        return 2;
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    int32_t depth = 0;
+    int64_t reached = 0;
+    auto b0 = Clock::now();
+    CHECK(pem_tiled_bfs_parents(ctx, src.t, (int64_t)(o.bfs_parents_src - 1), 0, (int32_t *)dl.p, (int32_t *)dp.p, &depth, &reached));
+    const double bfs_ms = ms_since(b0);
+    std::vector<int32_t> parents(n);
+    if (hipMemcpy(parents.data(), dp.p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    r->bfs_parents.resize(n);
+    for (size_t v = 0; v < n; ++v) r->bfs_parents[v] = (double)(parents[v] + 1);
+    printf("bfs: from %lld over %s: depth %d, reached %lld of %zu, bfs %.3fms\n", o.bfs_parents_src, r->last_name, depth, (long long)reached, n,
+           bfs_ms);
+    return 0;
+}
+
 // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
 // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
 // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
@@ -1822,7 +1929,7 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--out <file>`: the levels of --bfs, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
+// `--out <file>`: the levels of --bfs, else the parents of --bfs-parents, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
 // matrix: the sampled product of --sddmm, the final result when it is a tiling (its CSR export), or the plan's C (CSR export:
 // rows ascending, columns ascending).  The comment line says how the matrix came about.
 static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
@@ -1849,6 +1956,12 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     if (o.bfs_spec) {
         rc = write_mm_array(o.out_path, "integer", "bfs levels from " + std::to_string(o.bfs_src), (int64_t)r->bfs_levels.size(), 1, r->bfs_levels, 1,
                             false, "the ", "levels");
+    } else if (o.bfs_parents_spec) {
+        rc = write_mm_array(o.out_path, "integer", "bfs parents from " + std::to_string(o.bfs_parents_src) + " (1-based, 0: unreachable)",
+                            (int64_t)r->bfs_parents.size(), 1, r->bfs_parents, 1, false, "the ", "parents");
+    } else if (o.argreduce_dim >= 0) {
+        rc = write_mm_array(o.out_path, "integer", std::string("argreduce ") + o.argreduce_spec + " of C = A*B (1-based, 0: no entry)",
+                            (int64_t)r->arg_idx.size(), 1, r->arg_idx, 1, false, "the ", "indices");
     } else if (o.spmm_path) {
         rc = write_mm_array(o.out_path, "real", std::string("Y = R X (") + semiring + ")", r->spmm_ny, o.spmm_k, r->spmm_y, o.spmm_k > 1 ? o.spmm_k : 1,
                             o.fp32, "", "Y");
@@ -1901,6 +2014,8 @@ int main(int argc, char *argv[])
     if (!rc && in.St) rc = stack_stage(o, ctx, in, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
+    if (!rc && o.argreduce_dim >= 0) rc = argreduce_stage(o, ctx, &r);
+    if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
     if (!rc && o.sddmm_path) rc = sddmm_stage(o, ctx, &r);
     if (!rc) rc = save_stage(o, ctx, &r);
