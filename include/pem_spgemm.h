@@ -776,6 +776,47 @@ pem_status pem_tiled_sddmm(pem_ctx *ctx, const pem_tiled *S, int semiring, int64
 pem_status pem_tiled_sddmm_f32(pem_ctx *ctx, const pem_tiled *S, int semiring, int64_t k, const float *dX, int64_t ldx, const float *dY,
                                int64_t ldy, pem_tiled **out);
 
+/* Sampled sparse product: R = pattern(S) o (A * B) under a semiring, by dot products, on the device.
+ * Where SDDMM samples a dense product, this samples a sparse one; where the masked plan C<S> = A * B lists every tile-level product
+ * of A and B and then filters, this reads only the tile lists S's tiles touch: the cost follows S, not flop(A * B).
+ *   transpose_b = 0: A is m x n, B is n x p, S (or t) is m x p.  transpose_b = 1: B is p x n and the product is A * B^T (no
+ *     transposed tiling is needed).  Coordinates are those of the matrix each tiling represents (what pem_tiled_export_csr returns:
+ *     a tiling built with transpose = 1 is its own matrix).
+ *   For every stored position (i, j) of the pattern, R(i, j) is the fold over every k, in ascending k, where A(i, k) is stored and
+ *     B(k, j) is stored (transpose_b = 1: B(j, k)), with step 3's arithmetic (section 3g): plus_times is the chain acc = fma(a, b,
+ *     acc) from 0 (fmaf for fp32); min_plus / max_plus / max_times round each + / * once and fold with fmin / fmax from +-inf;
+ *     plus_pair counts the k's and reads no value; lor_land gives 1.0 / 0.0 with NaN counting as != 0.  A position that no k reaches
+ *     gets the semiring's start value (0, +inf, -inf, -inf, 0, 0), as SDDMM does at k = 0.  The pattern is never touched: zeros and
+ *     start values stay entries.  The stored values of S / the old values of t are never read (with accumulate = 0).  No atomics,
+ *     every value is written once: two calls give identical bits.
+ *   Consequences.  (1) Where the masked plan C<S> = A * B (transpose_b = 1: with pem_tiled_transpose(B) as its B) stores (i, j),
+ *     R(i, j) equals its value bit for bit; elsewhere in S's pattern R holds the start value.  (2) Under plus_pair,
+ *     pem_tiled_select(R, PEM_SELECT_VALUE_NE, 0) has exactly the masked plan's pattern.  (3) Split A's columns, and B's rows to
+ *     match, at any n1: a call on (A1, B1) followed by an accumulate call on (A2, B2) equals one call on (A, B), bit for bit (zero
+ *     signs under min / max excepted).
+ *   pem_tiled_sampled_mxm  a new tiling R with S's pattern and A's value type (S may hold either value type, as a mask may).  R owns
+ *       its arrays and works everywhere a tiling does.  It equals, every pem_tiled_array and every pem_tiled_info field but the two
+ *       timings, the tiling pem_tiled_from_csr builds from S's exported pattern with these values.  The call waits, like the other
+ *       builders; its allocations come from the context's arena.  An S with nnz = 0 gives a valid empty tiling.  S, A and B may be
+ *       the same handle in any combination (L o (L * L^T) is pem_tiled_sampled_mxm(ctx, L, L, L, 1, ..)).
+ *   pem_tiled_set_values_sampled_mxm  in place, on t's own pattern: t's values (vals and vals_t, written by the same kernel) become
+ *       the sampled product; t must hold A's value type.  accumulate = 1: every fold starts from the entry's old value (lor_land:
+ *       from old != 0; plus_pair: the count of a tile pair enters in one addition, which equals one addition per k while the
+ *       value is an integer below 2^24 (fp32) / 2^53).  Bumps t's value version (plans built on t turn stale under the rule of
+ *       pem_tiled_set_values).  Stream-ordered, never waits, reads nothing back; A's and B's current values are read.  Allocates
+ *       only on the tiling's first refresh (the vals_t map of pem_tiled_set_values); the tile intersections are searched again by
+ *       every call, not kept.
+ *   One untyped pair serves fp64 and fp32 (as pem_tiled_select): no host or device value array crosses the ABI.
+ *   PEM_E_INVALID, all checked before the device is touched (*out stays NULL): a null context, tiling or out; an unknown semiring;
+ *     transpose_b or accumulate not 0 or 1; A and B of different value types; t of another value type than A; inner dimensions that
+ *     differ; a pattern shape that is not m x p; t == A or t == B (the refresh would read what it writes).
+ *   PEM_SAMPLED_LPT in the environment (a measurement knob, read at every call): 16 packs four pattern tiles into a wave (16 lanes
+ *     each), 64 gives every pattern tile a wave; other values are ignored.  The results do not depend on it. */
+pem_status pem_tiled_sampled_mxm(pem_ctx *ctx, const pem_tiled *S, const pem_tiled *A, const pem_tiled *B, int transpose_b, int semiring,
+                                 pem_tiled **out);
+pem_status pem_tiled_set_values_sampled_mxm(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B, int transpose_b,
+                                            int semiring, int accumulate);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

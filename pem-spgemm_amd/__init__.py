@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "pem_tiled_build", "pem_tiled_build_f32", "pem_tiled_build_device", "pem_tiled_build_device_f32", "pem_tiled_set_values_from_build",
     "pem_tiled_set_values_from_build_f32", "pem_tiled_concat", "pem_tiled_set_values_from_concat",
     "pem_tiled_mxv_arg", "pem_tiled_mxv_arg_f32", "pem_tiled_reduce_arg", "pem_tiled_reduce_arg_f32", "pem_tiled_bfs_parents",
+    "pem_tiled_sampled_mxm", "pem_tiled_set_values_sampled_mxm",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -906,6 +907,28 @@ class Tiled:
         fn = lib().pem_tiled_set_values_sddmm_f32 if f32 else lib().pem_tiled_set_values_sddmm
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], k, px, ldx, py, ldy, int(bool(accumulate))))
 
+    def sampled_mxm(self, A, B, semiring="plus_times", transpose_b=False):
+        """Sampled sparse product: a new tiling R with this tiling's pattern and A's dtype, R(i, j) = the
+        fold, in ascending k, over the k where A(i, k) and B(k, j) (transpose_b: B(j, k)) are both stored, under a semiring of
+        SEMIRINGS with step 3's arithmetic -- pattern(S) o (A . B) by dot products, at a cost that follows the pattern.  Where the
+        masked plan C<S> = A . B stores an entry R holds its value bit for bit, elsewhere the semiring's start value.  This tiling's
+        values are never read; S, A and B may be the same tiling.  Waits.  New operand values go into R in place with
+        R.set_values_sampled_mxm."""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        h = C.c_void_p()
+        _check(lib().pem_tiled_sampled_mxm(self.ctx._h, self._h, A._h, B._h, int(bool(transpose_b)), SEMIRINGS[semiring], C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_sampled_mxm(self, A, B, semiring="plus_times", transpose_b=False, accumulate=False):
+        """sampled_mxm in place: this tiling's values become the sampled product at its own pattern (A, B of the tiling's dtype, neither
+        of them this tiling); with accumulate=True every fold starts from the entry's old value (lor_land: from old != 0).  Plans built
+        on the tiling turn stale as after set_values.  Ordered on the context's stream and never waits (see mxv)."""
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"unknown semiring {semiring!r}; one of {sorted(SEMIRINGS)}")
+        _check(lib().pem_tiled_set_values_sampled_mxm(self.ctx._h, self._h, A._h, B._h, int(bool(transpose_b)), SEMIRINGS[semiring],
+                                                      int(bool(accumulate))))
+
     def reduce(self, op="plus", dim="rows", out=None, accumulate=False):
         """Row or column reduction: out[i] = the left fold, in ascending index, of row i's (dim="cols":
         column i's) stored values under op (one of BINOPS), from the op's identity -- or from out's old value with accumulate=True.
@@ -982,6 +1005,17 @@ def tile_row_weights(ctx, A, B):
     w = np.zeros(A.tile_rows, dtype=np.float64)
     _check(lib().pem_tile_row_weights(ctx._h, A._h, B._h, _p(w, C.c_double)))
     return w
+
+
+def triangle_count(A):
+    """The triangles of the graph whose adjacency pattern A stores (a symmetric pattern; values and the diagonal are not read):
+    with L = A's strict lower triangle, the sum of L o (L . L^T) under plus_pair -- every triangle i > j > k counted once, at its
+    edge (i, j).  Three device calls (select, sampled_mxm, reduce); returns an int."""
+    L = A.select("tril", -1)
+    R = L.sampled_mxm(L, L, "plus_pair", transpose_b=True)
+    per_row = R.reduce("plus", "rows")
+    A.ctx.synchronize()
+    return int(round(float(per_row.double().sum().item())))
 
 
 class CPlan:

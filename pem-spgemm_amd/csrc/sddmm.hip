@@ -148,6 +148,11 @@ __global__ void __launch_bounds__(256) sddmm_headx_kernel(const int *__restrict_
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+void pem::tile_headx(pem_ctx *ctx, const pem_tiled *S, int *headx)
+{
+    PEM_LAUNCH(ctx, sddmm_headx_kernel, grid_for(16 * (size_t)S->ntiles, 256), 256, S->tile_nnz_ptr.as<int>(), (long long)S->ntiles, headx);
+}
+
 enum { SD_WIDTHS = 3 };
 static constexpr int kSdWidth[SD_WIDTHS] = {4, 8, 16};
 
@@ -279,7 +284,7 @@ static pem_status sddmm_build(pem_ctx *ctx, const pem_tiled *S, int semiring, in
         PEM_HIP(hipMemcpyAsync(T->tile_keys.p, S->tile_keys.p, sizeof(long long) * nt, hipMemcpyDeviceToDevice, st));
         PEM_HIP(hipMemcpyAsync(T->tile_nnz_ptr.p, S->tile_nnz_ptr.p, sizeof(int) * (nt + 1), hipMemcpyDeviceToDevice, st));
         PEM_HIP(hipMemcpyAsync(T->rowcolidx.p, S->rowcolidx.p, nnz, hipMemcpyDeviceToDevice, st));
-        PEM_LAUNCH(ctx, sddmm_headx_kernel, grid_for(16 * nt, 256), 256, S->tile_nnz_ptr.as<int>(), (long long)nt, headx);
+        tile_headx(ctx, S, headx);
         if (value_bytes == 4)
             sd_run<float>(ctx, S, semiring, k, dX, ldx, dY, ldy, 0, T->vals.p, nullptr, nullptr);
         else

@@ -1,5 +1,5 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip, sddmm.hip, sampled.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.  build.hip shares the
 // HEAD of pem_tiled_from_coo* (coo_sort_keys, then the radix sort) and this tail; its payload kernel is its own, because it compacts the
@@ -31,6 +31,8 @@ pem_status begin_payload(pem_ctx *ctx, pem_tiled *T, int **headx);
 // everything that follows from the sorted tile payload (tile_keys, tile_nnz_ptr, rowcolidx, vals); headx[0..nnz] = exclusive
 // scan of the tile-head flags.  ctx->ev[6] must have been recorded where the caller's payload kernels start.  Synchronises.
 pem_status derive_tiled(pem_ctx *ctx, pem_tiled *T, const int *headx, int bits_tr, int bits_tc);
+// headx of a tiling that takes S's pattern as it is (S has entries): the scan straight from S's tile offsets (sddmm.hip; sampled.hip)
+void tile_headx(pem_ctx *ctx, const pem_tiled *S, int *headx);
 // a derived route's size read-back: the flags (synchronises), then "<fn>: the result's entries exceed the int32 index range"
 // where the scan of the counts overflowed or nnz does not fit an int32, then check_internal
 pem_status check_result_entries(pem_ctx *ctx, int64_t nnz, const char *fn);

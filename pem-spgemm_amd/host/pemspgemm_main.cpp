@@ -107,6 +107,8 @@ struct Options {
     const char *bfs_parents_spec = nullptr;                         // --bfs-parents SRC: see bfs_parents_stage
     const char *spmm_path = nullptr;                                // --spmm X.mtx: see spmm_stage
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;      // --sddmm X.mtx [--sddmm-y Y.mtx]: see sddmm_stage
+    const char *sampled_path = nullptr;                             // --sampled S.mtx [--sampled-bt]: see sampled_stage
+    bool sampled_bt = false, triangles = false;                     // --triangles: see sampled_stage
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -153,11 +155,12 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
                   {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
-                  {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}};
+                  {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path}};
     const struct {
         const char *name;
         bool *flag, value;
-    } plain[] = {{"--fp32", &o->fp32, true}, {"--mask-complement", &o->mask_complement, true}, {"--no-tune-split", &o->tune_split, false}};
+    } plain[] = {{"--fp32", &o->fp32, true}, {"--mask-complement", &o->mask_complement, true}, {"--no-tune-split", &o->tune_split, false},
+                 {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}};
     o->args.assign(1, argv[0]);
     for (int r = 1; r < argc; ++r) {
         bool taken = false;
@@ -594,6 +597,54 @@ static int validate_dup(Options *o)
     return clashes(*o, "--dup") ? 1 : 0;
 }
 
+// --sampled S.mtx [--sampled-bt], --triangles: each takes the place of the plan product, so whatever shapes that product or works
+// on its result is refused by name
+static int validate_sampled(Options *o)
+{
+    if (o->sampled_bt && !o->sampled_path) {
+        printf("--sampled-bt needs --sampled <S.mtx>. Exiting.\n");
+        return 1;
+    }
+    const char *const flag = o->sampled_path ? "--sampled" : o->triangles ? "--triangles" : nullptr;
+    if (!flag) return 0;
+    if (o->sampled_path && o->triangles) {
+        printf("--triangles does not combine with --sampled (it is a sampled product of its own: L o (L*L^T) under plus_pair). Exiting.\n");
+        return 1;
+    }
+    if (o->sampled_bt && o->aat) {
+        printf("--sampled-bt does not combine with the A*A^T argument (both ask for B^T: --sampled-bt reads B's rows, the argument converts B^T). Exiting.\n");
+        return 1;
+    }
+    const struct {
+        const char *name;
+        bool present;
+    } plan_only[] = {{"--gpus", o->ngpu > 0}, {"--mask", o->mask_path != nullptr}, {"--power", o->power != 0}, {"--add", o->add_path != nullptr},
+                     {"--apply", o->apply_spec != nullptr}, {"--row-scale", o->scale_paths[0] != nullptr}, {"--col-scale", o->scale_paths[1] != nullptr},
+                     {"--select", o->select_spec != nullptr}, {"--topk", o->topk_spec != nullptr}, {"--extract-rows", o->extract_paths[0] != nullptr},
+                     {"--extract-cols", o->extract_paths[1] != nullptr}, {"--assign-into", o->assign_into != nullptr}, {"--kron", o->kron_path != nullptr},
+                     {"--hstack", o->stack_paths[0] != nullptr}, {"--vstack", o->stack_paths[1] != nullptr}, {"--reduce", o->reduce_spec != nullptr},
+                     {"--bfs", o->bfs_spec != nullptr}, {"--argreduce", o->argreduce_spec != nullptr}, {"--bfs-parents", o->bfs_parents_spec != nullptr},
+                     {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
+                     {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
+    for (const auto &f : plan_only)
+        if (f.present) {
+            printf("%s does not combine with %s (it takes the place of the plan product, and no stage runs after it). Exiting.\n", flag, f.name);
+            return 1;
+        }
+    if (o->triangles) {
+        const struct {
+            const char *name;
+            bool present;
+        } own[] = {{"--B", o->b_path != nullptr}, {"the A*A^T argument", o->aat}, {"--semiring", o->semiring_name != nullptr}, {"--out", o->out_path != nullptr}};
+        for (const auto &f : own)
+            if (f.present) {
+                printf("--triangles does not combine with %s (it counts the triangles of A's pattern and prints the count). Exiting.\n", f.name);
+                return 1;
+            }
+    }
+    return 0;
+}
+
 // Checks the options against each other and reads the files that can be refused before any work (index lists, X, Y).  Returns 0
 // to go on, else the exit code after the refusal; the order of the checks decides which refusal a command with two faults gets.
 static int validate(Options *o)
@@ -607,7 +658,7 @@ static int validate(Options *o)
     o->fastest = env_int("PEM_FASTEST", 0) != 0;                        // spgemm.cu:1359-1363
     o->save = o->args.size() >= 3 && atoi(o->args[2]) != 0;             // spgemm.cu:1485 (the reference dereferences argv[2] unconditionally)
     o->aat = o->args.size() == 4;                                       // spgemm.cu:788: presence of a 3rd argument, value ignored
-    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk, validate_dup, validate_stack})
+    for (auto step : {validate_product, validate_select, validate_lists, validate_dense, validate_vectors, validate_apply, validate_kron, validate_topk, validate_dup, validate_stack, validate_sampled})
         if (int rc = step(o)) return rc;
     if (o->ngpu > 0 && clashes(*o, "--gpus")) return 1;
     if (o->ngpu > 0 && (o->fp32 || o->cache_dir)) {
@@ -1198,6 +1249,7 @@ static int run_gpus(const Options &o)
 // The single-device path: the operands, then one function per stage, each leaving what it made in Result.
 // ------------------------------------------------------------------------------------------------------------------
 struct Operands {
+    Tiled Sp;   // --sampled's S
     Tiled A, B_own, Mt, Dt, Into, Kt, St;   // B_own: B when it is a tiling of its own; Mt the mask, Dt --add's D, Into --assign-into's D, Kt --kron's K, St --hstack's / --vstack's F
     pem_tiled *B = nullptr;
     pem_tiled_info ia, ib;
@@ -1300,14 +1352,29 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
     pem_tiled_info &ia = in->ia, &ib = in->ib;
     CHECK(pem_tiled_get_info(in->A.get(), &ia));
     CHECK(pem_tiled_get_info(in->B, &ib));
-    if (ia.cols != ib.rows) {
+    if (o.sampled_bt) {   // A * B^T from B's rows: the inner dimension is B's columns
+        if (ia.cols != ib.cols) {
+            printf("inner dimensions differ: A is %d x %d, B^T is %d x %d. Exiting.\n", ia.rows, ia.cols, ib.cols, ib.rows);
+            return 1;
+        }
+    } else if (ia.cols != ib.rows) {
         if (o.b_path)
             printf("inner dimensions differ: A is %d x %d, B%s is %d x %d. Exiting.\n", ia.rows, ia.cols, o.aat ? "^T" : "", ib.rows, ib.cols);
         else
             printf("input is rectangular. Only AAt is possible. Exiting.\n");   // spgemm.cu:782-786
         return 1;
     }
-    Coo cm, cd, cinto, ck, cs;
+    Coo cm, cd, cinto, ck, cs, csp;
+    if (o.sampled_path) {   // S's structure (its values are never read, so it is converted as fp64 whatever --fp32 says)
+        if (read_input(o, o.sampled_path, &csp) != 0) return 1;
+        const int pcols = o.sampled_bt ? ib.rows : ib.cols;
+        if (csp.rows != ia.rows || csp.cols != pcols) {
+            printf("--sampled %s is %d x %d but A*B%s is %d x %d. Exiting.\n", o.sampled_path, csp.rows, csp.cols, o.aat || o.sampled_bt ? "^T" : "",
+                   ia.rows, pcols);
+            return 1;
+        }
+        if (int rc = convert_or_refuse(ctx, o.sampled_path, csp, false, 0, o.dup, &in->Sp)) return rc;
+    }
     if (o.mask_path) {   // M's structure (its values are never read, so it is converted as fp64 whatever --fp32 says)
         if (read_input(o, o.mask_path, &cm) != 0) return 1;
         if (cm.rows != ia.rows || cm.cols != ib.cols) {
@@ -1345,6 +1412,8 @@ static int build_operands(const Options &o, pem_ctx *ctx, Operands *in)
     if (o.mask_path)
         printf("MASK%s\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", o.mask_complement ? " (complement)" : "", o.mask_path, cm.rows, cm.cols,
                (long long)cm.nnz);
+    if (o.sampled_path)
+        printf("SAMPLED AT\nfilepath: %s\nRows: %d\nCols: %d\nNnz: %lld\n", o.sampled_path, csp.rows, csp.cols, (long long)csp.nnz);
     in->conv_ms = ms_since(conv_start);
     return 0;
 }
@@ -1906,6 +1975,36 @@ static int sddmm_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--sampled S.mtx [--sampled-bt]` takes the place of the plan product: R = pattern(S) o (A*B) under the
+// semiring by dot products on the device (pem_tiled_sampled_mxm), A*B^T from B's rows with --sampled-bt; --out gets R.
+// `--triangles` prints the triangle count of A's pattern (symmetric, as the count assumes): with L = A's strict lower triangle,
+// the sum of L o (L*L^T) under plus_pair.  No plan is made and no later stage runs.
+static int sampled_stage(const Options &o, pem_ctx *ctx, const Operands &in)
+{
+    const auto t0 = Clock::now();
+    Tiled L, R;
+    Csr c;
+    if (o.triangles) {
+        CHECK(pem_tiled_select(ctx, in.A.get(), PEM_SELECT_TRIL, -1.0, out(ctx, L)));
+        CHECK(pem_tiled_sampled_mxm(ctx, L.get(), L.get(), L.get(), 1, PEM_SEMIRING_PLUS_PAIR, out(ctx, R)));
+        const double ms = ms_since(t0);
+        CHECK(export_csr(ctx, R.get(), o.fp32, &c));
+        long long n = 0;
+        for (double v : c.v) n += (long long)v;
+        printf("triangles: %lld (L o (L*L^T) under plus_pair, L = tril(A, -1) with %lld entries: %.3fms)\n", n, (long long)c.nnz(), ms);
+        return 0;
+    }
+    CHECK(pem_tiled_sampled_mxm(ctx, in.Sp.get(), in.A.get(), in.B, o.sampled_bt ? 1 : 0, o.semiring, out(ctx, R)));
+    const double ms = ms_since(t0);
+    CHECK(export_csr(ctx, R.get(), o.fp32, &c));
+    const char *const bt = o.aat || o.sampled_bt ? "^T" : "";
+    printf("sampled: R = pattern(S) o (A*B%s) (%s): sampled_mxm %.3fms, nnz %lld, host sum %.17g\n", bt, semiring_names[o.semiring], ms,
+           (long long)c.nnz(), sum_of(c.v));
+    if (o.out_path)
+        return write_mtx(o.out_path, c.rows, c.cols, c, std::string("R = pattern(S) o (A*B") + bt + ") (" + semiring_names[o.semiring] + ") by pemspgemm (pem-spgemm_amd)", "R");
+    return 0;
+}
+
 // The sorted COO files of the 2nd argument: the sampled product's, the stacked matrix's, the Kronecker product's or the assigned matrix's entries when
 // there is one (their CSR export is the sorted (row, column) order), else the plan's C as the reference writes it.
 static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
@@ -2001,6 +2100,11 @@ int main(int argc, char *argv[])
     Operands in;
     Result r;
     int rc = build_operands(o, ctx, &in);
+    if (!rc && (o.sampled_path || o.triangles)) {
+        if ((rc = sampled_stage(o, ctx, in))) return rc;
+        printf("CLEANING UP RESOURCES\n\n");
+        return 0;
+    }
     if (!rc) rc = power_prologue(o, ctx, &in, &r);
     if (!rc) rc = timed_product(o, ctx, in, &r);
     if (!rc && in.Dt) rc = add_stage(o, ctx, in, &r);
