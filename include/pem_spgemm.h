@@ -817,6 +817,39 @@ pem_status pem_tiled_sampled_mxm(pem_ctx *ctx, const pem_tiled *S, const pem_til
 pem_status pem_tiled_set_values_sampled_mxm(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const pem_tiled *B, int transpose_b,
                                             int semiring, int accumulate);
 
+/* Triangular solve: x = T^-1 b on the device, T the lower or upper triangle of a square tiling.
+ *   pem_tiled_trsv  A must be square (n = A.rows); coordinates are those of the matrix the tiling represents, as for pem_tiled_mxv.
+ *       T is the chosen triangle of A AS STORED: entries on the other side of the diagonal are ignored (the BLAS uplo convention), so
+ *       a full A serves Gauss-Seidel directly.  With unit_diag = 1 the stored diagonal entries are ignored as well and the diagonal
+ *       counts as 1.  db and dx are device arrays of n values of the tiling's value type; dx == db (the in-place solve) is legal.
+ *     Order (bit-exact; P = i / 16, the tile size of the format -- pem_tiled_get_array):
+ *       lower, rows ascending.  acc = b_i; for the stored a_ij with j < i in ascending j: acc = fma(-a_ij, x_j, acc); then
+ *         x_i = acc / a_ii, one IEEE division, or x_i = acc under unit_diag.
+ *       upper, rows descending.  acc = b_i; first the stored a_ij with j >= 16 (P + 1) in ascending j, then those with
+ *         i < j < 16 (P + 1) in descending j, the same fma; then the division.
+ *       fp32 tilings compute in fp32 (fmaf, fp32 division).  No atomics: two calls give identical bits.  A zero, infinite or NaN
+ *       diagonal value is no error: the division gives what IEEE gives.
+ *     PEM_E_INVALID: a null context or tiling; rows != cols; uplo or unit_diag not 0 or 1; the fp64 form on an fp32 tiling or the
+ *       reverse; a null db or dx where n > 0; db and dx overlapping other than exactly; with unit_diag = 0 a row without a stored
+ *       diagonal entry (the message names the first such row, 1-based).  n = 0, and an empty tiling under unit_diag, are legal.
+ *     Schedule.  The first call per (tiling, uplo) builds the dependency schedule and keeps it with the tiling: tile row P (16 rows)
+ *       waits for tile row Q wherever tile (P, Q) is stored on the chosen side; level(P) = 1 + the largest level it waits for.  That
+ *       call reads the tile CSR back (two int arrays, no entry-level data), counts the rows without a stored diagonal on the device,
+ *       carves one buffer (24 bytes per tile row) from the context's arena and waits.  Every later call allocates nothing, is
+ *       ordered on the context's stream, never waits and reads nothing back; pem_tiled_set_values* keeps the schedule.  A level wider
+ *       than merge_width tile rows is one kernel launch; a maximal run of consecutive levels each at most merge_width wide is one
+ *       launch of one workgroup.  No kernel waits on what another workgroup writes in the same launch.
+ *   pem_tiled_trsv_info  the schedule of a triangle (built if need be; same refusals for ctx, A, uplo; a null out): levels, the
+ *       launches of one solve, the widest level in tile rows, merge_width, the rows without a stored diagonal entry and the first of
+ *       them (1-based; 0 if none).  All 0 but merge_width for n = 0. */
+enum { PEM_TRSV_LOWER = 0, PEM_TRSV_UPPER = 1 };
+pem_status pem_tiled_trsv(pem_ctx *ctx, const pem_tiled *A, int uplo, int unit_diag, const double *db, double *dx);
+pem_status pem_tiled_trsv_f32(pem_ctx *ctx, const pem_tiled *A, int uplo, int unit_diag, const float *db, float *dx);
+typedef struct {
+    int64_t levels, launches, max_width, merge_width, missing_diag, first_missing_row;
+} pem_trsv_info;
+pem_status pem_tiled_trsv_info(pem_ctx *ctx, const pem_tiled *A, int uplo, pem_trsv_info *out);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "pem_tiled_set_values_from_build_f32", "pem_tiled_concat", "pem_tiled_set_values_from_concat",
     "pem_tiled_mxv_arg", "pem_tiled_mxv_arg_f32", "pem_tiled_reduce_arg", "pem_tiled_reduce_arg_f32", "pem_tiled_bfs_parents",
     "pem_tiled_sampled_mxm", "pem_tiled_set_values_sampled_mxm",
+    "pem_tiled_trsv", "pem_tiled_trsv_f32", "pem_tiled_trsv_info", "pem_test_trsv_split",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -92,6 +93,9 @@ REDUCE_DIMS = dict(rows=0, cols=1)
 # enum pem_arg_kind (include/pem_spgemm.h): Tiled.mxv_arg's kinds, by value; the last two read no value
 ARG_KINDS = ("min_plus", "max_plus", "max_times", "min_index", "max_index")
 INDEX_ARG_KINDS = ARG_KINDS[3:]
+
+# PEM_TRSV_LOWER / PEM_TRSV_UPPER (include/pem_spgemm.h): Tiled.trsv's triangles, by value
+TRSV_UPLO = ("lower", "upper")
 
 # enum pem_values_order (include/pem_spgemm.h): the order of the values handed to Tiled.set_values*
 VALUE_ORDERS = dict(row=0, col=1)
@@ -131,6 +135,11 @@ class CacheKey(C.Structure):
 class MemoryStats(C.Structure):
     _fields_ = [("slab_bytes", C.c_int64), ("in_use_bytes", C.c_int64), ("peak_in_use_bytes", C.c_int64), ("largest_free_bytes", C.c_int64),
                 ("driver_allocs", C.c_int64), ("block_allocs", C.c_int64)]
+
+
+class TrsvInfo(C.Structure):
+    _fields_ = [("levels", C.c_int64), ("launches", C.c_int64), ("max_width", C.c_int64), ("merge_width", C.c_int64),
+                ("missing_diag", C.c_int64), ("first_missing_row", C.c_int64)]
 
 
 class Timings(C.Structure):
@@ -213,6 +222,10 @@ class Context:
     def debug_refused_launch(self):
         """test hook: a kernel launch the runtime refuses; the error surfaces at the next synchronising call"""
         _check(lib().pem_debug_refused_launch(self._h))
+
+    def trsv_split(self, on):
+        """test hook (pem_test.h): on forces merge_width = 0 in this context's triangular solves, one launch per level"""
+        _check(lib().pem_test_trsv_split(self._h, int(bool(on))))
 
     def set_graph_replay(self, on):
         """repeat passes of CPlan.spgemm() replayed as one hipGraph (no per-step timings for those passes)"""
@@ -706,6 +719,31 @@ class Tiled:
         fn = lib().pem_tiled_mxv_f32 if self.value_bytes == 4 else lib().pem_tiled_mxv
         _check(fn(self.ctx._h, self._h, SEMIRINGS[semiring], int(bool(transpose)), px, py, int(bool(accumulate))))
         return out
+
+    def trsv(self, b, uplo="lower", unit_diag=False, out=None):
+        """Triangular solve: out = T^-1 b, T the lower or upper triangle (uplo, one of TRSV_UPLO) of this
+        square tiling as stored -- entries on the other side are ignored, and with unit_diag=True so are the stored diagonal entries
+        (the diagonal counts as 1).  b: a contiguous device torch tensor of the tiling's dtype with rows entries; out: one like it,
+        allocated when None; out is b solves in place.  Any other argument raises ValueError; what the library refuses (a partial overlap,
+        a tiling that is not square) raises PemError.  Bit-exact order: section 3x.  A row without a
+        stored diagonal entry is refused unless unit_diag.  The first call per triangle builds the level schedule (waits once); every
+        later call is ordered on the context's stream and never waits (see mxv).  Returns out."""
+        if uplo not in TRSV_UPLO:
+            raise ValueError(f"unknown uplo {uplo!r}; one of {TRSV_UPLO}")
+        pb = self._vector("trsv", "b", b, self.rows)
+        out, px = self._out("trsv", out, self.rows, like=b)
+        fn = lib().pem_tiled_trsv_f32 if self.value_bytes == 4 else lib().pem_tiled_trsv
+        _check(fn(self.ctx._h, self._h, TRSV_UPLO.index(uplo), int(bool(unit_diag)), pb, px))
+        return out
+
+    def trsv_info(self, uplo="lower"):
+        """the schedule of a triangle (built if need be) as a dict: levels, launches (of one solve), max_width (tile rows of the
+        widest level), merge_width, missing_diag (rows without a stored diagonal entry), first_missing_row (1-based, 0 if none)"""
+        if uplo not in TRSV_UPLO:
+            raise ValueError(f"unknown uplo {uplo!r}; one of {TRSV_UPLO}")
+        i = TrsvInfo()
+        _check(lib().pem_tiled_trsv_info(self.ctx._h, self._h, TRSV_UPLO.index(uplo), C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in TrsvInfo._fields_}
 
     def _bytes(self, fn, name, v, n):
         """the device pointer of a contiguous torch.bool / torch.uint8 tensor of n bytes on the context's device; None passes as NULL"""

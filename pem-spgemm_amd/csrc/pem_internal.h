@@ -199,6 +199,7 @@ struct pem_ctx {
     pem::DevBuf fr_scratch;
     size_t fr_flags_off = 0;
     int64_t fr_lines = -1;
+    int dbg_trsv_split = 0;            // pem_test_trsv_split: 1 forces the triangular solve's merge_width to 0 (one launch per level)
     int dbg_scan_force = 0;            // pem_debug_scan_i32: 0 automatic, 2 single-launch chained scan, 3 three-launch scan
     int dbg_scan_stall_ticket = -1;    // ... and the chained scan's block that stalls before it publishes
     // timing
@@ -340,6 +341,18 @@ struct Derivation {
     bool map_ready = false;
 };
 
+// The triangular solve's schedule of one triangle (trsv.hip), built on the first pem_tiled_trsv* / pem_tiled_trsv_info per
+// (tiling, uplo) and then kept -- the pattern never changes.  One device buffer: int4 per tile row P (the positions [x, y) of
+// its off-diagonal tiles on the chosen side, z its diagonal tile's id or -1), then the tile rows sorted by level, then the
+// level offsets; the level offsets again on the host, which issues the launches.
+struct TrsvSched {
+    bool ready = false;
+    DevBuf buf;
+    size_t order_off = 0, lvl_off = 0;     // in ints, from the start of buf
+    std::vector<int> h_lvl;                // levels + 1 offsets into the sorted tile rows
+    int64_t max_width = 0, missing_diag = 0, first_missing_row = 0;   // rows without a stored diagonal entry; the first, 1-based
+};
+
 }  // namespace pem
 
 struct pem_tiled {
@@ -369,6 +382,7 @@ struct pem_tiled {
     // and per slot of vals_t the entry's (c << 4) | r (uint8[nnz]).  The row walk reads the tiling's own arrays.
     mutable pem::DevBuf mx_csc_off, mx_csc_base, mx_rci_t;
     mutable bool mx_cols_ready = false;
+    mutable pem::TrsvSched trsv[2];   // triangular solve (trsv.hip): the schedule of the lower and of the upper triangle
 };
 
 struct pem_cplan {

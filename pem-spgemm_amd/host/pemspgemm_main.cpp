@@ -5,7 +5,7 @@
 // to ./pemspgemm_benchmark_result.csv and, when the 2nd argument is non-zero, writes the
 // sorted COO result to /tmp/SPGEMM_RESULT_{NNZ,ROWS,COLS,VALS}.txt.
 // Host C++ over the C ABI of libpemspgemm_hip.so.  The only HIP calls in this file are those of DevBuf: the dense device
-// vectors that --reduce, --argreduce, --bfs, --bfs-parents, --spmm and --sddmm hand to the library.
+// vectors that --reduce, --trsv, --argreduce, --bfs, --bfs-parents, --spmm and --sddmm hand to the library.
 // Layout: Options (parse_args, validate), the helpers every stage shares, --gpus, then one function per stage; main() at the
 // end of the file is the table of contents.
 #include <algorithm>
@@ -109,6 +109,7 @@ struct Options {
     const char *sddmm_path = nullptr, *sddmm_y_path = nullptr;      // --sddmm X.mtx [--sddmm-y Y.mtx]: see sddmm_stage
     const char *sampled_path = nullptr;                             // --sampled S.mtx [--sampled-bt]: see sampled_stage
     bool sampled_bt = false, triangles = false;                     // --triangles: see sampled_stage
+    const char *trsv_spec = nullptr, *rhs_path = nullptr;           // --trsv lower|upper[:unit] [--rhs b.mtx]: see trsv_stage
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -137,6 +138,9 @@ struct Options {
     long long bfs_src = 0;                                // 1-based
     int argreduce_dim = -1, argreduce_op = -1;
     long long bfs_parents_src = 0;                        // 1-based
+    int trsv_uplo = -1;                                   // PEM_TRSV_LOWER / PEM_TRSV_UPPER
+    bool trsv_unit = false;
+    std::vector<double> rhs;                              // --rhs' values
 };
 
 // Strips the flags above out of argv; what is not one of them (or is one without its value) stays positional.
@@ -155,7 +159,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--row-scale", &o->scale_paths[0]}, {"--col-scale", &o->scale_paths[1]}, {"--scale-op", &o->scale_op_name},
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
                   {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
-                  {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path}};
+                  {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path},
+                  {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -198,6 +203,7 @@ static const struct ClashRule {
     {"--bfs", {"--gpus", "--power", "--reduce", "--spmm", "--sddmm"}, ""},
     {"--argreduce", {"--gpus", "--power", "--reduce", "--bfs", "--spmm", "--sddmm"}, ""},
     {"--bfs-parents", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
+    {"--trsv", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
@@ -432,9 +438,40 @@ static int validate_dense(Options *o)
 }
 
 // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source; --argreduce:
-// the dimension and min or max; --bfs-parents: the 1-based source
+// the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front
 static int validate_vectors(Options *o)
 {
+    if (o->rhs_path && !o->trsv_spec) {
+        printf("--rhs needs --trsv lower|upper[:unit]. Exiting.\n");
+        return 1;
+    }
+    if (o->trsv_spec) {
+        if (clashes(*o, "--trsv")) return 1;
+        if (o->bfs_parents_spec) {
+            printf("--trsv does not combine with --bfs-parents. Exiting.\n");
+            return 1;
+        }
+        const char *colon = strchr(o->trsv_spec, ':');
+        const std::string tri = colon ? std::string(o->trsv_spec, (size_t)(colon - o->trsv_spec)) : std::string(o->trsv_spec);
+        o->trsv_uplo = tri == "lower" ? PEM_TRSV_LOWER : tri == "upper" ? PEM_TRSV_UPPER : -1;
+        if (o->trsv_uplo < 0) {
+            printf("--trsv %s: unknown triangle %s (lower, upper). Exiting.\n", o->trsv_spec, tri.c_str());
+            return 1;
+        }
+        if (colon && strcmp(colon + 1, "unit")) {
+            printf("--trsv %s: want lower|upper[:unit]. Exiting.\n", o->trsv_spec);
+            return 1;
+        }
+        o->trsv_unit = colon != nullptr;
+        if (o->rhs_path) {
+            int64_t n = 0, k = 0;
+            if (read_dense_array("--rhs", o->rhs_path, &n, &k, &o->rhs)) return 1;
+            if (k != 1) {
+                printf("--rhs %s: an array of %lld columns, not of one. Exiting.\n", o->rhs_path, (long long)k);
+                return 1;
+            }
+        }
+    }
     o->reduce_op = add_ops[o->semiring];
     if (o->reduce_spec) {
         if (clashes(*o, "--reduce")) return 1;
@@ -625,6 +662,7 @@ static int validate_sampled(Options *o)
                      {"--hstack", o->stack_paths[0] != nullptr}, {"--vstack", o->stack_paths[1] != nullptr}, {"--reduce", o->reduce_spec != nullptr},
                      {"--bfs", o->bfs_spec != nullptr}, {"--argreduce", o->argreduce_spec != nullptr}, {"--bfs-parents", o->bfs_parents_spec != nullptr},
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
+                     {"--trsv", o->trsv_spec != nullptr},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1266,6 +1304,7 @@ struct Result {
     const char *last_name = "C";        // ... and what the report lines call it
     std::vector<double> red, bfs_levels, spmm_y;   // --reduce's vector, --bfs' levels, --spmm's Y (row-major), on the host
     std::vector<double> arg_idx, bfs_parents;      // --argreduce's indices, --bfs-parents' parents: 1-based, 0 for none
+    std::vector<double> trsv_x;                    // --trsv's solution
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
     int rc = 0;               // 2 once a result file could not be written (the run still finishes)
@@ -1796,6 +1835,59 @@ static int reduce_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--trsv lower|upper[:unit] [--rhs b.mtx]` solves T x = b on the device (pem_tiled_trsv), T the named
+// triangle of the final result (what --reduce would fold; it must be square) as stored, the diagonal taken as 1 under :unit.  b is
+// a Matrix-Market `array real general` file of one column, all ones without --rhs.  One line reports the solve's time (the
+// schedule built by a first solve, which is timed apart), the levels and the launches; --out then writes x (Matrix-Market array)
+// instead of the matrix.  The CSV row describes the product.
+static int trsv_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("--trsv %s: %s is %d x %d; a triangular solve needs a square matrix. Exiting.\n", o.trsv_spec, r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    if (o.rhs_path && o.rhs.size() != n) {
+        printf("--rhs %s: the vector has %zu values; %s has %d rows. Exiting.\n", o.rhs_path, o.rhs.size(), r->last_name, si.rows);
+        return 1;
+    }
+    const std::vector<double> ones(o.rhs_path ? 0 : n, 1.0);
+    DevBuf db, dx;
+    if (!db.upload(o.rhs_path ? o.rhs : ones, n, o.fp32) || !dx.alloc(n, o.fp32 ? 4 : 8)) {
+        fprintf(stderr, "pemspgemm: --trsv: device allocation of %zu values failed\n", n);
+        return 2;
+    }
+    const auto solve = [&] {
+        return o.fp32 ? pem_tiled_trsv_f32(ctx, src.t, o.trsv_uplo, o.trsv_unit, (const float *)db.p, (float *)dx.p)
+                      : pem_tiled_trsv(ctx, src.t, o.trsv_uplo, o.trsv_unit, (const double *)db.p, (double *)dx.p);
+    };
+    CHECK(pem_ctx_synchronize(ctx));
+    auto t0 = Clock::now();
+    const pem_status first = solve();   // builds the schedule
+    if (first == PEM_E_INVALID) {
+        printf("--trsv %s: %s. Exiting.\n", o.trsv_spec, pem_last_error());
+        return 1;
+    }
+    CHECK(first);
+    CHECK(pem_ctx_synchronize(ctx));
+    const double first_ms = ms_since(t0);
+    t0 = Clock::now();
+    CHECK(solve());
+    CHECK(pem_ctx_synchronize(ctx));
+    const double solve_ms = ms_since(t0);
+    pem_trsv_info ti;
+    CHECK(pem_tiled_trsv_info(ctx, src.t, o.trsv_uplo, &ti));
+    if (!dx.download(&r->trsv_x, n, o.fp32)) return 2;
+    printf("trsv: %s%s of %s: solve %.3fms (first, with the schedule, %.3fms), %zu values, %lld levels, %lld launches, host sum %.17g\n",
+           o.trsv_uplo == PEM_TRSV_UPPER ? "upper" : "lower", o.trsv_unit ? ":unit" : "", r->last_name, solve_ms, first_ms, n, (long long)ti.levels,
+           (long long)ti.launches, sum_of(r->trsv_x));
+    return 0;
+}
+
 // `--bfs SRC` runs a breadth-first search from the 1-based vertex SRC over the pattern of the final
 // result (what --reduce would fold; it must be square) on the device (pem_tiled_bfs): a stored entry (i, j) is an edge i -> j.
 // One line reports depth, reached and the time; --out then writes the levels (Matrix-Market `array integer general`, -1 for
@@ -2028,7 +2120,7 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--out <file>`: the levels of --bfs, else the parents of --bfs-parents, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
+// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
 // matrix: the sampled product of --sddmm, the final result when it is a tiling (its CSR export), or the plan's C (CSR export:
 // rows ascending, columns ascending).  The comment line says how the matrix came about.
 static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
@@ -2052,7 +2144,10 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     if (r->stk) how += std::string(o.stack_paths[1] ? ", vstack with " : ", hstack with ") + o.stack_paths[o.stack_paths[1] ? 1 : 0];
     how += " by pemspgemm (pem-spgemm_amd)";
     int rc = 0;
-    if (o.bfs_spec) {
+    if (o.trsv_uplo >= 0) {
+        rc = write_mm_array(o.out_path, "real", std::string("x of T x = b, T the ") + o.trsv_spec + " triangle of C = A*B" + (o.rhs_path ? std::string(", b ") + o.rhs_path : std::string(", b all ones")),
+                            (int64_t)r->trsv_x.size(), 1, r->trsv_x, 1, o.fp32, "the ", "solution");
+    } else if (o.bfs_spec) {
         rc = write_mm_array(o.out_path, "integer", "bfs levels from " + std::to_string(o.bfs_src), (int64_t)r->bfs_levels.size(), 1, r->bfs_levels, 1,
                             false, "the ", "levels");
     } else if (o.bfs_parents_spec) {
@@ -2117,6 +2212,7 @@ int main(int argc, char *argv[])
     if (!rc && in.Kt) rc = kron_stage(o, ctx, in, &r);
     if (!rc && in.St) rc = stack_stage(o, ctx, in, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
+    if (!rc && o.trsv_uplo >= 0) rc = trsv_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
     if (!rc && o.argreduce_dim >= 0) rc = argreduce_stage(o, ctx, &r);
     if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
