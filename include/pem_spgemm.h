@@ -850,6 +850,37 @@ typedef struct {
 } pem_trsv_info;
 pem_status pem_tiled_trsv_info(pem_ctx *ctx, const pem_tiled *A, int uplo, pem_trsv_info *out);
 
+/* ILU(0): the incomplete LU of a square tiling on its own pattern, on the device.
+ *   pem_tiled_ilu0  A is square with stored pattern S (coordinates of the matrix the tiling represents).  *out is a new tiling F
+ *       with exactly A's pattern and value type that stores L's strict lower triangle and U with its diagonal in one tiling; L has
+ *       a unit diagonal, which is not stored.  Nothing is ever dropped from the pattern and nothing is added to it.
+ *     Order (bit-exact).  With m = min(i, j), for every stored (i, j):
+ *         acc = a_ij;  for k ascending over { k < m : (i, k) in S and (k, j) in S }: acc = fma(-f_ik, f_kj, acc);
+ *         f_ij = acc / f_jj where j < i (one IEEE division, correctly rounded, in the value type), else f_ij = acc.
+ *       fp32 tilings compute in fp32 (fmaf, fp32 division), fp64 tilings in fp64.  No atomics: the same bits on every call and on
+ *       every launch route.  A position that is not stored is never multiplied -- it is not a zero: an infinite f_ik next to an
+ *       unstored (k, j) leaves f_ij untouched.  A zero, infinite or NaN pivot is no error: the division gives what IEEE gives.
+ *     F is an ordinary tiling (export, save / load, mxv, transpose, operand of a plan).  The preconditioner solve z = U^-1 L^-1 r is
+ *       pem_tiled_trsv(ctx, F, PEM_TRSV_LOWER, 1, r, t) then pem_tiled_trsv(ctx, F, PEM_TRSV_UPPER, 0, t, z): no select needed.
+ *     Schedule: the lower triangle's of pem_tiled_trsv (tile row P waits for Q wherever tile (P, Q), Q < P, is stored), built for F
+ *       by this call and kept; a level wider than merge_width tile rows is one launch, a maximal run of narrower levels one launch of
+ *       one workgroup.  Waits; allocates from the context's arena.
+ *     PEM_E_INVALID (*out stays NULL): a null argument; rows != cols; a row without a stored diagonal entry (the message names the
+ *       first such row, 1-based).
+ *   pem_tiled_set_values_from_ilu0  recomputes F from A's current values (after pem_tiled_set_values* on A) and bumps F's value
+ *       version.  Stream-ordered: never waits, reads nothing back, allocates nothing; F's trsv schedules stay.  F must have been
+ *       made by pem_tiled_ilu0 from exactly this A, else PEM_E_INVALID (the rule of the other pem_tiled_set_values_from_*).
+ *   pem_tiled_ilu0_info  of a square tiling F: the levels, launches, widest level and merge width of the factorisation's launch
+ *       plan; zero_pivots, the rows whose f_ii is +-0, not finite or not stored, and the first of them (1-based; 0 if none).  One
+ *       small kernel over the diagonal and two scalars read back: the only one of the three that has to synchronise on a factor.
+ *   Not covered: IC(0), fill levels above 0, pivoting, diagonal shifts, a pem_mgpu_* path. */
+pem_status pem_tiled_ilu0(pem_ctx *ctx, const pem_tiled *A, pem_tiled **out);
+pem_status pem_tiled_set_values_from_ilu0(pem_ctx *ctx, pem_tiled *F, const pem_tiled *A);
+typedef struct {
+    int64_t levels, launches, max_width, merge_width, zero_pivots, first_zero_pivot_row;
+} pem_ilu0_info;
+pem_status pem_tiled_ilu0_info(pem_ctx *ctx, const pem_tiled *F, pem_ilu0_info *out);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

@@ -65,7 +65,7 @@ pem_status pem_debug_refused_launch(pem_ctx *ctx);
  * number of lines.  Waits.  PEM_E_STATE if that call had dx_present == NULL (nothing is marked then) or there was none. */
 pem_status pem_test_frontier_line_flags(pem_ctx *ctx, uint8_t *host_dst, int64_t nlines);
 
-/* on = 1 forces merge_width = 0 in the context's triangular solves (pem_tiled_trsv*, pem_tiled_trsv_info): one launch per level,
+/* on = 1 forces merge_width = 0 in the context's triangular solves (pem_tiled_trsv*, pem_tiled_trsv_info) and in ILU(0) (pem_tiled_ilu0*): one launch per level,
  * whatever its width; on = 0 (default) restores the merged launch of narrow levels.  The results are bit for bit the same. */
 pem_status pem_test_trsv_split(pem_ctx *ctx, int on);
 

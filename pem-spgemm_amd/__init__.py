@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "pem_tiled_mxv_arg", "pem_tiled_mxv_arg_f32", "pem_tiled_reduce_arg", "pem_tiled_reduce_arg_f32", "pem_tiled_bfs_parents",
     "pem_tiled_sampled_mxm", "pem_tiled_set_values_sampled_mxm",
     "pem_tiled_trsv", "pem_tiled_trsv_f32", "pem_tiled_trsv_info", "pem_test_trsv_split",
+    "pem_tiled_ilu0", "pem_tiled_set_values_from_ilu0", "pem_tiled_ilu0_info",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -140,6 +141,11 @@ class MemoryStats(C.Structure):
 class TrsvInfo(C.Structure):
     _fields_ = [("levels", C.c_int64), ("launches", C.c_int64), ("max_width", C.c_int64), ("merge_width", C.c_int64),
                 ("missing_diag", C.c_int64), ("first_missing_row", C.c_int64)]
+
+
+class Ilu0Info(C.Structure):
+    _fields_ = [("levels", C.c_int64), ("launches", C.c_int64), ("max_width", C.c_int64), ("merge_width", C.c_int64),
+                ("zero_pivots", C.c_int64), ("first_zero_pivot_row", C.c_int64)]
 
 
 class Timings(C.Structure):
@@ -224,7 +230,7 @@ class Context:
         _check(lib().pem_debug_refused_launch(self._h))
 
     def trsv_split(self, on):
-        """test hook (pem_test.h): on forces merge_width = 0 in this context's triangular solves, one launch per level"""
+        """test hook (pem_test.h): on forces merge_width = 0 in this context's triangular solves and ILU(0), one launch per level"""
         _check(lib().pem_test_trsv_split(self._h, int(bool(on))))
 
     def set_graph_replay(self, on):
@@ -744,6 +750,33 @@ class Tiled:
         i = TrsvInfo()
         _check(lib().pem_tiled_trsv_info(self.ctx._h, self._h, TRSV_UPLO.index(uplo), C.byref(i)))
         return {k: int(getattr(i, k)) for k, _ in TrsvInfo._fields_}
+
+    def ilu0(self):
+        """ILU(0): the incomplete LU of this square tiling on its own pattern as a new tiling F of the same
+        pattern and dtype -- L's strict lower triangle (unit diagonal, not stored) and U with its diagonal.  Bit-exact order: section
+        3y.  Every row must store its diagonal entry (PemError names the first that does not).  Waits."""
+        h = C.c_void_p()
+        _check(lib().pem_tiled_ilu0(self.ctx._h, self._h, C.byref(h)))
+        return Tiled(self.ctx, h)
+
+    def set_values_from_ilu0(self, A):
+        """Refresh a tiling made by A.ilu0() from A's current values, in place: bit for bit a fresh A.ilu0().  Ordered on the context's
+        stream; returns without waiting and allocates nothing."""
+        _check(lib().pem_tiled_set_values_from_ilu0(self.ctx._h, self._h, A._h))
+
+    def ilu0_info(self):
+        """of a factor: levels, launches, max_width and merge_width of the factorisation's launch plan, zero_pivots (rows whose f_ii is
+        +-0, not finite or not stored) and first_zero_pivot_row (1-based, 0 if none), as a dict.  Waits."""
+        i = Ilu0Info()
+        _check(lib().pem_tiled_ilu0_info(self.ctx._h, self._h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in Ilu0Info._fields_}
+
+    def lu_solve(self, b, out=None, work=None):
+        """z = U^-1 L^-1 b with this tiling an ILU(0) factor: trsv(b, "lower", unit_diag=True, out=work), then trsv(work, "upper",
+        out=out).  b, out, work: as trsv's vectors; out and work are allocated when None.  Never waits once both schedules exist.
+        Returns out."""
+        work = self.trsv(b, "lower", unit_diag=True, out=work)
+        return self.trsv(work, "upper", out=out)
 
     def _bytes(self, fn, name, v, n):
         """the device pointer of a contiguous torch.bool / torch.uint8 tensor of n bytes on the context's device; None passes as NULL"""

@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) scale_kernel(const long long *__restrict_
 // R's shape, sizes and structural arrays from A: device copies of everything derive_tiled produces but the values, the host copy
 // of the tile row pointers too.  R's vals and vals_t are allocated and left for the caller's kernel.  One sizing phase over R's own
 // arrays (and its vmap_t where the caller will fill it): none of the context's conversion scratch is needed, so none is grown.
-static pem_status clone_structure(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, bool with_vmap_t)
+pem_status pem::clone_structure(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, bool with_vmap_t)
 {
     set_tiled_shape(R, A->value_bytes, A->rows, A->cols);
     R->nnz = A->nnz;

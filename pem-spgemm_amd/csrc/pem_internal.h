@@ -199,7 +199,7 @@ struct pem_ctx {
     pem::DevBuf fr_scratch;
     size_t fr_flags_off = 0;
     int64_t fr_lines = -1;
-    int dbg_trsv_split = 0;            // pem_test_trsv_split: 1 forces the triangular solve's merge_width to 0 (one launch per level)
+    int dbg_trsv_split = 0;            // pem_test_trsv_split: 1 forces the triangular solve's and ILU(0)'s merge_width to 0 (one launch per level)
     int dbg_scan_force = 0;            // pem_debug_scan_i32: 0 automatic, 2 single-launch chained scan, 3 three-launch scan
     int dbg_scan_stall_ticket = -1;    // ... and the chained scan's block that stalls before it publishes
     // timing
@@ -330,9 +330,12 @@ uint64_t next_tiled_serial();
 //                                              of the build, which the first refresh's map kernel reads again.  idx[1] (first
 //                                              refresh): a pointer per cell, the blocks' vals, rewritten by every refresh.
 //                                              map: int2[nnz], every entry's (cell, slot in that block's vals).
+//   ILU0    pem_tiled_ilu0 (ilu0.hip)          src[0] = A's serial.  No map: the pattern is A's, so the refresh copies A's vals slot for
+//                                              slot and factors them in place; the tiling's own vmap_t (made by the build) fills
+//                                              vals_t, and its own lower trsv schedule (made by the build) orders the launches.
 // map is built on the first refresh (map_ready); the int32 maps are what refresh_gather's four-entry loads need (values.hip).
 struct Derivation {
-    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK, BUILD, CONCAT } kind = NONE;
+    enum Kind { NONE, CPLAN, EWISE, SELECT, TRANSPOSE, EXTRACT, ASSIGN, APPLY, SCALE, KRON, TOPK, BUILD, CONCAT, ILU0 } kind = NONE;
     uint64_t src[2] = {0, 0};
     std::vector<uint64_t> srcs;   // CONCAT: one serial per grid cell
     int op = 0, pattern = 0;

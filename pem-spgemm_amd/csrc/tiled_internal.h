@@ -1,5 +1,5 @@
 // tiled_internal.h -- what the units that build, refresh or look up a tiling share (convert.hip, values.hip, chain.hip, mask.hip,
-// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip, sddmm.hip, sampled.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip) is built by build_derived around its route: the shape
+// ewise.hip, select.hip, topk.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip, sddmm.hip, sampled.hip, trsv.hip, ilu0.hip).  A derived tiling (chain.hip, ewise.hip, select.hip, extract.hip, assign.hip, apply.hip, kron.hip, build.hip, concat.hip, ilu0.hip) is built by build_derived around its route: the shape
 // (set_tiled_shape), the payload arrays (reserve_payload, begin_payload), the route's payload kernels, derive_tiled; its
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.  build.hip shares the
 // HEAD of pem_tiled_from_coo* (coo_sort_keys, then the radix sort) and this tail; its payload kernel is its own, because it compacts the
@@ -98,6 +98,31 @@ pem_status refresh_derived(pem_ctx *ctx, pem_tiled *t, BuildMap build_map, Launc
     }
     ++t->value_version;
     return PEM_OK;
+}
+
+// R's shape, sizes and structural arrays from A: device copies of everything derive_tiled produces but the values; R's vals and
+// vals_t (and vmap_t with with_vmap_t) are allocated and left for the caller's kernel (apply.hip; ilu0.hip)
+pem_status clone_structure(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, bool with_vmap_t);
+
+// ---- the level schedule of a triangle (trsv.hip; the lower one is also ILU(0)'s, ilu0.hip) ----
+// A->trsv[uplo] on first use: reads the tile CSR back, counts the rows without a stored diagonal entry.  Synchronises once.
+pem_status ensure_trsv(pem_ctx *ctx, const pem_tiled *A, int uplo);
+// the launches of a schedule under merge width mw: fn(first level, end level, merged) for every one, in order; returns their
+// number.  A level wider than mw is one launch, a maximal run of narrower levels is one (merged) launch of one workgroup.
+template <typename Fn>
+int64_t trsv_for_launches(const TrsvSched &S, int mw, Fn fn)
+{
+    const int levels = (int)S.h_lvl.size() - 1;
+    int64_t launches = 0;
+    for (int v = 0; v < levels; ++launches) {
+        int e = v + 1;
+        const bool merged = S.h_lvl[v + 1] - S.h_lvl[v] <= mw;
+        if (merged)
+            while (e < levels && S.h_lvl[e + 1] - S.h_lvl[e] <= mw) ++e;
+        fn(v, e, merged);
+        v = e;
+    }
+    return launches;
 }
 
 // ---- device: tile lookups in a tiling's tile CSR (mask.hip, ewise.hip) ----

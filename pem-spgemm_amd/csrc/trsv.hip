@@ -174,10 +174,12 @@ __global__ void trsv_diag_kernel(const int4 *__restrict__ rows, const uint32_t *
     atomicMax(first, (unsigned long long)(n - i));
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------------------
-// the schedule (once per tiling and triangle)
+// the schedule (once per tiling and triangle; also ilu0.hip's, tiled_internal.h)
 // ------------------------------------------------------------------------------------------
-pem_status ensure_trsv(pem_ctx *ctx, const pem_tiled *A, int uplo)
+pem_status pem::ensure_trsv(pem_ctx *ctx, const pem_tiled *A, int uplo)
 {
     TrsvSched &S = A->trsv[uplo];
     if (S.ready) return PEM_OK;
@@ -236,24 +238,9 @@ pem_status ensure_trsv(pem_ctx *ctx, const pem_tiled *A, int uplo)
     return PEM_OK;
 }
 
-int trsv_merge_width(const pem_ctx *ctx) { return ctx->dbg_trsv_split ? 0 : TRSV_MERGE; }
+namespace {
 
-// the launches of a schedule: fn(first level, end level, merged) for every one, in order; returns their number
-template <typename Fn>
-int64_t trsv_for_launches(const TrsvSched &S, int mw, Fn fn)
-{
-    const int levels = (int)S.h_lvl.size() - 1;
-    int64_t launches = 0;
-    for (int v = 0; v < levels; ++launches) {
-        int e = v + 1;
-        const bool merged = S.h_lvl[v + 1] - S.h_lvl[v] <= mw;
-        if (merged)
-            while (e < levels && S.h_lvl[e + 1] - S.h_lvl[e] <= mw) ++e;
-        fn(v, e, merged);
-        v = e;
-    }
-    return launches;
-}
+int trsv_merge_width(const pem_ctx *ctx) { return ctx->dbg_trsv_split ? 0 : TRSV_MERGE; }
 
 template <typename VT, bool UPPER>
 pem_status trsv_launch(pem_ctx *ctx, const pem_tiled *A, int unit, const VT *b, VT *x)

@@ -110,6 +110,7 @@ struct Options {
     const char *sampled_path = nullptr;                             // --sampled S.mtx [--sampled-bt]: see sampled_stage
     bool sampled_bt = false, triangles = false;                     // --triangles: see sampled_stage
     const char *trsv_spec = nullptr, *rhs_path = nullptr;           // --trsv lower|upper[:unit] [--rhs b.mtx]: see trsv_stage
+    bool ilu0 = false;                                              // --ilu0: see ilu0_stage
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -165,7 +166,7 @@ static void parse_args(int argc, char *argv[], Options *o)
         const char *name;
         bool *flag, value;
     } plain[] = {{"--fp32", &o->fp32, true}, {"--mask-complement", &o->mask_complement, true}, {"--no-tune-split", &o->tune_split, false},
-                 {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}};
+                 {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}, {"--ilu0", &o->ilu0, true}};
     o->args.assign(1, argv[0]);
     for (int r = 1; r < argc; ++r) {
         bool taken = false;
@@ -212,6 +213,7 @@ static const struct ClashRule {
     {"--topk", {"--gpus", "--power"}, ""},
     {"--hstack", {"--gpus", "--vstack"}, ""},
     {"--vstack", {"--gpus"}, ""},
+    {"--ilu0", {"--gpus", "--power"}, ""},
     {"--dup", {"--gpus", "--cache"}, ""},   // (a cached tiling would depend on the op, which its key does not carry)
 };
 
@@ -438,9 +440,10 @@ static int validate_dense(Options *o)
 }
 
 // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source; --argreduce:
-// the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front
+// the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front; --ilu0: what it does not combine with
 static int validate_vectors(Options *o)
 {
+    if (o->ilu0 && clashes(*o, "--ilu0")) return 1;
     if (o->rhs_path && !o->trsv_spec) {
         printf("--rhs needs --trsv lower|upper[:unit]. Exiting.\n");
         return 1;
@@ -662,7 +665,7 @@ static int validate_sampled(Options *o)
                      {"--hstack", o->stack_paths[0] != nullptr}, {"--vstack", o->stack_paths[1] != nullptr}, {"--reduce", o->reduce_spec != nullptr},
                      {"--bfs", o->bfs_spec != nullptr}, {"--argreduce", o->argreduce_spec != nullptr}, {"--bfs-parents", o->bfs_parents_spec != nullptr},
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
-                     {"--trsv", o->trsv_spec != nullptr},
+                     {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1297,7 +1300,7 @@ struct Operands {
 struct Result {
     Tiled L_own;              // --power: A^(K-1), the last product's left operand
     pem_tiled *L = nullptr;   // A otherwise
-    Tiled sum, app, scl, sel, top, ext, asg, krn, stk, sd;   // what --add, --apply, --row/col-scale, --select, --topk, --extract-*, --assign-into, --kron, --hstack / --vstack and --sddmm made
+    Tiled sum, app, scl, sel, top, ext, asg, krn, stk, sd, ilu;   // what --add, --apply, --row/col-scale, --select, --topk, --extract-*, --assign-into, --kron, --hstack / --vstack, --sddmm and --ilu0 made
     Plan plan;
     pem_cplan_info ci;
     pem_tiled *last = nullptr;          // the final result so far when it is a tiling (null: it is the plan's C) ...
@@ -1835,6 +1838,36 @@ static int reduce_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--ilu0` replaces the final result (C, or what --add, --select, --apply ... left) by its incomplete LU
+// on its own pattern (pem_tiled_ilu0): L's strict lower triangle and U in one tiling.  It is the last matrix stage: the vector
+// stages see the factor, so `--ilu0 --trsv lower:unit --rhs b.mtx` applies L^-1, and --out writes F.  The result must be square and
+// store every diagonal entry.  The CSV row describes the product.
+static int ilu0_stage(const Options &, pem_ctx *ctx, Result *r)
+{
+    auto t0 = Clock::now();
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    pem_tiled_info si;
+    CHECK(pem_tiled_get_info(src.t, &si));
+    if (si.rows != si.cols) {
+        printf("--ilu0: %s is %d x %d; an incomplete LU needs a square matrix. Exiting.\n", r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    if (pem_tiled_ilu0(ctx, src.t, out(ctx, r->ilu)) != PEM_OK) {
+        printf("--ilu0: %s. Exiting.\n", pem_last_error());
+        return 1;
+    }
+    const double total_ms = ms_since(t0);
+    pem_tiled_info fi;
+    CHECK(pem_tiled_get_info(r->ilu.get(), &fi));
+    pem_ilu0_info ii;
+    CHECK(pem_tiled_ilu0_info(ctx, r->ilu.get(), &ii));
+    printf("ilu0: of %s: ilu0 %.2fms, total %.2fms, nnz %lld, %lld levels, %lld launches, %lld zero pivots\n", r->last_name, fi.conv_ms, total_ms,
+           (long long)fi.nnz, (long long)ii.levels, (long long)ii.launches, (long long)ii.zero_pivots);
+    r->now_last(r->ilu, "the ILU(0) factor");
+    return 0;
+}
+
 // `--trsv lower|upper[:unit] [--rhs b.mtx]` solves T x = b on the device (pem_tiled_trsv), T the named
 // triangle of the final result (what --reduce would fold; it must be square) as stored, the diagonal taken as 1 under :unit.  b is
 // a Matrix-Market `array real general` file of one column, all ones without --rhs.  One line reports the solve's time (the
@@ -2142,6 +2175,7 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
                (o.assign_accum == PEM_ACCUM_NONE ? std::string() : std::string(" accum ") + binop_names[o.assign_accum]);
     if (r->krn) how += std::string(", kron ") + binop_names[o.kron_op] + " with " + o.kron_path;
     if (r->stk) how += std::string(o.stack_paths[1] ? ", vstack with " : ", hstack with ") + o.stack_paths[o.stack_paths[1] ? 1 : 0];
+    if (r->ilu) how += ", its ILU(0) factor (L strictly below the diagonal, unit diagonal not stored; U on and above)";
     how += " by pemspgemm (pem-spgemm_amd)";
     int rc = 0;
     if (o.trsv_uplo >= 0) {
@@ -2211,6 +2245,7 @@ int main(int argc, char *argv[])
     if (!rc && in.Into) rc = assign_stage(o, ctx, in, &r);
     if (!rc && in.Kt) rc = kron_stage(o, ctx, in, &r);
     if (!rc && in.St) rc = stack_stage(o, ctx, in, &r);
+    if (!rc && o.ilu0) rc = ilu0_stage(o, ctx, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
     if (!rc && o.trsv_uplo >= 0) rc = trsv_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
