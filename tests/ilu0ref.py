@@ -50,3 +50,15 @@ def ilu0(n, rp, ci, v, dtype=np.float64):
                 f[e] = acc
                 longest = max(longest, chain)
     return np.array(f, dtype), longest
+
+
+def pivots(n, rp, ci, f):
+    """(zero_pivots, first_zero_pivot_row) as pem_tiled_ilu0_info counts them: the rows whose f_ii is +-0, not finite or not stored,
+    and the first of them 1-based (0 if none)"""
+    rp, ci, f = np.asarray(rp, np.int64), np.asarray(ci, np.int64), np.asarray(f)
+    I = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    d = I == ci
+    good = np.zeros(n, bool)
+    good[I[d]] = (f[d] != 0) & np.isfinite(f[d])
+    bad = np.flatnonzero(~good)
+    return len(bad), int(bad[0]) + 1 if len(bad) else 0

@@ -2,9 +2,10 @@
 
 first_divergence(program, mutation) runs the true model and the mutated one side by side and returns (step, where) of the first
 point at which they differ in something tests/seqrun.py observes -- the status of a call, the handle a step wrote, a dense
-result, or, at an audit, any live handle.  A library that follows the true model must make the runner report its mismatch exactly
-there: tests/test_gpu_seq.py runs each NEGATIVE seed under its mutation and asserts that, tests/test_seq_cpu.py asserts that the
-committed figures below are what first_divergence gives.  No GPU import.
+result (every array of it), or, at an audit, any live handle (a factor's ilu0_info fields included).  A library that follows the
+true model must make the runner report its mismatch exactly there: tests/test_gpu_seq.py runs each NEGATIVE seed under its
+mutation and asserts that, tests/test_seq_cpu.py asserts that the committed figures below are what first_divergence gives.  No GPU
+import.
 """
 import numpy as np
 
@@ -17,12 +18,17 @@ NEGATIVE = {
     "no_bump": (103, (19, "audit")),
     "stale_vals_t": (101, (9, "audit")),
     "no_option_reset": (102, (19, "audit")),
+    "concat_stale_block": (1406, (21, "step")),
+    "ilu0_stale_source": (1408, (9, "step")),
+    "trsv_stale_values": (1401, (8, "step")),
 }
 
 
 def _tiling_differs(a, b, kind="exact", transposed_too=True):
     if (a.rows, a.cols, a.nnz) != (b.rows, b.cols, b.nnz) or not np.array_equal(a.ci, b.ci) or not sm.same(a.vals, b.vals, kind):
         return True
+    if transposed_too and a.prov is not None and a.prov[0] == "ilu0" and not np.array_equal(sm.pivot_fields(a), sm.pivot_fields(b)):
+        return True                      # (the audit's ilu0_info; its trsv_info reads the pattern alone, which no mutation touches)
     return transposed_too and not sm.same(a.vals_t, b.vals_t)
 
 

@@ -13,14 +13,49 @@ written last is read next more often than not, and kinds the program has used le
 every kind in both value types).
 
 Text form: one JSON array [op, [ids], {arguments}] per line (dumps / loads); tools/seq_replay.py reads it back.
+
+Two operation sets.  A seed below SET2_FROM draws from the first set (_Gen), and program() returns for it what it returned when
+the sequence test was added (tests/golden/seq_program_digests.json holds the digests of SEEDS' programs).  A seed from SET2_FROM
+on draws from the second set (_Gen2; SEEDS2 is its committed list): everything the first has, plus
+  derivations with a refresh   apply, scale, transpose, extract, assign, kron, concat, build / build_device (keep_map), ilu0,
+                               each with its set_values_from_*
+  derivations without one      select_topk, sampled_mxm, a build without a map; split, emitted as its extracts (d_extract draws
+                               pieces of a partition by ranges, which is what Tiled.split emits)
+  a writer                     set_values_sampled_mxm (every semiring, transpose_b, with and without accumulate)
+  dense readers                triangle_count (on symmetric patterns),               mxv_frontier, mxv_arg, reduce_arg, bfs, bfs_parents, trsv, lu_solve, trsv_info, ilu0_info
+and the refusals of REFUSALS2.  Boundary values (powi's 1, 2, 64; top-k's k = 0, 1, the line length and beyond; the dup ops;
+run lengths either side of BUILD_INORDER_MAX; the concat shapes) come from the feature tests' lists.  Square matrices that store their
+diagonal come from tests/trsvcases.py, tests/ilu0cases.py (hubs_1600 rarely) and random ones with the diagonal forced in.  Three
+scenarios are scripted into the random order and interleaved with it (start_scenario2): a chain of three derivations refreshed
+link by link, the life of a factor, a concat between refreshes.
+
+Special values in the second set: trsv, lu_solve and ilu0 run on whatever values the program wrote last, the inf / NaN / zero /
+subnormal mix included -- trsvref and ilu0ref are bit-exact there (NaN equals NaN; test_gpu_trsv.py and test_gpu_ilu0.py check
+zero pivots, infinities and NaN by bits), so no special value is left out of them.
+
+Left out, because the header lets the library round differently from the references there: runs of duplicates longer than
+BUILD_INORDER_MAX under plus and times (they may be regrouped; the other six dup ops get such runs), and set_values_sampled_mxm
+with accumulate under plus_pair (a tile pair's count enters in one addition).  Also left out: refusals of trsv_info / ilu0_info.
+
+The second set's pool holds MAX_TILINGS2 = 10 tilings (more kinds of derived tilings have to be alive at once).  Most of its draws
+go to r_needy, which serves the (kind, value type) a program ran least in a fixed round that every program enters at its own
+place: that, not chance, is what lets 24 x 120 steps reach every new kind ten times in both value types.  The first set's kinds
+keep a share (conversions, writers, plans and readers through the categories, ewise / select / sddmm / from_cplan / save_load
+through a draw of their own), so the new readers and refreshes also meet sources that an old feature wrote last; the step-wise
+plan calls, set_semiring and the exports are drawn rarely here -- the first set covers them.
 """
 import json
 
 import numpy as np
 
+import applyref
+import argref
+import buildref
 import ewiseref
+import kronref
 import selectref
 import seqmodel as sm
+import topkref
 from semiringref import SEMIRINGS
 
 MAX_TILINGS, MAX_PLANS = 8, 4
@@ -44,6 +79,35 @@ CONTEXT_KINDS = ("session", "torch_stream", "graph_replay")
 # the committed programs: seed i of the list runs on context kind CONTEXT_KINDS[i % 3] (8 seeds per kind)
 SEEDS = tuple(range(101, 125))
 STEPS = 120
+
+# ---- the second operation set (_Gen2): seeds from SET2_FROM on draw from it; SEEDS2 is dealt to the context kinds as SEEDS is
+SET2_FROM = 1000
+# How SEEDS2 was found: with the weights below, runs of 24 consecutive seeds starting at 1201, 1301, ... were tried against
+# test_second_set_coverage_conditions (tests/test_seq_cpu.py); about half of them meet every condition (1201, 1301, 1401, 1701,
+# 1901 of the first ten), and 1401 was taken.  After a change to the weights, BOOST2 or a draw: search
+# again the same way, then take the three figures of seqcontrol.NEGATIVE from seqcontrol.first_divergence.
+SEEDS2 = tuple(range(1401, 1425))
+TRSV_CASES = ("dense_1", "dense_15", "dense_16", "dense_17", "dense_33", "bidiagonal_200", "arrow_400", "wide_thin_wide",
+              "grid_40x40_red_black", "random_600")                  # tests/trsvcases.py's
+TRSV_WEIGHT = (1, 2, 2, 3, 3, 2, 1.5, 0.7, 0.7, 1)
+ILU0_CASES = ("dense_1", "dense_15", "dense_16", "dense_17", "dense_33", "tridiagonal_200", "band_100_20", "grid_40x40_red_black",
+              "wide_thin_wide", "double_arrow_400", "random_300", "hubs_1600")   # tests/ilu0cases.py's
+ILU0_WEIGHT = (1, 2, 2, 3, 3, 2, 1.5, 0.7, 0.7, 1, 1.5, 0.15)
+CONCAT_SHAPES = ("1xn", "nx1", "2x2", "none_cell", "same_twice", "zero_strip")
+# size guards of the second set: entries of a solve or a factor (trsvref and ilu0ref walk them in Python), ilu0ref's inner steps,
+# nnz(A) * nnz(B) of a kron, the entries of a concat, the larger dimension of either, the length of an index list in a record
+MAX_TRSV_NNZ, MAX_ILU0_COST, MAX_KRON_NNZ, MAX_CONCAT_NNZ, MAX_DIM2, MAX_LIST = 30_000, 200_000, 40_000, 60_000, 6000, 300
+KINDS2_T = ("build", "build_device", "set_values_from_build", "sampled_mxm", "set_values_sampled_mxm", "triangle_count", "apply", "set_values_from_apply", "scale", "set_values_from_scale", "assign", "set_values_from_assign", "select_topk",
+            "mxv_frontier", "mxv_arg", "reduce_arg", "bfs", "bfs_parents", "transpose", "set_values_from_transpose", "extract", "set_values_from_extract", "kron",
+            "set_values_from_kron", "concat", "set_values_from_concat", "ilu0", "set_values_from_ilu0", "trsv", "lu_solve", "trsv_info",
+            "ilu0_info")
+REFUSALS2 = ("wrong_kind_refresh", "wrong_source_refresh", "concat_swapped", "concat_wrong_count", "trsv_nonsquare", "ilu0_nonsquare",
+             "trsv_missing_diag", "ilu0_missing_diag", "trsv_overlap", "powi_thunk", "extract_empty_device", "assign_repeat_device", "build_refresh_no_map",
+             "build_refresh_wrong_nnz")
+MAX_TILINGS2 = 10                      # the second set's pool: more kinds of derived tilings have to be alive at once
+MAX_SAMPLED_WORK = 300_000             # matched-pair candidates of one sampled product (sampledref lists them all)
+BOOST2 = dict(build_refresh_no_map=8.0, build_refresh_wrong_nnz=3.0, concat_swapped=3.0, ilu0_info=14.0, lu_solve=9.0, kron=4.0, ilu0=6.0, assign=3.0, concat=1.5, trsv_info=30.0, bfs=14.0, bfs_parents=12.0, apply=1.5, transpose=1.5, extract=2.0, select_topk=1.5,
+              set_values_from_extract=2.0)
 
 KINDS_T = ("from_coo", "from_csr", "from_coo_device", "set_values", "set_values_device", "set_values_from_cplan", "set_values_from_ewise",
            "set_values_from_select", "set_values_sddmm", "from_cplan", "ewise", "select", "sddmm", "mxv", "reduce", "spmm", "save_load", "close")
@@ -80,6 +144,8 @@ def record_dtype(model, rec):
 
 
 class _Gen:
+    MAX_T = MAX_TILINGS               # the pool's tilings (the second set takes more)
+
     def __init__(self, seed):
         self.rng = np.random.default_rng(seed)
         self.m = sm.Model()
@@ -142,7 +208,7 @@ class _Gen:
 
     # ---- records: each returns a record or None when the pool offers no operand ----------------------------------------------------
     def r_convert(self, dtype):
-        if len(self.m.t) >= MAX_TILINGS:
+        if len(self.m.t) >= self.MAX_T:
             return self.r_close(dtype)
         op = self.least(("from_coo", "from_csr", "from_coo_device"), dtype)
         peers = self.tilings(lambda T: sm.dtname(T.dtype) == dtype and T.rows * T.cols > 0)
@@ -230,7 +296,7 @@ class _Gen:
             kinds.append("step3")
         if self.m.current(p):
             kinds += ["export_csr", "export_coo"]
-            if len(p.C[1]) <= MAX_C_NNZ and len(self.m.t) < MAX_TILINGS:
+            if len(p.C[1]) <= MAX_C_NNZ and len(self.m.t) < self.MAX_T:
                 kinds += ["from_cplan"]
         op = self.least(kinds, dtype)
         if op == "set_semiring":
@@ -300,7 +366,7 @@ class _Gen:
         return int(self.pick([k for k in SDDMM_KS if max(T.nnz, T.rows, T.cols) * (k + 11) <= MAX_DENSE_WORK] or [0]))
 
     def r_derive(self, dtype):
-        if len(self.m.t) >= MAX_TILINGS:
+        if len(self.m.t) >= self.MAX_T:
             return self.r_close(dtype)
         op = self.least(("ewise", "select", "sddmm", "from_cplan", "save_load"), dtype)
         ts = self.tilings(lambda T: sm.dtname(T.dtype) == dtype)
@@ -498,13 +564,650 @@ class _Gen:
         self.prog.append(rec)
 
 
+class _Gen2(_Gen):
+    """the second operation set: everything _Gen draws, plus the records listed in the module's docstring"""
+
+    MAX_T = MAX_TILINGS2
+
+    def __init__(self, seed):
+        super().__init__(seed)
+        self.turn = (int(seed) * 29) % (2 * len(KINDS2_T))   # where this program starts in the round of r_needy
+        self.script2 = []                # pending steps of a scenario of the second set (see start_scenario2)
+        self.cast = []                   # the tilings that scenario works on: not closed while it runs
+        self.started = {}
+        self.stalls = 0
+        self.owed = None                 # the derivation a close made room for
+        self.young = []                  # derived tilings not refreshed yet: half of them are refreshed soon
+
+    def least(self, kinds, dtype):
+        if tuple(kinds) == ("plan_a", "plan_b", "row", "col"):
+            # the old readers of the tiling written last, after writer `dtype`: ties go round from a place every program has of its own,
+            # so that the seed list as a whole follows every writer by every reader
+            kinds = list(kinds)
+            return min(kinds, key=lambda k: (self.count.get((k, dtype), 0), (kinds.index(k) - self.turn - len(str(dtype))) % 4))
+        w = [BOOST2.get(k, BOOST.get(k, 1.0)) / (1 + self.count.get((k, dtype), 0)) ** 2 for k in kinds]
+        return self.pick(kinds, w)
+
+    def cycle(self, name, options):
+        """one of `options`, those this program drew least under `name` first"""
+        x = self.least(options, name)
+        self.count[(x, name)] = self.count.get((x, name), 0) + 1
+        return x
+
+    # ---- the pool ----------------------------------------------------------------------------------------------------------
+    def named(self, tid):
+        T = self.m.t[tid]
+        if tid in self.cast or any(T is p.A or T is p.B or T is p.M for p in self.m.p.values()):
+            return True
+        return any(tid in sm.sources(D.prov) for D in self.m.t.values())
+
+    def of(self, dtype, pred=lambda T: True):
+        return self.tilings(lambda T: sm.dtname(T.dtype) == dtype and pred(T))
+
+    @staticmethod
+    def solvable(T):
+        return T.rows == T.cols and T.nnz <= MAX_TRSV_NNZ
+
+    @staticmethod
+    def factorable(T):
+        return T.rows == T.cols and T.nnz <= MAX_TRSV_NNZ and sm.ilu0_cost(T) <= MAX_ILU0_COST and sm.missing_diag(T)[0] == 0
+
+    def r_convert(self, dtype):
+        """nearly half of the converted matrices are square and store their diagonal"""
+        if len(self.m.t) >= self.MAX_T or not self.chance(0.55):
+            return super().r_convert(dtype)
+        return self.square_convert(dtype)
+
+    def square_convert(self, dtype):
+        op = self.least(("from_coo", "from_csr", "from_coo_device"), dtype)
+        how = self.pick(("trsv", "ilu0", "randdiag"), (1.0, 1.0, 1.3))
+        if how == "trsv":
+            src = {"trsv": [self.pick(TRSV_CASES, TRSV_WEIGHT), int(self.chance(0.5))]}
+        elif how == "ilu0":
+            src = {"ilu0": self.pick(ILU0_CASES, ILU0_WEIGHT)}
+        else:
+            n = int(self.pick(DIMS))
+            src = {"randdiag": [self.seed(), n, max(1, int(n * n * self.pick(DENSITIES)))]}
+        return (op, (), dict(out=self.new_t(), src=src, dtype=dtype, transpose=op != "from_csr" and self.chance(0.3)))
+
+    # ---- derivations: each takes the tiling to derive from (None: any of the value type) and returns a record or None ----------------
+    def d_apply(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype)
+        if not ts:
+            return None
+        op = self.cycle("apply_op", applyref.OPS)
+        thunk = float(self.cycle("powi_k", (1, 2, 64))) if op == "powi" else 0.0 if op in applyref.UNARY else float(self.pick(VALUE_THUNKS + (2.0,)))
+        return ("apply", (self.pick(ts),), dict(out=self.new_t(), op=op, thunk=thunk))
+
+    def scale_args(self):
+        rows, cols = self.cycle("scale_vectors", ((True, False), (False, True), (True, True)))
+        return dict(rows=self.seed() if rows else None, cols=self.seed() if cols else None, special=self.chance(0.25))
+
+    def d_scale(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype)
+        if not ts:
+            return None
+        return ("scale", (self.pick(ts),), dict(out=self.new_t(), op=self.cycle("scale_op", applyref.BINOPS), **self.scale_args()))
+
+    def region_spec(self, dim, n):
+        """n different indices of 0 .. dim - 1 for assign: all of them in order where n == dim, a range, a host or a device list"""
+        how = self.cycle("assign_list", ("all", "slice", "host", "device") if n == dim else ("slice", "host", "device"))
+        if how == "all":
+            return None
+        if how == "slice":
+            lo = int(self.rng.integers(0, dim - n + 1))
+            return ["slice", lo, lo + n, 1]
+        return [how, [int(x) for x in self.rng.permutation(dim)[:n]]]
+
+    def d_assign(self, dtype, i=None):
+        """C(I, J) = A with A any tiling of the pool that fits into C: where A stores less than C's region did, entries are deleted"""
+        fits = lambda C, A: A.rows <= C.rows and A.cols <= C.cols and max(A.rows, A.cols) <= MAX_LIST and C.nnz + A.nnz <= MAX_C_NNZ // 2
+        pairs = [(c, x) for c in ([i] if i is not None else self.of(dtype)) for x in self.of(sm.dtname(self.m.t[c].dtype))
+                 if fits(self.m.t[c], self.m.t[x])]
+        if not pairs:
+            return None
+        c, x = self.pick(pairs)
+        C, A = self.m.t[c], self.m.t[x]
+        accum = self.cycle("assign_accum", (None,) + applyref.BINOPS) if self.chance(0.5) else None
+        return ("assign", (c, x), dict(out=self.new_t(), rows=self.region_spec(C.rows, A.rows), cols=self.region_spec(C.cols, A.cols), accum=accum))
+
+    def d_build(self, dtype, i=None, op=None):
+        """build / build_device from a small matrix's entries repeated; runs longer than the in-order limit only under the ops whose
+        result does not depend on the grouping (the header lets plus and times round differently there)"""
+        if self.chance(0.3):
+            src = {"case": self.pick(("tiny_9x9", "rand_50", "ragged_37", "dense_tile", "empty_rows"))}
+        else:
+            rows, cols = int(self.pick(DIMS)), int(self.pick(DIMS))
+            src = {"rand": [self.seed(), rows, cols, min(3000, max(1, int(rows * cols * self.pick(DENSITIES)))), False]}
+        dup = self.cycle("dup", buildref.DUP_OPS)
+        op = op or self.least(("build", "build_device"), dtype)
+        return (op, (), dict(out=self.new_t(), dtype=dtype, src=src, dup=dup, transpose=self.chance(0.3), keep_map=self.chance(0.6),
+                             lens_seed=self.seed(), long=dup not in ("plus", "times") and self.chance(0.5)))
+
+    def d_build_device(self, dtype, i=None):
+        return self.d_build(dtype, op="build_device")
+
+    def sampled_operands(self, s, fixed=None):
+        """(a, b, transpose_b) with A . B (or A . B^T) of S's shape, of one value type (fixed: that of an in-place target)"""
+        S = self.m.t[s]
+        out = []
+        for a, A in self.m.t.items():
+            if A.rows != S.rows or (fixed is not None and (A.dtype != fixed or a == s)):
+                continue
+            if S.nnz and int(np.diff(A.rp)[sm.rows_of(S.rows, S.rp)].sum()) > MAX_SAMPLED_WORK:
+                continue
+            for b, B in self.m.t.items():
+                if B.dtype == A.dtype and not (fixed is not None and b == s):
+                    out += [(a, b, tb) for tb in (False, True) if ((B.cols, B.rows) if tb else (B.rows, B.cols)) == (A.cols, S.cols)]
+        return out
+
+    def d_sampled_mxm(self, dtype, i=None):
+        cand = [(s,) + x for s in self.tilings() for x in self.sampled_operands(s) if sm.dtname(self.m.t[x[0]].dtype) == dtype]
+        if not cand:
+            return None
+        s, a, b, tb = self.pick(cand)
+        return ("sampled_mxm", (s, a, b), dict(out=self.new_t(), dtype=dtype, semiring=self.cycle("sampled_semiring", sorted(SEMIRINGS)), transpose_b=tb))
+
+    def r_sampled_writer(self, dtype):
+        cand = [(t,) + x for t in self.of(dtype, lambda T: T.nnz > 0) for x in self.sampled_operands(t, self.m.t[t].dtype)]
+        if not cand:
+            return None
+        t, a, b, tb = self.pick(cand)
+        semiring = self.cycle("sampled_semiring", sorted(SEMIRINGS))
+        # (an accumulate under plus_pair adds a tile pair's count in one addition: only exact on small integers, so it is left out)
+        return ("set_values_sampled_mxm", (t, a, b), dict(semiring=semiring, transpose_b=tb, accumulate=semiring != "plus_pair" and self.chance(0.5)))
+
+    def d_select_topk(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype)
+        if not ts:
+            return None
+        i = self.pick(ts)
+        T = self.m.t[i]
+        dim = self.cycle("topk_dim", topkref.DIMS)
+        longest = int(np.bincount(T.ci, minlength=1).max() if dim == "cols" else np.diff(T.rp).max()) if T.nnz else 0
+        k = self.cycle("topk_k", ("0", "1", "line", "beyond"))
+        k = {"0": 0, "1": 1, "line": longest, "beyond": longest + int(self.pick((1, 1000)))}[k]
+        return ("select_topk", (i,), dict(out=self.new_t(), k=int(k), order=self.cycle("topk_order", topkref.ORDERS), dim=dim))
+
+    def d_transpose(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype)
+        return ("transpose", (self.pick(ts),), dict(out=self.new_t())) if ts else None
+
+    def index_spec(self, dim, keep_all=False):
+        how = "all" if keep_all else self.cycle("extract_list", ("all", "slice", "host", "device"))
+        if how == "all":
+            return None
+        if how == "slice":
+            lo = int(self.rng.integers(0, dim))
+            return ["slice", lo, int(self.rng.integers(lo + 1, dim + 1)), int(self.pick((1, 1, 2)))]
+        n = min(int(self.pick((1, dim // 2 + 1, dim + 3))), MAX_LIST)
+        return [how, [int(x) for x in self.rng.integers(0, dim, n)]]     # (out of order, with repeats)
+
+    def d_extract(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype, lambda T: T.nnz <= MAX_C_NNZ // 4)
+        if not ts:
+            return None
+        i = self.pick(ts)
+        T = self.m.t[i]
+        if self.chance(0.2):                 # a piece of T.split(row_sizes, col_sizes): what split emits is one extract per piece
+            spec = []
+            for dim in (T.rows, T.cols):
+                cuts = sorted({0, dim, int(self.rng.integers(0, dim + 1))})
+                k = int(self.rng.integers(0, len(cuts) - 1))
+                spec.append(["slice", cuts[k], cuts[k + 1], 1])
+            return ("extract", (i,), dict(out=self.new_t(), rows=spec[0], cols=spec[1]))
+        return ("extract", (i,), dict(out=self.new_t(), rows=self.index_spec(T.rows), cols=self.index_spec(T.cols)))
+
+    def d_kron(self, dtype, i=None):
+        fits = lambda A, B: A.nnz * B.nnz <= MAX_KRON_NNZ and A.rows * B.rows <= 3 * MAX_DIM2 and A.cols * B.cols <= 3 * MAX_DIM2
+        pairs = [(x, y) for x in ([i] if i is not None else self.of(dtype)) for y in self.of(sm.dtname(self.m.t[x].dtype))
+                 if fits(self.m.t[x], self.m.t[y])]
+        if not pairs and i is None:          # (no two tilings of this value type are small enough: convert a small one)
+            rows, cols = int(self.pick((1, 9, 16))), int(self.pick((1, 9, 16)))
+            src = {"rand": [self.seed(), rows, cols, int(self.rng.integers(1, rows * cols + 1)), False]}
+            return (self.least(("from_coo", "from_csr", "from_coo_device"), dtype), (), dict(out=self.new_t(), src=src, dtype=dtype, transpose=False))
+        if not pairs:
+            return None
+        same = [p for p in pairs if p[0] == p[1]]
+        x, y = self.pick(same) if same and self.chance(0.3) else self.pick(pairs)
+        return ("kron", (x, y), dict(out=self.new_t(), op=self.cycle("kron_op", kronref.BINOPS)))
+
+    def d_concat(self, dtype, i=None):
+        ts = [i] if i is not None else self.of(dtype)
+        if not ts:
+            return None
+        i = self.pick(ts)
+        T = self.m.t[i]
+        dtype = sm.dtname(T.dtype)
+        rowmates = self.of(dtype, lambda U: U.rows == T.rows)
+        colmates = self.of(dtype, lambda U: U.cols == T.cols)
+        shape = self.cycle("concat_shape", CONCAT_SHAPES)
+        if shape == "1xn":
+            grid = [[i] + [self.pick(rowmates) for _ in range(int(self.pick((1, 2))))]]
+        elif shape == "nx1":
+            grid = [[i]] + [[self.pick(colmates)] for _ in range(int(self.pick((1, 2))))]
+        elif shape == "2x2":
+            b, c = self.pick(rowmates), self.pick(colmates)
+            fit = self.of(dtype, lambda U: (U.rows, U.cols) == (self.m.t[c].rows, self.m.t[b].cols))
+            grid = [[i, b], [c, self.pick(fit) if fit else None]]
+        elif shape == "none_cell":
+            grid = [[i, None], [None, self.pick(self.of(dtype))]]
+        elif shape == "same_twice":
+            grid = [[i, i]] if self.chance(0.5) else [[i], [i]]
+        else:                            # a strip of no rows (or no columns), given by its size alone
+            grid = [[i], [None]] if self.chance(0.5) else [[i, None]]
+        cells = [[None if h is None else self.m.t[h] for h in row] for row in grid]
+        rs = [next((c.rows for c in row if c is not None), 0) for row in cells]
+        cs = [next((row[k].cols for row in cells if row[k] is not None), 0) for k in range(len(grid[0]))]
+        if sum(rs) > MAX_DIM2 or sum(cs) > MAX_DIM2 or sum(c.nnz for row in cells for c in row if c is not None) > MAX_CONCAT_NNZ:
+            return None
+        return ("concat", tuple(h for row in grid for h in row),
+                dict(out=self.new_t(), dtype=dtype, grid=[len(grid), len(grid[0])], row_sizes=[int(x) for x in rs], col_sizes=[int(x) for x in cs]))
+
+    def d_ilu0(self, dtype, i=None):
+        ts = [i] if i is not None and self.factorable(self.m.t[i]) else [] if i is not None else self.of(dtype, self.factorable)
+        if not ts and i is None:             # (nothing of this value type can be factored: convert something that can)
+            return self.square_convert(dtype)
+        return ("ilu0", (self.pick(ts),), dict(out=self.new_t())) if ts else None
+
+    def r_derive(self, dtype):
+        if len(self.m.t) >= self.MAX_T:
+            return self.r_close(dtype)
+        if self.chance(0.12):
+            return super().r_derive(dtype)
+        # the kind this program derived least in this value type that the pool allows (ties at random)
+        # (ilu0 and kron fit few pools: they count half)
+        kinds = list(sm.KINDS2 + ("select_topk", "build", "build_device", "sampled_mxm"))
+        used = {k: self.count.get((k, dtype), 0) / (3 if k == "kron" else 2 if k == "ilu0" else 1) for k in kinds}
+        for k in sorted(kinds, key=lambda k: (used[k], self.rng.random())):
+            rec = getattr(self, "d_" + k)(dtype)
+            if rec is not None:
+                return rec
+        return None
+
+    # ---- refreshes -----------------------------------------------------------------------------------------------------------
+    def refresh_rec(self, i):
+        """the set_values_from_<kind> record of a tiling of the second set's kinds, None while a source is gone"""
+        T = self.m.t[i]
+        if T.prov is not None and T.prov[0] == "build":
+            return ("set_values_from_build", (i,), {"build": T.prov[2]}) if T.prov[1]["keep_map"] and T.nnz else None
+        if T.prov is None or T.prov[0] not in sm.KINDS2 or T.nnz == 0 or not all(s in self.m.t for s in sm.sources(T.prov)):
+            return None
+        tail = tuple(T.prov[1]) if T.prov[0] == "concat" else sm.sources(T.prov)
+        return ("set_values_from_" + T.prov[0], (i,) + tail, {"scale": True} if T.prov[0] == "scale" else {})
+
+    def emit(self, rec):
+        """a refresh record as it is emitted: a scale's vectors are given anew"""
+        if rec is not None and rec[0] == "set_values_from_scale" and "scale" in rec[2]:
+            return (rec[0], rec[1], dict(self.scale_args(), **{k: v for k, v in rec[2].items() if k != "scale"}))
+        if rec is not None and rec[0] == "set_values_from_build" and "build" in rec[2]:
+            return (rec[0], rec[1], dict(self.vals_args(), nnz_in=rec[2]["build"]))
+        return rec
+
+    def r_chase(self, dtype):
+        cand = []
+        for i, T in self.m.t.items():
+            if T.prov is None or T.nnz == 0:
+                continue
+            k = T.prov[0]
+            if k in sm.KINDS2 + ("build",):
+                ok = self.refresh_rec(i) is not None
+            elif k == "cplan":
+                ok = T.prov[1] in self.m.p
+            else:
+                ok = T.prov[1] in self.m.t and (T.prov[2] in self.m.t if k == "ewise" else T.prov[2] in selectref.POSITIONAL)
+            if ok:
+                cand.append((self.count.get(("set_values_from_" + k, sm.dtname(T.dtype)), 0), i))
+        if not cand:
+            return None
+        low = min(c for c, _ in cand)
+        i = self.pick([i for c, i in cand if c == low])
+        return self.emit(self.refresh_rec(i)) or _Gen.r_writer(self, None, i, refresh=True)
+
+    def r_writer(self, dtype, tid=None, refresh=False):
+        ts = [tid] if tid is not None else self.of(dtype)
+        recs = [r for r in (self.refresh_rec(i) for i in ts) if r]
+        if tid is None and self.chance(0.2):
+            rec = self.r_sampled_writer(dtype)
+            if rec:
+                return rec
+        if recs and (self.chance(0.4) or (refresh and self.m.t[tid].prov[0] in sm.KINDS2)):
+            op = self.least(sorted({r[0] for r in recs}), dtype)
+            return self.emit(self.pick([r for r in recs if r[0] == op]))
+        return super().r_writer(dtype, tid, refresh)
+
+    # ---- readers ---------------------------------------------------------------------------------------------------------------
+    def solve_rec(self, i, uplo=None):
+        T = self.m.t[i]
+        unit = bool(sm.missing_diag(T)[0]) or self.chance(0.4)
+        return ("trsv", (i,), dict(uplo=uplo or self.cycle("uplo", ("lower", "upper")), unit_diag=unit, in_place=self.chance(0.5), **self.vals_args()))
+
+    def r_needy(self, dtype):
+        """the (kind, value type) of the second set this program ran least, the first the pool allows.  Ties go by a fixed round
+        over all of them that every program enters at a place of its own (self.turn), so that the seed list as a whole reaches
+        every one about equally often -- a random tie-break left some short of the ten times tests/test_seq_cpu.py asks for"""
+        cells = [(k, d) for k in KINDS2_T for d in ("f64", "f32")]
+        order = sorted(range(len(cells)), key=lambda c: (self.count.get(cells[c], 0), (c - self.turn) % len(cells)))
+        for c in order[:16]:
+            k, dtype = cells[c]
+            rec = None
+            if k.startswith("set_values_from_"):
+                recs = [r for r in (self.refresh_rec(i) for i in self.of(dtype)) if r and r[0] == k]
+                if recs:
+                    return self.emit(self.pick(recs))
+                k = k[16:]                   # (nothing of that kind is alive: derive one, the refresh comes on a later draw)
+            elif k in ("lu_solve", "ilu0_info") and not [1 for i in self.of(dtype, self.solvable) if (self.m.t[i].prov or ("",))[0] == "ilu0"]:
+                k = "ilu0"
+            if k == "set_values_sampled_mxm":
+                rec = self.r_sampled_writer(dtype)
+            elif k in ("mxv_frontier", "mxv_arg", "reduce_arg"):
+                rec = self.r_fold(dtype, force=k)
+            elif k in ("trsv", "trsv_info", "bfs", "bfs_parents", "lu_solve", "ilu0_info", "triangle_count"):
+                rec = self.r_solve(dtype, force=k)
+                if rec is None and k == "triangle_count":
+                    return self.r_triangles(dtype)
+            elif len(self.m.t) >= self.MAX_T:
+                self.owed = (k, dtype)       # (make room now, derive on the next draw)
+                return self.r_close(dtype)
+            else:
+                rec = getattr(self, "d_" + k)(dtype)
+            if rec is not None:
+                return rec
+        return None
+
+    def r_triangles(self, dtype):
+        """triangle_count on a symmetric pattern of this value type; where none is alive, make room, convert one, count on the next draw"""
+        rec = self.r_solve(dtype, force="triangle_count")
+        if rec is None:
+            self.owed = ("triangle_count", dtype)
+            if len(self.m.t) >= self.MAX_T:
+                return self.r_close(dtype)
+            src = {"ilu0": self.pick(("dense_15", "dense_17", "dense_33", "tridiagonal_200", "band_100_20", "double_arrow_400"))}
+            rec = (self.least(("from_coo", "from_csr", "from_coo_device"), dtype), (), dict(out=self.new_t(), src=src, dtype=dtype, transpose=False))
+        return rec
+
+    def r_solve(self, dtype, tid=None, force=None):
+        ts = [i for i in ([tid] if tid is not None else self.of(dtype)) if self.solvable(self.m.t[i])]
+        if not ts:
+            return None
+        factors = [i for i in ts if self.m.t[i].prov is not None and self.m.t[i].prov[0] == "ilu0"]
+        op = self.least(("trsv", "trsv_info", "bfs", "bfs_parents") + (("lu_solve", "ilu0_info") if factors else ()), sm.dtname(self.m.t[ts[0]].dtype))
+        graphs = [i for i in ts if self.m.t[i].rows <= 700 and sm.symmetric(self.m.t[i])]
+        if force is None and graphs and self.chance(0.15):
+            op = "triangle_count"
+        if force is not None:
+            if (force in ("lu_solve", "ilu0_info") and not factors) or (force == "triangle_count" and not graphs):
+                return None
+            op = force
+        if op == "triangle_count":
+            return (op, (self.pick(graphs),), {})
+        if op in ("bfs", "bfs_parents"):
+            i = self.pick(ts)
+            return (op, (i,), dict(source=int(self.rng.integers(0, self.m.t[i].rows)), transpose=self.chance(0.5)))
+        if op == "trsv":
+            return self.solve_rec(self.pick(ts))
+        if op == "trsv_info":
+            return (op, (self.pick(ts),), dict(uplo=self.cycle("uplo", ("lower", "upper"))))
+        return (op, (self.pick(factors),), self.vals_args() if op == "lu_solve" else {})
+
+    def r_factor_read(self):
+        """lu_solve or ilu0_info on a live factor, the value type that saw fewer first"""
+        fs = [i for i, T in self.m.t.items() if T.prov is not None and T.prov[0] == "ilu0"]
+        if not fs:
+            return None
+        i = self.pick(fs, [1.0 / (1 + self.count.get(("lu_solve", sm.dtname(self.m.t[i].dtype)), 0)) ** 2 for i in fs])
+        op = self.least(("lu_solve", "ilu0_info"), sm.dtname(self.m.t[i].dtype))
+        return (op, (i,), self.vals_args() if op == "lu_solve" else {})
+
+    def r_fold(self, dtype, tid=None, column=None, arg=None, force=None):
+        """mxv_frontier, mxv_arg or reduce_arg (arg: None any, False the first, True one of the other two)"""
+        ts = [tid] if tid is not None else self.of(dtype, lambda T: T.nnz <= MAX_TRSV_NNZ)
+        if not ts:
+            return None
+        i = self.pick(ts)
+        op = self.least({None: ("mxv_frontier", "mxv_arg", "reduce_arg"), False: ("mxv_frontier",), True: ("mxv_arg", "reduce_arg")}[arg],
+                        sm.dtname(self.m.t[i].dtype))
+        op = force or op
+        tr = self.chance(0.5) if column is None else column
+        if op == "reduce_arg":
+            return (op, (i,), dict(op=self.cycle("arg_op", ("min", "max")), dim="cols" if tr else "rows"))
+        a = dict(transpose=tr, x_present=self.cycle("x_present", ("none", "sparse", "empty")), mask=self.cycle("mask", (None, "mask", "complement")),
+                 out_present=self.chance(0.5), accumulate=self.chance(0.4), **self.vals_args())
+        if op == "mxv_arg":
+            kind = self.cycle("arg_kind", argref.KINDS)
+            return (op, (i,), dict(a, kind=kind, x_none=kind in argref.INDEX_KINDS and self.chance(0.5)))
+        semiring = "plus_pair" if self.chance(0.15) else self.pick(SEMIRINGS)
+        return (op, (i,), dict(a, semiring=semiring, x_none=semiring == "plus_pair" and self.chance(0.6)))
+
+    def r_reader(self, dtype, tid=None, column=None):
+        if column is None and self.chance(0.7):
+            rec = self.r_solve(dtype, tid) if self.chance(0.65) else self.r_fold(dtype, tid)
+            if rec:
+                return rec
+        return super().r_reader(dtype, tid, column)
+
+    def r_read_hot(self, dtype):
+        """the solves count among the readers of the tiling written last"""
+        i = self.hot
+        if i in self.m.t and self.solvable(self.m.t[i]) and self.chance(0.1):
+            w = self.m.t[i].last_writer
+            how = self.least(("trsv_lower", "trsv_upper"), w)
+            self.count[(how, w)] = self.count.get((how, w), 0) + 1
+            return self.solve_rec(i, how[5:])
+        if i in self.m.t and self.m.t[i].nnz <= MAX_TRSV_NNZ and self.chance(0.1):
+            w = self.m.t[i].last_writer
+            how = self.least(("frontier_row", "frontier_col", "arg_row", "arg_col"), w)
+            self.count[(how, w)] = self.count.get((how, w), 0) + 1
+            return self.r_fold(dtype, i, how.endswith("col"), how.startswith("arg"))
+        return super().r_read_hot(dtype)
+
+    # ---- deliberate refusals -----------------------------------------------------------------------------------------------------
+    def r_refusal(self, dtype):
+        if self.chance(0.25):
+            return super().r_refusal(dtype)
+        m = self.m
+        derived = [i for i, T in m.t.items() if T.prov is not None and T.nnz > 0]
+        fresh = [i for i in m.t if self.refresh_rec(i)]
+        concats = [i for i in fresh if m.t[i].prov[0] == "concat"]
+        oblong = [i for i, T in m.t.items() if T.rows != T.cols]
+        holed = [i for i, T in m.t.items() if T.rows == T.cols and sm.missing_diag(T)[0] and T.nnz <= MAX_TRSV_NNZ]
+        opts = ["powi_thunk", "extract_empty_device"]
+        regions = [(c, x) for c, C in m.t.items() for x, A in m.t.items() if C.dtype == A.dtype and 2 <= A.rows <= min(C.rows, MAX_LIST)
+                   and A.cols <= C.cols and C.nnz + A.nnz <= MAX_C_NNZ // 2]
+        opts += ["assign_repeat_device"] if regions else []
+        built = [i for i, T in m.t.items() if T.prov is not None and T.prov[0] == "build" and T.nnz > 0]
+        opts += ["build_refresh_no_map"] if [i for i in built if not m.t[i].prov[1]["keep_map"]] else []
+        opts += ["build_refresh_wrong_nnz"] if [i for i in built if m.t[i].prov[1]["keep_map"]] else []
+        opts += ["wrong_kind_refresh"] if derived else []
+        opts += ["wrong_source_refresh"] if [i for i in fresh if m.t[i].prov[0] not in ("concat", "build")] and len(m.t) >= 3 else []
+        opts += ["concat_wrong_count"] if concats else []
+        opts += ["concat_swapped"] if [i for i in concats if len(set(m.t[i].prov[1])) > 1] else []
+        opts += ["trsv_nonsquare", "ilu0_nonsquare"] if oblong else []
+        opts += ["trsv_missing_diag", "ilu0_missing_diag"] if holed else []
+        opts += ["trsv_overlap"] if [i for i, T in m.t.items() if self.solvable(T) and T.rows >= 2] else []
+        why = self.least(opts, "refusal")
+        if why == "powi_thunk":
+            return ("apply", (self.pick(self.tilings()),), dict(out=self.new_t(), op="powi", thunk=float(self.pick((0, 65, -1, 2.5))), expect=why))
+        if why == "extract_empty_device":
+            i = self.pick(self.tilings())
+            T = m.t[i]
+            rows, cols = (["device", []], self.index_spec(T.cols)) if self.chance(0.5) else (self.index_spec(T.rows), ["device", []])
+            return ("extract", (i,), dict(out=self.new_t(), rows=rows, cols=cols, expect=why))
+        if why in ("build_refresh_no_map", "build_refresh_wrong_nnz"):
+            i = self.pick([i for i in built if m.t[i].prov[1]["keep_map"] == (why == "build_refresh_wrong_nnz")])
+            n = m.t[i].prov[2] + (0 if why == "build_refresh_no_map" else int(self.pick((-1, 1))))
+            return ("set_values_from_build", (i,), dict(self.vals_args(), nnz_in=n, expect=why))
+        if why == "assign_repeat_device":
+            c, x = self.pick(regions)
+            C, A = m.t[c], m.t[x]
+            rows = [int(r) for r in self.rng.permutation(C.rows)[:A.rows]]
+            rows[int(self.rng.integers(1, len(rows)))] = rows[0]
+            cols = None if A.cols == C.cols else ["slice", 0, A.cols, 1]
+            return ("assign", (c, x), dict(out=self.new_t(), rows=["device", rows], cols=cols, accum=None, expect=why))
+        if why == "wrong_kind_refresh":
+            i = self.pick(derived)
+            T = m.t[i]
+            kind = self.pick([k for k in ("apply", "transpose", "extract", "ilu0") if k != T.prov[0]])
+            alive = [s for s in sm.sources(T.prov) if s in m.t]
+            return ("set_values_from_" + kind, (i, alive[0] if alive else self.pick([j for j in m.t if j != i] or [i])), dict(expect=why))
+        if why == "wrong_source_refresh":
+            op, ids, _ = self.refresh_rec(self.pick([i for i in fresh if m.t[i].prov[0] not in ("concat", "build")]))
+            k = int(self.rng.integers(1, len(ids)))
+            other = [j for j in m.t if j != ids[k]]
+            ids = ids[:k] + (self.pick(other),) + ids[k + 1:]
+            return self.emit((op, ids, dict(_, expect=why)))
+        if why == "concat_wrong_count":
+            op, ids, _ = self.refresh_rec(self.pick(concats))
+            return (op, ids[:-1] if len(ids) > 2 and self.chance(0.5) else ids + (ids[-1],), dict(expect=why))
+        if why == "concat_swapped":
+            op, ids, _ = self.refresh_rec(self.pick([i for i in concats if len(set(m.t[i].prov[1])) > 1]))
+            x, y = self.pick([(x, y) for x in range(1, len(ids)) for y in range(x + 1, len(ids)) if ids[x] != ids[y]])
+            ids = list(ids)
+            ids[x], ids[y] = ids[y], ids[x]
+            return (op, tuple(ids), dict(expect=why))
+        if why in ("trsv_nonsquare", "trsv_missing_diag"):
+            i = self.pick(oblong if why == "trsv_nonsquare" else holed)
+            return ("trsv", (i,), dict(uplo=self.pick(("lower", "upper")), unit_diag=why == "trsv_nonsquare" and self.chance(0.5), in_place=self.chance(0.5),
+                                       expect=why, **self.vals_args()))
+        if why in ("ilu0_nonsquare", "ilu0_missing_diag"):
+            return ("ilu0", (self.pick(oblong if why == "ilu0_nonsquare" else holed),), dict(out=self.new_t(), expect=why))
+        rec = self.solve_rec(self.pick([i for i, T in m.t.items() if self.solvable(T) and T.rows >= 2]))
+        return (rec[0], rec[1], dict(rec[2], in_place=False, overlap=True, expect=why))
+
+    # ---- scenarios of the second set: a chain refreshed link by link, the life of a factor, a concat between refreshes ---------------------
+    def start_scenario2(self):
+        kinds = [k for k in ("chain", "life", "concat") if self.started.get(k, 0) < (2 if k == "chain" else 1)]
+        if not kinds or len(self.m.t) > self.MAX_T - 1:
+            return
+        # the life of a factor and the concat need one free place, the chain three; what this program has not run comes first
+        kind = "life" if "life" in kinds else self.pick(kinds)
+        if kind == "chain" and len(self.m.t) > self.MAX_T - 3:
+            return
+        small = lambda T: 0 < T.nnz <= 3000 and max(T.rows, T.cols) <= 700
+        if kind == "chain":
+            ts = self.tilings(lambda T: small(T) and self.factorable(T)) if self.chance(0.6) else []
+            ts = ts or self.tilings(small)
+            steps = ["link", "link", "link", "colread", "write", "refresh1", "refresh2", "refresh3", "read"]
+        elif kind == "life":
+            ts = self.tilings(lambda T: T.nnz > 0 and self.factorable(T))
+            steps = ["ilu0", "lu_solve", "write", "refresh1", "lu_solve"]
+        else:
+            ts = self.tilings(small)
+            steps = ["concat", "refresh1", "write", "refresh1", "ctx", "refresh1"]
+        if ts:
+            self.cast, self.script2, self.stalls = [self.pick(ts)], steps, 0
+            self.started[kind] = self.started.get(kind, 0) + 1
+
+    def r_script2(self, dtype):
+        if any(i not in self.m.t or self.m.t[i].nnz == 0 for i in self.cast) or self.stalls > 8:
+            self.script2, self.cast = [], []
+            return None
+        what = self.script2[0]
+        base, tip = self.cast[0], self.cast[-1]
+        dtype = sm.dtname(self.m.t[base].dtype)
+        if what in ("link", "ilu0", "concat"):
+            if len(self.m.t) >= self.MAX_T:
+                self.stalls += 1
+                return self.r_close(dtype)
+            if what == "link":
+                kinds = list(sm.KINDS2)
+                rec = None
+                while kinds and rec is None:
+                    k = self.least(kinds, "link")
+                    kinds.remove(k)
+                    rec = self.d_extract_all(tip) if k == "extract" else getattr(self, "d_" + k)(dtype, tip)
+                if rec is not None:
+                    self.count[(rec[0], "link")] = self.count.get((rec[0], "link"), 0) + 1
+            else:
+                rec = getattr(self, "d_" + what)(dtype, tip)
+            if rec is None:
+                self.script2, self.cast = [], []
+                return None
+            self.cast.append(rec[2]["out"])
+        elif what == "write":
+            rec = (self.pick(("set_values", "set_values_device")), (base,), dict(order=self.pick(("row", "col")), **self.vals_args()))
+        elif what.startswith("refresh"):
+            rec = self.emit(self.refresh_rec(self.cast[int(what[7:])]))
+        elif what == "ctx":
+            rec = ("trim", (), {}) if self.chance(0.5) else ("reserve", (), dict(bytes=int(self.pick(RESERVES))))
+        elif what == "lu_solve":
+            rec = ("lu_solve", (tip,), self.vals_args())
+        elif what == "colread":
+            rec = _Gen.r_reader(self, dtype, self.pick(self.cast[1:]), True)
+        else:
+            rec = _Gen.r_reader(self, dtype, tip)
+        if rec is None:
+            self.script2, self.cast = [], []
+            return None
+        self.script2 = self.script2[1:]
+        if not self.script2:
+            self.cast = []
+        return rec
+
+    def d_extract_all(self, i):
+        """a link of a chain: an extract that keeps every row and takes the columns as they are or by a slice"""
+        T = self.m.t[i]
+        return ("extract", (i,), dict(out=self.new_t(), rows=None, cols=None if self.chance(0.5) else ["slice", 0, T.cols, 1]))
+
+    def step(self):
+        super().step()
+        op, _, a = self.prog[-1]
+        if "expect" not in a and (op in sm.KINDS2 or (op.startswith("build") and a["keep_map"])) and self.chance(0.5):
+            self.young.append(a["out"])
+
+    def draw(self):
+        dtype = self.want_dtype()
+        if self.script and self.chance(0.5):
+            return self.r_script()
+        if self.script2 and self.chance(0.6):
+            return self.r_script2(dtype)
+        if self.owed is not None:
+            (k, d), self.owed = self.owed, None
+            rec = self.r_triangles(d) if k == "triangle_count" else getattr(self, "d_" + k)(d) if len(self.m.t) < self.MAX_T else None
+            if rec is not None:
+                return rec
+        if self.young and self.chance(0.3):
+            i = self.young.pop(0)
+            rec = self.emit(self.refresh_rec(i)) if i in self.m.t else None
+            if rec is not None:
+                return rec
+        if not self.script and self.scenarios < 1 and self.m.p and self.chance(0.15):
+            self.start_scenario()
+        if not self.script2 and len(self.m.t) >= 2 and self.chance(0.2):
+            self.start_scenario2()
+        if len(self.m.t) < 2:
+            return self.r_convert(dtype)
+        if self.refusals * 12 < len(self.prog) and self.chance(0.09):
+            return self.r_refusal(dtype)
+        if self.chance(0.08):
+            return self.r_chase(dtype)
+        if self.chance(0.03):
+            return self.r_factor_read()
+        if self.chance(0.1):                 # the first set's derivations, so that the new readers and refreshes meet their writers too
+            return _Gen.r_derive(self, dtype)
+        if self.hot is not None and self.chance(0.45):
+            return self.r_read_hot(dtype)
+        if self.chance(0.8):
+            return self.r_needy(dtype)
+        cat = self.pick(("convert", "plan_create", "plan_op", "writer", "derive", "reader", "ctx", "close", "plan_close", "export"),
+                        (1.0, 0.4, 1.0, 1.6, 5.0, 1.4, 0.5, 0.3, 0.2, 0.3))
+        return getattr(self, "r_" + cat)(dtype)
+
+
+def op_set(seed):
+    """the operation set a seed draws from: the second from SET2_FROM on"""
+    return 2 if int(seed) >= SET2_FROM else 1
+
+
 def context_kind(seed):
     """the context kind a committed seed runs on (any other seed: by its value)"""
+    if seed in SEEDS2:
+        return CONTEXT_KINDS[SEEDS2.index(seed) % 3]
     return CONTEXT_KINDS[(SEEDS.index(seed) if seed in SEEDS else int(seed)) % 3]
 
 
 def program(seed, steps):
-    g = _Gen(int(seed))
+    g = (_Gen2 if op_set(seed) == 2 else _Gen)(int(seed))
     while len(g.prog) < steps:
         g.step()
     return g.prog

@@ -4,34 +4,55 @@ them on the GPU next to this model; DESIGN.md, "Sequence test").
 Plain Python / numpy, no GPU import.  The model holds, per live handle, what include/pem_spgemm.h lets a caller observe:
 
   MTiled  rows, cols, dtype, the canonical CSR (rowptr, colidx, vals), a value version, and the provenance pem_internal.h's
-          Derivation keeps (none / plan + transpose / ewise operands + op + pattern + alpha + beta / select source + op + thunk)
+          Derivation keeps (none / plan + transpose / ewise operands + op + pattern + alpha + beta / select source + op + thunk;
+          of the second operation set: apply source + op + thunk / scale source + op / transpose source / extract source + lists /
+          assign C + A + lists + accum / kron operands + op / concat cells + grid + sizes / build triplet source + dup op + nnz_in /
+          ilu0 source), and which lazily built structures it holds (the refresh maps, the two trsv schedules)
   MPlan   its operands, mask + complement, tile-row range, semiring, options, state 0-3, C as CSR, and the operand versions and
           semiring under which step 3 last ran: "C is current" is computed from those, never assumed
 
 Model.apply(record) executes one record of a program.  It first evaluates the precondition the header documents and returns either
 the result or the documented status (PEM_E_STATE, PEM_E_INVALID); only refusals the header spells out are modelled.  It adds no
 arithmetic: every value comes from the reference the feature's own GPU test uses (oracle.csr_spgemm, semiringref, maskref,
-ewiseref, selectref, mxvref, spmmref, sddmmref); what is here is the reshaping between CSR and COO those references ask for.
+ewiseref, selectref, mxvref, spmmref, sddmmref; applyref, extractref, assignref, kronref, concatref, buildref, topkref,
+sampledref, frontierref, argref, trsvref, ilu0ref); what is here is the reshaping between CSR and COO those references ask for.
 
-`mutations` switches on one of three deliberate mistakes of the MODEL (negative controls of tests/test_gpu_seq.py; the library
+`mutations` switches on one of six deliberate mistakes of the MODEL (negative controls of tests/test_gpu_seq.py; the library
 is never touched): "no_bump" (a refresh leaves the value version alone), "stale_vals_t" (in-place writers leave the values the
-audit's vals_t readers use as they were), "no_option_reset" (set_option leaves the plan's state alone).
+audit's vals_t readers use as they were), "no_option_reset" (set_option leaves the plan's state alone), "concat_stale_block" (a
+concat's refresh takes the blocks' values as of its first refresh: a pointer table that is not rewritten), "ilu0_stale_source"
+(set_values_from_ilu0 factors the source's values as of the build), "trsv_stale_values" (a solve takes the values the tiling had
+when that triangle's schedule was built).
 """
 import numpy as np
 
+import applyref
+import argref
+import assignref
+import buildref
+import concatref
 import ewiseref
+import extractref
+import frontierref
+import ilu0ref
+import kronref
 import maskref
 import mxvref
+import sampledref
 import sddmmref
 import selectref
 import semiringref
 import spmmref
+import topkref
+import trsvref
 from matgen import cases
 
 PEM_OK, PEM_E_INVALID, PEM_E_STATE = 0, -1, -6
 MINMAX = ("min_plus", "max_plus", "max_times")
 SPECIAL = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 3.0e-310, 1.0e-40, 0.5, -0.5, 2.0])   # test_gpu_sddmm.py's mix
-MUTATIONS = ("no_bump", "stale_vals_t", "no_option_reset")
+MUTATIONS = ("no_bump", "stale_vals_t", "no_option_reset", "concat_stale_block", "ilu0_stale_source", "trsv_stale_values")
+# the derivation kinds of the second operation set (seqgen.py): each has a set_values_from_<kind>
+KINDS2 = ("apply", "scale", "transpose", "extract", "assign", "kron", "concat", "ilu0")
 
 # pem_cplan_set_option: the options the generator draws from, their defaults (pem_internal.h), whether the value is kept as an
 # integer (else as value != 0), and the step the plan falls back to (spgemm.hip: "the last step the option does not touch")
@@ -80,11 +101,47 @@ def rand_matrix(seed, rows, cols, nnz, clustered):
     return (keys[p] // cols).astype(np.int32), (keys[p] % cols).astype(np.int32), v[p]
 
 
+_SQUARE = {}
+
+
+def square_case(kind, name, side=0):
+    """a square matrix that stores its diagonal, from the triangular-solve tests' list (side 0: the lower case, 1: the upper) or
+    the ILU(0) tests'"""
+    if kind not in _SQUARE:
+        import ilu0cases
+        import trsvcases
+        _SQUARE[kind] = (trsvcases if kind == "trsv" else ilu0cases).cases()
+    c = _SQUARE[kind][name]
+    n, I, J, V = c[side] if kind == "trsv" else c
+    return n, n, np.asarray(I, np.int32), np.asarray(J, np.int32), np.asarray(V, np.float64)
+
+
+def rand_square(seed, n, nnz):
+    """rand_matrix's entries off the diagonal plus the whole diagonal, with trsvcases' dominant diagonal values"""
+    I, J, V = rand_matrix(seed, n, n, nnz, False)
+    off = I != J
+    I, J, V = I[off], J[off], V[off]
+    rng = np.random.default_rng(seed + 1)
+    s = np.zeros(n)
+    np.add.at(s, I, np.abs(V))
+    d = (s + 1.0 + rng.random(n)) * rng.choice([-1.0, 1.0], n)
+    k = np.arange(n, dtype=np.int32)
+    return np.concatenate([I, k]), np.concatenate([J, k]), np.concatenate([V, d])
+
+
 def matrix(src):
-    """(rows, cols, I, J, V) of a record's matrix source: {"case": name} or {"rand": [seed, rows, cols, nnz, clustered]}"""
+    """(rows, cols, I, J, V) of a record's matrix source: {"case": name}, {"rand": [seed, rows, cols, nnz, clustered]} or, square
+    with the diagonal stored, {"trsv": [name, side]}, {"ilu0": name}, {"randdiag": [seed, n, nnz]}"""
     if "case" in src:
         rows, cols, I, J, V, _ = case(src["case"])
         return rows, cols, I, J, V
+    if "trsv" in src:
+        return square_case("trsv", src["trsv"][0], src["trsv"][1])
+    if "ilu0" in src:
+        return square_case("ilu0", src["ilu0"])
+    if "randdiag" in src:
+        seed, n, nnz = src["randdiag"]
+        return (n, n) + rand_square(seed, n, nnz)
     seed, rows, cols, nnz, clustered = src["rand"]
     return (rows, cols) + rand_matrix(seed, rows, cols, nnz, bool(clustered))
 
@@ -133,6 +190,8 @@ class MTiled:
         self.prov = prov
         self.built = set()               # lazily built structures (coverage bookkeeping only)
         self.last_writer = None          # the last in-place writer kind (coverage bookkeeping only)
+        self.trail = []                  # of a concat or a factor: refreshes, writes to a source, trim / reserve (coverage only)
+        self.kept = {}                   # what a mutation of the second set holds on to (values as of some earlier call)
 
     @property
     def nnz(self):
@@ -183,6 +242,72 @@ def _kind(name):
     return "minmax" if name in MINMAX or name in ("min", "max") else "exact"
 
 
+def sources(prov):
+    """the ids of the tilings a provenance tuple names (a concat's cells: the non-null ones, repeats included)"""
+    if prov is None or prov[0] in ("cplan", "build"):
+        return ()
+    if prov[0] in ("ewise", "kron", "assign"):
+        return (prov[1], prov[2])
+    if prov[0] == "concat":
+        return tuple(h for h in prov[1] if h is not None)
+    return (prov[1],)
+
+
+def triplets(a, dtype):
+    """(rows, cols, I, J, V) of a build record's triplet list: the record's matrix with every entry repeated 1 to 5 times (mostly
+    once) and, under a["long"], a few of them as often as or more often than the build folds strictly in order"""
+    rows, cols, I, J, V = matrix(a["src"])
+    rng = np.random.default_rng(a["lens_seed"])
+    lengths = rng.choice(np.array([1, 1, 1, 2, 3, 5]), len(I))
+    if a["long"] and len(I):
+        lengths[rng.integers(0, len(I), 3)] = rng.choice(np.array([32, 33, 40]), 3)    # (BUILD_INORDER_MAX is 32)
+    I2, J2, V2 = buildref.with_duplicates(I, J, np.asarray(V, dtype), rng, lengths)
+    return rows, cols, I2, J2, V2
+
+
+def symmetric(T):
+    """a square tiling whose pattern equals its transpose's (what triangle_count takes)"""
+    if T.rows != T.cols:
+        return False
+    I, J, _ = T.coo()
+    return np.array_equal(np.sort(I * T.cols + J), np.sort(J * T.cols + I))
+
+
+def index_list(spec, dim):
+    """an index argument of extract as the records carry it: None (all), ["slice", start, stop, step], ["host", [..]] or
+    ["device", [..]] -> None or the int64 list"""
+    if spec is None:
+        return None
+    if spec[0] == "slice":
+        return np.arange(*slice(*spec[1:]).indices(dim), dtype=np.int64)
+    return np.asarray(spec[1], np.int64)
+
+
+def missing_diag(T):
+    """(rows without a stored diagonal entry, the first of them 1-based or 0) of a square tiling"""
+    I, J, _ = T.coo()
+    has = np.zeros(T.rows, bool)
+    has[I[I == J]] = True
+    miss = np.flatnonzero(~has)
+    return len(miss), int(miss[0]) + 1 if len(miss) else 0
+
+
+def ilu0_cost(T):
+    """steps of ilu0ref's inner loop on T (the generator's size guard)"""
+    return int((np.diff(T.rp) ** 2).sum())
+
+
+def trsv_fields(T, uplo):
+    """pem_tiled_trsv_info's levels, max_width, missing_diag, first_missing_row from trsvref.levels of the pattern"""
+    w = trsvref.widths(trsvref.levels(T.rows, T.rp, T.ci, uplo))
+    return np.array([len(w), max(w)] + list(missing_diag(T)), np.int64)
+
+
+def pivot_fields(T):
+    """pem_tiled_ilu0_info's zero_pivots and first_zero_pivot_row of a factor, by ilu0ref.pivots"""
+    return np.array(ilu0ref.pivots(T.rows, T.rp, T.ci, T.vals), np.int64)
+
+
 class Model:
     def __init__(self, mutations=()):
         assert all(m in MUTATIONS for m in mutations)
@@ -204,6 +329,9 @@ class Model:
         for p in self.p.values():
             if p.A is T or p.B is T:
                 p.trail.append("refresh")
+        for D in self.t.values():
+            if D.prov is not None and D.prov[0] in ("concat", "ilu0") and any(self.t.get(h) is T for h in sources(D.prov)):
+                D.trail.append("source")
 
     def adopt(self, tid, vals):
         """take the device's bits where the header leaves them open (the sign of a zero under min / max, NaN payloads)"""
@@ -492,11 +620,304 @@ class Model:
                               oracle=oracle(), transpose=a["transpose"])
         return Result(out=Y, kind=_kind(a["semiring"]))
 
+    # ---- the second operation set: derived tilings with a refresh --------------------------------------------------------------
+    def _made_from(self, T, kind, srcs):
+        """the serial rule of the set_values_from_* calls: T was made by `kind` from exactly these tilings, in this order"""
+        if T.prov is None or T.prov[0] != kind:
+            return False
+        return tuple(T.prov[1]) == tuple(srcs) if kind == "concat" else sources(T.prov) == tuple(srcs)
+
+    def _refreshed(self, ids, kind, V, result_kind="exact", built=None):
+        T = self.t[ids[0]]
+        if built:
+            T.built.add(built)
+        T.trail.append("refresh")
+        self._wrote(T, V, "from_" + kind)
+        return Result(wrote=ids[0], kind=result_kind)
+
+    def op_apply(self, ids, a):
+        A = self.t[ids[0]]
+        if a["op"] == "powi" and not applyref.powi_thunk_ok(a["thunk"]):
+            return Result(PEM_E_INVALID)
+        V = applyref.apply(A.vals, a["op"], a["thunk"], A.dtype)
+        r = self._new(a, MTiled(A.rows, A.cols, A.dtype, A.rp, A.ci, V, ("apply", ids[0], a["op"], a["thunk"])))
+        r.kind = _kind(a["op"])
+        return r
+
+    def op_set_values_from_apply(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "apply", ids[1:]):
+            return Result(PEM_E_INVALID)
+        return self._refreshed(ids, "apply", applyref.apply(self.t[ids[1]].vals, T.prov[2], T.prov[3], T.dtype), _kind(T.prov[2]))
+
+    def _scaled(self, A, a, op):
+        """a["rows"] / a["cols"]: the seed of that vector, or None"""
+        r, c = (None if a[k] is None else values(n, a[k], a["special"], A.dtype) for k, n in (("rows", A.rows), ("cols", A.cols)))
+        I, J, V = A.coo()
+        return applyref.scale(I, J, V, r, c, op, A.dtype)
+
+    def op_scale(self, ids, a):
+        A = self.t[ids[0]]
+        r = self._new(a, MTiled(A.rows, A.cols, A.dtype, A.rp, A.ci, self._scaled(A, a, a["op"]), ("scale", ids[0], a["op"])))
+        r.kind = _kind(a["op"])
+        return r
+
+    def op_set_values_from_scale(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "scale", ids[1:]):
+            return Result(PEM_E_INVALID)
+        return self._refreshed(ids, "scale", self._scaled(self.t[ids[1]], a, T.prov[2]), _kind(T.prov[2]))
+
+    def _assigned(self, C, A, rows, cols, accum, prov=None):
+        I, J, V = assignref.assign(C.rows, C.cols, C.coo(), A.coo(), index_list(rows, C.rows), index_list(cols, C.cols), accum)
+        return MTiled.from_coo(C.rows, C.cols, I, J, V, C.dtype, prov)
+
+    def op_assign(self, ids, a):
+        C, A = self.t[ids[0]], self.t[ids[1]]
+        for spec in (a["rows"], a["cols"]):
+            if spec is not None and spec[0] != "slice" and len(set(spec[1])) != len(spec[1]):
+                return Result(PEM_E_INVALID)
+        r = self._new(a, self._assigned(C, A, a["rows"], a["cols"], a["accum"], ("assign", ids[0], ids[1], a["rows"], a["cols"], a["accum"])))
+        r.kind = _kind(a["accum"])
+        return r
+
+    def op_set_values_from_assign(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "assign", ids[1:]):
+            return Result(PEM_E_INVALID)
+        V = self._assigned(self.t[ids[1]], self.t[ids[2]], *T.prov[3:]).vals
+        return self._refreshed(ids, "assign", V, _kind(T.prov[5]), "map_assign")
+
+    def op_build(self, ids, a):
+        dtype = dt(a["dtype"])
+        rows, cols, I, J, V = triplets(a, dtype)
+        oI, oJ, oV = buildref.fold(rows, cols, I, J, V, a["dup"], a["transpose"])
+        if a["transpose"]:
+            rows, cols = cols, rows
+        prov = ("build", {k: a[k] for k in ("src", "lens_seed", "long", "dup", "transpose", "keep_map")}, len(I))
+        r = self._new(a, MTiled.from_coo(rows, cols, oI, oJ, oV, dtype, prov))
+        r.kind = _kind(a["dup"])
+        return r
+
+    def op_build_device(self, ids, a):
+        return self.op_build(ids, a)
+
+    def op_set_values_from_build(self, ids, a):
+        T = self.t[ids[0]]
+        if T.prov is None or T.prov[0] != "build" or not T.prov[1]["keep_map"] or a["nnz_in"] != T.prov[2]:
+            return Result(PEM_E_INVALID)
+        b = T.prov[1]
+        rows, cols, I, J, _ = triplets(b, T.dtype)
+        _, _, V = buildref.fold(rows, cols, I, J, values(len(I), a["seed"], a["special"], T.dtype), b["dup"], b["transpose"])
+        return self._refreshed(ids, "build", V, _kind(b["dup"]), "map_build")
+
+    def _sampled(self, S, A, B, a, old=None):
+        if a["transpose_b"]:
+            B = self._transposed(B)
+        I, J, _ = S.coo()
+        return sampledref.sampled(I, J, (A.rp, A.ci, A.vals), (B.rp, B.ci, B.vals), A.cols, B.cols, a["semiring"], A.dtype, old, oracle())
+
+    def op_sampled_mxm(self, ids, a):
+        S, A, B = (self.t[h] for h in ids)
+        r = self._new(a, MTiled(S.rows, S.cols, A.dtype, S.rp, S.ci, self._sampled(S, A, B, a)))
+        r.kind = _kind(a["semiring"])
+        return r
+
+    def op_set_values_sampled_mxm(self, ids, a):
+        T, A, B = (self.t[h] for h in ids)
+        self._wrote(T, self._sampled(T, A, B, a, T.vals if a["accumulate"] else None), "sampled_acc" if a["accumulate"] else "sampled")
+        return Result(wrote=ids[0], kind=_kind(a["semiring"]))
+
+    def op_triangle_count(self, ids, a):
+        T = self.t[ids[0]]
+        I, J, _ = T.coo()
+        off = I != J                             # (the diagonal is not read)
+        return Result(out=np.array([sampledref.triangles(T.rows, I[off], J[off])], np.int64))
+
+    def op_select_topk(self, ids, a):
+        A = self.t[ids[0]]
+        if a["dim"] == "cols":
+            A.built.add("mx_cols")
+        I, J, V = topkref.select_topk(*A.coo(), a["order"], a["dim"], a["k"], A.dtype)
+        return self._new(a, MTiled.from_coo(A.rows, A.cols, I, J, V, A.dtype))
+
+    def _transposed(self, A, prov=None):
+        rows, cols, I, J, V = extractref.transpose(A.rows, A.cols, *A.coo())
+        return MTiled.from_coo(rows, cols, I, J, V, A.dtype, prov)
+
+    def op_transpose(self, ids, a):
+        return self._new(a, self._transposed(self.t[ids[0]], ("transpose", ids[0])))
+
+    def op_set_values_from_transpose(self, ids, a):
+        if not self._made_from(self.t[ids[0]], "transpose", ids[1:]):
+            return Result(PEM_E_INVALID)
+        return self._refreshed(ids, "transpose", self._transposed(self.t[ids[1]]).vals, built="map_transpose")
+
+    def _extracted(self, A, rows, cols, prov=None):
+        ni, nj, I, J, V = extractref.extract(A.rows, A.cols, *A.coo(), index_list(rows, A.rows), index_list(cols, A.cols))
+        return MTiled.from_coo(ni, nj, I, J, V, A.dtype, prov)
+
+    def op_extract(self, ids, a):
+        for spec in (a["rows"], a["cols"]):
+            if spec is not None and spec[0] != "slice" and len(spec[1]) == 0:
+                return Result(PEM_E_INVALID)
+        return self._new(a, self._extracted(self.t[ids[0]], a["rows"], a["cols"], ("extract", ids[0], a["rows"], a["cols"])))
+
+    def op_set_values_from_extract(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "extract", ids[1:]):
+            return Result(PEM_E_INVALID)
+        return self._refreshed(ids, "extract", self._extracted(self.t[ids[1]], T.prov[2], T.prov[3]).vals, built="map_extract")
+
+    def _kron(self, A, B, op, prov=None):
+        rows, cols, I, J, V = kronref.kron(A.rows, A.cols, *A.coo(), B.rows, B.cols, *B.coo(), op, A.dtype)
+        return MTiled.from_coo(rows, cols, I, J, V, A.dtype, prov)
+
+    def op_kron(self, ids, a):
+        r = self._new(a, self._kron(self.t[ids[0]], self.t[ids[1]], a["op"], ("kron", ids[0], ids[1], a["op"])))
+        r.kind = _kind(a["op"])
+        return r
+
+    def op_set_values_from_kron(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "kron", ids[1:]):
+            return Result(PEM_E_INVALID)
+        return self._refreshed(ids, "kron", self._kron(self.t[ids[1]], self.t[ids[2]], T.prov[3]).vals, _kind(T.prov[3]), "map_kron")
+
+    @staticmethod
+    def _grid(flat, gc):
+        return [list(flat[k:k + gc]) for k in range(0, len(flat), gc)]
+
+    def op_concat(self, ids, a):
+        gr, gc = a["grid"]
+        blocks = self._grid([None if h is None else self.t[h].coo() for h in ids], gc)
+        rows, cols, I, J, V = concatref.concat(blocks, a["row_sizes"], a["col_sizes"], dt(a["dtype"]))
+        prov = ("concat", tuple(ids), gc, tuple(a["row_sizes"]), tuple(a["col_sizes"]))
+        return self._new(a, MTiled.from_coo(rows, cols, I, J, V, dt(a["dtype"]), prov))
+
+    def op_set_values_from_concat(self, ids, a):
+        T = self.t[ids[0]]
+        if not self._made_from(T, "concat", ids[1:]):
+            return Result(PEM_E_INVALID)
+        cells = [None if h is None else self.t[h] for h in T.prov[1]]
+        values = [None if c is None else c.vals for c in cells]
+        if "concat_stale_block" in self.mut:     # (the blocks' values as of the first refresh: a pointer table never rewritten)
+            values = T.kept.setdefault("blocks", values)
+        blocks = self._grid([None if c is None else c.coo() for c in cells], T.prov[2])
+        return self._refreshed(ids, "concat", concatref.refreshed(blocks, T.prov[3], T.prov[4], values, T.dtype), built="map_concat")
+
+    def op_ilu0(self, ids, a):
+        A = self.t[ids[0]]
+        if A.rows != A.cols or missing_diag(A)[0]:
+            return Result(PEM_E_INVALID)
+        V, _ = ilu0ref.ilu0(A.rows, A.rp, A.ci, A.vals, A.dtype)
+        F = MTiled(A.rows, A.cols, A.dtype, A.rp, A.ci, V, ("ilu0", ids[0]))
+        F.kept["source"] = A.vals
+        F.trail.append("ilu0")
+        self._schedule(F, "lower")               # (a factor is born with its lower schedule)
+        return self._new(a, F)
+
+    def op_set_values_from_ilu0(self, ids, a):
+        F = self.t[ids[0]]
+        if not self._made_from(F, "ilu0", ids[1:]):
+            return Result(PEM_E_INVALID)
+        A = self.t[ids[1]]
+        src = F.kept["source"] if "ilu0_stale_source" in self.mut else A.vals
+        return self._refreshed(ids, "ilu0", ilu0ref.ilu0(A.rows, A.rp, A.ci, src, A.dtype)[0])
+
+    # ---- the second operation set: readers ---------------------------------------------------------------------------------------
+    def _schedule(self, T, uplo):
+        if "trsv_" + uplo not in T.built:
+            T.built.add("trsv_" + uplo)
+            T.kept[uplo] = T.vals
+
+    def _trsv(self, T, b, uplo, unit_diag):
+        self._schedule(T, uplo)
+        vals = T.kept[uplo] if "trsv_stale_values" in self.mut else T.vals
+        return trsvref.trsv(T.rows, T.rp, T.ci, vals, b, uplo, unit_diag, T.dtype)
+
+    def op_trsv(self, ids, a):
+        T = self.t[ids[0]]
+        if T.rows != T.cols or a.get("overlap") or (not a["unit_diag"] and missing_diag(T)[0]):
+            return Result(PEM_E_INVALID)
+        return Result(out=self._trsv(T, values(T.rows, a["seed"], a["special"], T.dtype), a["uplo"], a["unit_diag"]))
+
+    def op_lu_solve(self, ids, a):
+        F = self.t[ids[0]]
+        F.trail.append("lu_solve")
+        work = self._trsv(F, values(F.rows, a["seed"], a["special"], F.dtype), "lower", True)
+        return Result(out=self._trsv(F, work, "upper", False))
+
+    def op_trsv_info(self, ids, a):
+        T = self.t[ids[0]]
+        self._schedule(T, a["uplo"])
+        return Result(out=trsv_fields(T, a["uplo"]))
+
+    def op_ilu0_info(self, ids, a):
+        return Result(out=pivot_fields(self.t[ids[0]]))
+
+    def frontier_operands(self, T, a):
+        """x, the old out, the old index vector, x_present and mask of a frontier or arg record (None where the record has none):
+        the absent x positions hold the special mix whatever the record says, the presence bytes are 0 / 1 / 255"""
+        nx, ny = (T.rows, T.cols) if a["transpose"] else (T.cols, T.rows)
+        rng = np.random.default_rng(a["seed"] + 2)
+        present = {"none": None, "sparse": (rng.random(nx) < 0.3) * rng.choice(np.array([1, 255], np.uint8), nx),
+                   "empty": np.zeros(nx, np.uint8)}[a["x_present"]]
+        mask = None if a["mask"] is None else ((rng.random(ny) < 0.5) * rng.choice(np.array([1, 255], np.uint8), ny)).astype(np.uint8)
+        x = None if a.get("x_none") else values(nx, a["seed"], a["special"], T.dtype)
+        if x is not None and present is not None:
+            x = np.where(present != 0, x, values(nx, a["seed"] + 3, True, T.dtype))
+        idx0 = rng.integers(-1, max(nx, 1), ny).astype(np.int32)
+        return x, values(ny, a["seed"] + 1, a["special"], T.dtype), idx0, None if present is None else present.astype(np.uint8), mask
+
+    def op_mxv_frontier(self, ids, a):
+        T = self.t[ids[0]]
+        x, y0, _, present, mask = self.frontier_operands(T, a)
+        if a["transpose"]:
+            T.built.add("mx_cols")
+        y, pres = frontierref.mxv_frontier(T.rows, T.cols, T.rp, T.ci, T.vals, x, a["semiring"], T.dtype, present, mask, a["mask"] == "complement",
+                                           y_old=y0, accumulate=a["accumulate"], oracle=oracle(), transpose=a["transpose"])
+        return Result(out=(np.asarray(y, T.dtype), pres) if a["out_present"] else np.asarray(y, T.dtype), kind=_kind(a["semiring"]))
+
+    def op_mxv_arg(self, ids, a):
+        T = self.t[ids[0]]
+        x, y0, idx0, present, mask = self.frontier_operands(T, a)
+        if a["transpose"]:
+            T.built.add("mx_cols")
+        y, idx, pres = argref.mxv_arg(T.rows, T.cols, T.rp, T.ci, T.vals, x, a["kind"], T.dtype, present, mask, a["mask"] == "complement",
+                                      y_old=y0, idx_old=idx0, accumulate=a["accumulate"], transpose=a["transpose"])
+        out = (() if y is None else (np.asarray(y, T.dtype),)) + (idx,) + ((pres,) if a["out_present"] else ())
+        return Result(out=out, kind="minmax")
+
+    def op_reduce_arg(self, ids, a):
+        T = self.t[ids[0]]
+        if a["dim"] == "cols":
+            T.built.add("mx_cols")
+        y, idx = argref.reduce_arg(T.rows, T.cols, T.rp, T.ci, T.vals, a["op"], T.dtype, a["dim"])
+        return Result(out=(np.asarray(y, T.dtype), idx), kind="minmax")
+
+    def op_bfs(self, ids, a):
+        T = self.t[ids[0]]
+        levels, depth, reached = frontierref.bfs(T.rows, T.rp, T.ci, a["source"], a["transpose"])
+        return Result(out=(levels, np.array([depth, reached], np.int64)))
+
+    def op_bfs_parents(self, ids, a):
+        T = self.t[ids[0]]
+        levels, parents, depth, reached = argref.bfs_parents(T.rows, T.rp, T.ci, a["source"], a["transpose"])
+        return Result(out=(levels, parents, np.array([depth, reached], np.int64)))
+
     # housekeeping: nothing a caller can observe changes
+    def _ctx_event(self):
+        for T in self.t.values():
+            if T.prov is not None and T.prov[0] == "concat":
+                T.trail.append("ctx")
+
     def op_trim(self, ids, a):
+        self._ctx_event()
         return Result()
 
     def op_reserve(self, ids, a):
+        self._ctx_event()
         return Result()
 
     def op_synchronize(self, ids, a):

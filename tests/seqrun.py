@@ -18,6 +18,7 @@ text form tools/seq_replay.py reads.  A HIP error status (PEM_E_HIP) raises SeqG
 import numpy as np
 import torch
 
+import argref
 import seqgen as sg
 import seqmodel as sm
 from semiringref import coo_to_csr
@@ -28,6 +29,8 @@ PEM_E_HIP = -5
 INFO = ("rows", "cols", "nnz", "tile_rows", "tile_cols", "ntiles", "value_bytes")
 ARRAYS = ("tile_keys", "tile_nnz_ptr", "masks", "rowptr", "rowcolidx", "vals", "masks_t", "tile_rowptr", "tile_colidx", "tile_colptr",
           "tile_rowidx", "tile_offsets")
+TRSV_FIELDS = ("levels", "max_width", "missing_diag", "first_missing_row")       # of pem_tiled_trsv_info; sm.trsv_fields' order
+PIVOT_FIELDS = ("zero_pivots", "first_zero_pivot_row")                           # of pem_tiled_ilu0_info; sm.pivot_fields' order
 SYMBOLIC = ("c_tile_rowptr", "c_tile_colidx", "c_mask", "c_tile_nnz_ptr")
 
 
@@ -136,7 +139,8 @@ class Runner:
 
     def audit_tiling(self, tid, where):
         """every info field and every pem_tiled_array against a from_csr rebuild from the model, and vals_t through both of its
-        readers: as the B operand of a small dense-row plan, and mxv(transpose=True)"""
+        readers: as the B operand of a small dense-row plan, and mxv(transpose=True); trsv_info of every triangle whose schedule the
+        model has as built, and ilu0_info of a factor"""
         T, M = self.t[tid], self.m.t[tid]
         self.check_tiling(tid, "exact", where)
         W = self._rebuild(M, M.vals)
@@ -165,6 +169,16 @@ class Runner:
             yt, wt = self.host(T.mxv(xv, transpose=True)), self.host(Wt.mxv(xv, transpose=True))
             if not same(yt, wt):
                 self.fail(f"{tid}: vals_t under the column walk (mxv transpose) differs from a rebuild of the model", where)
+            for uplo in ("lower", "upper"):      # only the triangles the model has as built: trsv_info would build the other
+                if "trsv_" + uplo in M.built:
+                    got, want = self._fields(T.trsv_info(uplo), TRSV_FIELDS), sm.trsv_fields(M, uplo)
+                    if not np.array_equal(got, want):
+                        self.fail(f"{tid}: trsv_info({uplo}) {dict(zip(TRSV_FIELDS, got.tolist()))}, trsvref's levels of the model's pattern "
+                                  f"give {want.tolist()}", where)
+            if M.prov is not None and M.prov[0] == "ilu0":
+                got, want = self._fields(T.ilu0_info(), PIVOT_FIELDS), sm.pivot_fields(M)
+                if not np.array_equal(got, want):
+                    self.fail(f"{tid}: ilu0_info {dict(zip(PIVOT_FIELDS, got.tolist()))}, the model's factor gives {want.tolist()}", where)
         finally:
             if Wt is not W:
                 Wt.close()
@@ -342,6 +356,171 @@ class Runner:
         self.uploaded()
         self.t[ids[0]].spmm(X[:, 1:1 + k], a["semiring"], a["transpose"], out=Y[:, :k], accumulate=a["accumulate"])
         return self.host(Y)
+
+    # ---- the second operation set --------------------------------------------------------------------------------------------------
+    def g_apply(self, ids, a):
+        self.t[a["out"]] = self.t[ids[0]].apply(a["op"], a["thunk"])
+
+    def g_set_values_from_apply(self, ids, a):
+        self.t[ids[0]].set_values_from_apply(self.t[ids[1]])
+
+    def g_transpose(self, ids, a):
+        self.t[a["out"]] = self.t[ids[0]].transpose()
+
+    def g_set_values_from_transpose(self, ids, a):
+        self.t[ids[0]].set_values_from_transpose(self.t[ids[1]])
+
+    def _index_arg(self, spec):
+        """an index list of a record as extract takes it: None, a slice, a host array or a device tensor"""
+        if spec is None:
+            return None
+        if spec[0] == "slice":
+            return slice(*spec[1:])
+        L = np.asarray(spec[1], np.int32)
+        return self.dev(L) if spec[0] == "device" else L
+
+    def g_extract(self, ids, a):
+        rows, cols = self._index_arg(a["rows"]), self._index_arg(a["cols"])
+        self.uploaded()
+        self.t[a["out"]] = self.t[ids[0]].extract(rows, cols)
+
+    def g_set_values_from_extract(self, ids, a):
+        self.t[ids[0]].set_values_from_extract(self.t[ids[1]])
+
+    def g_kron(self, ids, a):
+        self.t[a["out"]] = self.pkg.Tiled.kron(self.t[ids[0]], self.t[ids[1]], a["op"])
+
+    def g_set_values_from_kron(self, ids, a):
+        self.t[ids[0]].set_values_from_kron(self.t[ids[1]], self.t[ids[2]])
+
+    def g_concat(self, ids, a):
+        cells = [None if h is None else self.t[h] for h in ids]
+        gc = a["grid"][1]
+        self.t[a["out"]] = self.pkg.Tiled.concat([cells[k:k + gc] for k in range(0, len(cells), gc)], a["row_sizes"], a["col_sizes"])
+
+    def g_set_values_from_concat(self, ids, a):
+        self.t[ids[0]].set_values_from_concat([[None if h is None else self.t[h] for h in ids[1:]]])
+
+    def g_ilu0(self, ids, a):
+        self.t[a["out"]] = self.t[ids[0]].ilu0()
+
+    def g_set_values_from_ilu0(self, ids, a):
+        self.t[ids[0]].set_values_from_ilu0(self.t[ids[1]])
+
+    def g_trsv(self, ids, a):
+        M = self.m.t[ids[0]]
+        b = sm.values(M.rows, a["seed"], a["special"], M.dtype)
+        if a.get("overlap"):             # b and out one element apart in one buffer
+            buf = self.dev(np.concatenate([b, b[:1]]))
+            db, out = buf[:M.rows], buf[1:]
+        else:
+            db = self.dev(b)
+            out = db if a["in_place"] else self.dev(sm.values(M.rows, a["seed"] + 1, True, M.dtype))
+        self.uploaded()
+        return self.host(self.t[ids[0]].trsv(db, a["uplo"], a["unit_diag"], out=out))
+
+    def g_lu_solve(self, ids, a):
+        M = self.m.t[ids[0]]
+        db = self.dev(sm.values(M.rows, a["seed"], a["special"], M.dtype))
+        self.uploaded()
+        return self.host(self.t[ids[0]].lu_solve(db))
+
+    def _scale_vectors(self, M, a):
+        r, c = (None if a[k] is None else self.dev(sm.values(n, a[k], a["special"], M.dtype)) for k, n in (("rows", M.rows), ("cols", M.cols)))
+        self.uploaded()
+        return r, c
+
+    def g_scale(self, ids, a):
+        r, c = self._scale_vectors(self.m.t[ids[0]], a)
+        self.t[a["out"]] = self.t[ids[0]].scale(r, c, a["op"])
+
+    def g_set_values_from_scale(self, ids, a):
+        r, c = self._scale_vectors(self.m.t[ids[0]], a)      # (a scale keeps the shape: the vectors fit whatever source is named)
+        self.t[ids[0]].set_values_from_scale(self.t[ids[1]], r, c)
+
+    def g_assign(self, ids, a):
+        rows, cols = self._index_arg(a["rows"]), self._index_arg(a["cols"])
+        self.uploaded()
+        self.t[a["out"]] = self.t[ids[0]].assign(self.t[ids[1]], rows, cols, a["accum"])
+
+    def g_set_values_from_assign(self, ids, a):
+        self.t[ids[0]].set_values_from_assign(self.t[ids[1]], self.t[ids[2]])
+
+    def g_build(self, ids, a):
+        dtype = sm.dt(a["dtype"])
+        rows, cols, I, J, V = sm.triplets(a, dtype)
+        self.t[a["out"]] = self.pkg.Tiled.build(self.ctx, rows, cols, I, J, V, a["dup"], a["transpose"], dtype=dtype, keep_map=a["keep_map"])
+
+    def g_build_device(self, ids, a):
+        dtype = sm.dt(a["dtype"])
+        rows, cols, I, J, V = sm.triplets(a, dtype)
+        dI, dJ, dV = self.dev(np.asarray(I, np.int32)), self.dev(np.asarray(J, np.int32)), self.dev(V)
+        self.uploaded()
+        self.t[a["out"]] = self.pkg.Tiled.build_device(self.ctx, rows, cols, len(I), dI.data_ptr(), dJ.data_ptr(), dV.data_ptr(), a["dup"],
+                                                       a["transpose"], dtype=dtype, keep_map=a["keep_map"])
+
+    def g_set_values_from_build(self, ids, a):
+        dV = self.dev(sm.values(a["nnz_in"], a["seed"], a["special"], self.m.t[ids[0]].dtype))
+        self.uploaded()
+        self.t[ids[0]].set_values_from_build(dV)
+
+    def g_sampled_mxm(self, ids, a):
+        self.t[a["out"]] = self.t[ids[0]].sampled_mxm(self.t[ids[1]], self.t[ids[2]], a["semiring"], a["transpose_b"])
+
+    def g_set_values_sampled_mxm(self, ids, a):
+        self.t[ids[0]].set_values_sampled_mxm(self.t[ids[1]], self.t[ids[2]], a["semiring"], a["transpose_b"], a["accumulate"])
+
+    def g_triangle_count(self, ids, a):
+        return np.array([self.pkg.triangle_count(self.t[ids[0]])], np.int64)
+
+    def g_select_topk(self, ids, a):
+        self.t[a["out"]] = self.t[ids[0]].select_topk(a["k"], a["order"], a["dim"])
+
+    def _frontier_dev(self, M, a, index=False):
+        """the operands of a frontier or arg record on the device; every output vector is uploaded, so that what a call must not
+        write still holds what was uploaded"""
+        x, y0, idx0, present, mask = self.m.frontier_operands(M, a)
+        ny = len(y0)
+        d = dict(x=None if x is None else self.dev(x), y=self.dev(y0), idx=self.dev(idx0) if index else None,
+                 present=None if present is None else self.dev(present), mask=None if mask is None else self.dev(mask),
+                 out_present=self.dev(np.full(ny, 7, np.uint8)) if a["out_present"] else None)
+        self.uploaded()
+        return d
+
+    def g_mxv_frontier(self, ids, a):
+        d = self._frontier_dev(self.m.t[ids[0]], a)
+        y = self.t[ids[0]].mxv_frontier(d["x"], d["present"], d["mask"], a["mask"] == "complement", a["semiring"], a["transpose"], out=d["y"],
+                                        accumulate=a["accumulate"], out_present=d["out_present"])
+        return (self.host(y), self.host(d["out_present"])) if a["out_present"] else self.host(y)
+
+    def g_mxv_arg(self, ids, a):
+        d = self._frontier_dev(self.m.t[ids[0]], a, index=True)
+        values = a["kind"] in argref.VALUE_KINDS
+        y, idx = self.t[ids[0]].mxv_arg(d["x"], a["kind"], a["transpose"], d["present"], d["mask"], a["mask"] == "complement",
+                                        out=d["y"] if values else None, out_index=d["idx"], out_present=d["out_present"], accumulate=a["accumulate"])
+        return ((self.host(y),) if values else ()) + (self.host(idx),) + ((self.host(d["out_present"]),) if a["out_present"] else ())
+
+    def g_reduce_arg(self, ids, a):
+        y, idx = self.t[ids[0]].reduce_arg(a["op"], a["dim"])
+        return self.host(y), self.host(idx)
+
+    def g_bfs(self, ids, a):
+        levels, depth, reached = self.t[ids[0]].bfs(a["source"], a["transpose"])
+        return self.host(levels), np.array([depth, reached], np.int64)
+
+    def g_bfs_parents(self, ids, a):
+        levels, parents, depth, reached = self.t[ids[0]].bfs_parents(a["source"], a["transpose"])
+        return self.host(levels), self.host(parents), np.array([depth, reached], np.int64)
+
+    @staticmethod
+    def _fields(info, names):
+        return np.array([info[k] for k in names], np.int64)
+
+    def g_trsv_info(self, ids, a):
+        return self._fields(self.t[ids[0]].trsv_info(a["uplo"]), TRSV_FIELDS)
+
+    def g_ilu0_info(self, ids, a):
+        return self._fields(self.t[ids[0]].ilu0_info(), PIVOT_FIELDS)
 
     def g_trim(self, ids, a):
         self.ctx.trim()

@@ -8,25 +8,35 @@ auditing every live handle every 10 steps.  Every comparison is bit for bit over
 only); the model computes nothing itself: every value comes from the references of the feature tests (the oracle, semiringref,
 maskref, ewiseref, selectref, mxvref, spmmref, sddmmref).
 
-The seed list runs on three kinds of context, eight seeds each: the session context, one on a non-default torch stream (torch
+Two seed lists: seqgen.SEEDS draws from the operation set the test was added with (its programs are pinned by digest in
+tests/test_seq_cpu.py), seqgen.SEEDS2 from the second set, which adds apply, scale, transpose, extract, assign, kron, concat, build
+and ilu0 with their refreshes, select_topk, sampled_mxm and its in-place writer, the frontier and arg folds, bfs, bfs_parents,
+triangle_count, trsv, lu_solve, trsv_info and ilu0_info (references: applyref, extractref, assignref, kronref, concatref, buildref,
+topkref, sampledref, frontierref, argref, trsvref, ilu0ref).  The audit also
+compares trsv_info of every triangle whose schedule the model has as built, and a factor's ilu0_info.
+
+Each seed list runs on three kinds of context, eight seeds each: the session context, one on a non-default torch stream (torch
 tensors and library calls with no synchronisation between them), and one with graph replay on.
 
 PEM_SEQ_SEED (and PEM_SEQ_STEPS, default seqgen.STEPS) in the environment make this file run that one program instead of the
-committed list; tools/seq_replay.py replays a program from the text a failure prints.
+committed lists (a seed from seqgen.SET2_FROM on draws from the second set); tools/seq_replay.py replays a program from the text a failure prints.
 
-Negative controls: three deliberate mistakes of the MODEL (seqmodel.MUTATIONS; the library is never touched, nothing can fault)
+Negative controls: six deliberate mistakes of the MODEL (seqmodel.MUTATIONS; the library is never touched, nothing can fault)
 must each make the runner report a mismatch, at the step tests/seqcontrol.py computes from the models alone.
 
 Left out, and why: the multi-GPU entry points (pem_mgpu_*, their own contexts and ranks: test_gpu_multirank.py); matgen's
 million-row cases (k64_bins, wide_tilecols, xl_mixed_AAt, hub_tile_2100_AAt, blockrows_10000: the numpy references take seconds
-per call there); the CLI; the export_*_device forms, flop_count and the tile-row split helpers (read-only, no kept state);
+per call there); duplicate runs longer than BUILD_INORDER_MAX under plus / times and set_values_sampled_mxm with accumulate under
+plus_pair (the header lets both round differently from the references); refusals of trsv_info / ilu0_info; the CLI and its
+stages; the export_*_device forms, flop_count and the tile-row split helpers (read-only, no kept state);
 pem_cplan_info's ntiles_c / npairs (they depend on the options; prune_ref checks them in test_gpu_sweep.py); PEM_OPT_S1_XLCAP,
 S1_SERIAL, STEP1_GLOBAL_SORT, WARM, EXPORT_ROWS and S3_POISON of the options; writers on a tiling without entries and the
 destruction of a tiling another live handle names (the header leaves both outcomes open); kernel profiling.
 
-Wall time, measured on one MI355X in one session: this file (24 programs x 120 steps and the three negative controls) 8.1 s,
-tests/test_gpu_sddmm.py (the yardstick the list is sized against) 17.5 s; a single seed in a process of its own about 3 s, most of
-it start-up.  The CPU-only model run of the committed list takes about 2 s (tests/test_seq_cpu.py).
+Wall time, measured on one MI355X in one session: this file (48 programs x 120 steps and the six negative controls) 15.8 s,
+tests/test_gpu_sddmm.py (the yardstick the lists are sized against) 16.8 s; with the first list alone it was 8.1 s against 17.5 s.
+A single seed in a process of its own takes about 3 s, most of it start-up.  The CPU-only model runs of the committed lists take
+about 10 s together (tests/test_seq_cpu.py).
 """
 import os
 
@@ -45,7 +55,7 @@ if os.environ.get("PEM_SEQ_SEED"):
     SEEDS = (int(os.environ["PEM_SEQ_SEED"]),)
     STEPS = int(os.environ.get("PEM_SEQ_STEPS") or sg.STEPS)
 else:
-    SEEDS, STEPS = sg.SEEDS, sg.STEPS
+    SEEDS, STEPS = sg.SEEDS + sg.SEEDS2, sg.STEPS
 
 
 class _Contexts:

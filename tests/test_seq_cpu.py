@@ -7,15 +7,22 @@
   - the coverage conditions the committed seed list must meet (test_coverage_conditions).  They are conditions, not measurements:
     if a change to the generator misses one, change the weights or add seeds.
 
+The programs of the second operation set (sg.SEEDS2) have their own walk, table and conditions (test_second_set_coverage_conditions),
+and the first set's programs are pinned by their digests.
+
 One condition is read narrower than it could be: each derivation map (C^T's, ewise's, select's) can only be built by its own
 set_values_from_* entry point, so "first built by two different operation kinds" cannot hold for it; asserted instead is that each
 is built at least twice and at least once on a tiling that already holds another lazily built structure.
 """
 import collections
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
 
+import concatref
 import seqgen as sg
 import seqmodel as sm
 
@@ -166,6 +173,210 @@ def test_coverage_conditions():
     # refusals
     assert sum(cov["refusals"].values()) * 10 <= cov["steps"]
     for k in sg.REFUSALS:
+        assert cov["refusals"][k] >= 3, f"refusal {k}: {cov['refusals'][k]} times"
+
+
+# ---- the second operation set (sg.SEEDS2) ---------------------------------------------------------------------------------------
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seq_program_digests.json")
+WRITERS2 = tuple("from_" + k for k in sm.KINDS2) + ("from_build", "sampled", "sampled_acc")
+READERS2 = ("sampled_operand", "frontier_row", "frontier_col", "arg_row", "arg_col", "trsv_lower", "trsv_upper")
+MAPS2 = ("map_transpose", "map_extract", "map_assign", "map_kron", "map_concat", "map_build")
+SCHEDULES = ("trsv_lower", "trsv_upper")
+LIFE = ("ilu0", "lu_solve", "source", "refresh", "lu_solve")
+CONCAT_LIFE = ("refresh", "source", "refresh", "ctx", "refresh")
+
+
+def test_the_first_sets_programs_are_those_of_the_commit_that_added_them():
+    """SHA-256 of the text form of every program of SEEDS, recorded before the second set was added"""
+    want = json.load(open(DIGESTS))
+    assert sorted(want) == sorted(str(s) for s in sg.SEEDS)
+    for seed in sg.SEEDS:
+        assert hashlib.sha256(sg.dumps(_program(seed)).encode()).hexdigest() == want[str(seed)], f"seed {seed}: the program changed"
+
+
+def _downstream(m, tid):
+    """the tilings derived from tid, transitively"""
+    out, grew = {tid}, True
+    while grew:
+        grew = False
+        for j, D in m.t.items():
+            if j not in out and any(s in out for s in sm.sources(D.prov)):
+                out.add(j)
+                grew = True
+    return out - {tid}
+
+
+def _same_tiling(a, b):
+    return (a.rows, a.cols) == (b.rows, b.cols) and np.array_equal(a.rp, b.rp) and np.array_equal(a.ci, b.ci) and sm.same(a.vals, b.vals)
+
+
+def _check_glue(m, rec, label):
+    """the model's reshaping by a second route: a transpose transposed again is its source, a concat split again gives its blocks"""
+    op, ids, a = rec
+    R = m.t[a["out"]]
+    if op == "transpose":
+        assert _same_tiling(m._transposed(R), m.t[ids[0]]), f"{label}: transpose twice"
+    else:
+        pieces = concatref.split(*R.coo(), a["row_sizes"], a["col_sizes"])
+        for k, h in enumerate(ids):
+            I, J, V = pieces[k // a["grid"][1]][k % a["grid"][1]]
+            bi, bj, bv = m.t[h].coo() if h is not None else (np.zeros(0, int), np.zeros(0, int), np.zeros(0, R.dtype))
+            assert np.array_equal(I, bi) and np.array_equal(J, bj) and sm.same(V, bv), f"{label}: cell {k} of concat then split"
+
+
+def walk2(prog, cov, kind):
+    """run the model over one program of the second set, collecting the coverage figures"""
+    m = sm.Model()
+    fresh = {}                           # tiling -> links refreshed source first, one by one, since the chain's base was written
+    seen = set()
+    for i, rec in enumerate(prog):
+        op, ids, a = rec
+        dtype = sg.record_dtype(m, rec)
+        for h in ids:
+            assert h is None or h in m.t or h in m.p, f"step {i}: {rec} names a handle that is not alive"
+        built = {h: set(m.t[h].built) for h in ids if h in m.t}
+        refresh = op[16:] if op.startswith("set_values_from_") and op[16:] in sm.KINDS2 + ("build",) else None
+        if op in ("mxv", "reduce", "spmm"):
+            col = a["transpose"] if op != "reduce" else a["dim"] == "cols"
+            reads = [(ids[0], "col" if col else "row")]
+        elif op in ("step3", "spgemm"):
+            p = m.p[ids[0]]
+            reads = [(next(h for h, T in m.t.items() if T is x), r) for x, r in ((p.A, "plan_a"), (p.B, "plan_b")) if any(T is x for T in m.t.values())]
+        elif op in ("mxv_frontier", "mxv_arg", "reduce_arg"):
+            col = a["transpose"] if op != "reduce_arg" else a["dim"] == "cols"
+            reads = [(ids[0], ("frontier_" if op == "mxv_frontier" else "arg_") + ("col" if col else "row"))]
+        elif op in ("sampled_mxm", "set_values_sampled_mxm"):
+            reads = [(ids[1], "sampled_operand"), (ids[2], "sampled_operand")]
+        elif op == "trsv":
+            reads = [(ids[0], "trsv_" + a["uplo"])]
+        elif op == "lu_solve":
+            reads = [(ids[0], "trsv_lower"), (ids[0], "trsv_upper")]
+        else:
+            reads = []
+        reads = [(h, m.t[h].last_writer, r) for h, r in reads]
+        source_writers = [m.t[s].last_writer for s in ids[1:] if s in m.t] if refresh else []
+        trail = m.t[ids[0]].trail if op == "close" else None
+        res = m.apply(rec)
+        assert (res.status != 0) == ("expect" in a), f"step {i}: {rec}: model status {res.status}"
+        cov["steps"] += 1
+        if res.status != 0:
+            assert res.status == sm.PEM_E_INVALID or a["expect"] in sg.REFUSALS
+            cov["refusals"][a["expect"]] += 1
+            continue
+        cov["ops"][(op, dtype)] += 1
+        if op in ("transpose", "concat"):
+            _check_glue(m, rec, f"step {i}: {rec}")
+        for h, w, r in reads:
+            if w is not None:
+                cov["pairs"][(w, r)] += 1
+            if fresh.get(h, 0) >= 3:
+                seen.add("chain")
+        for h, before in built.items():
+            if h in m.t:
+                for s in m.t[h].built - before:
+                    cov["first"][s].add(op)
+        if op == "ilu0":
+            cov["first"]["trsv_lower"].add(op)
+        if refresh:
+            r = cov["refresh"][refresh]
+            r["times"] += 1
+            r["after a refresh of another kind"] += any(w is not None and w.startswith("from_") and w != "from_" + refresh for w in source_writers)
+            r["after set_values"] += any(w in ("set_values_row", "set_values_col") for w in source_writers)
+            r["holding another structure"] += bool(built[ids[0]] - {"map_" + refresh})
+        if op.startswith("set_values"):                  # the chain condition: what was refreshed in source-first order
+            tid = ids[0]
+            srcs = [s for s in sm.sources(m.t[tid].prov) if s in fresh] if "_from_" in op and op[16:] not in ("cplan", "build") else None
+            if srcs is None:
+                fresh[tid] = 0
+            elif srcs:
+                fresh[tid] = 1 + max(fresh[s] for s in srcs)
+            else:
+                fresh.pop(tid, None)
+            for j in _downstream(m, tid):
+                fresh.pop(j, None)
+        trails = [trail] if trail is not None else [T.trail for T in m.t.values()] if i + 1 == len(prog) else []
+        for t in trails:
+            if _has_subsequence(t, LIFE):
+                seen.add("life")
+            if "refresh" in t and "source" not in t[:t.index("refresh")] and _has_subsequence(t, CONCAT_LIFE):
+                seen.add("concat")
+        if op == "close":
+            fresh.pop(ids[0], None)
+    for s in seen:
+        cov[s][kind] += 1
+
+
+def coverage2():
+    cov = dict(steps=0, ops=collections.Counter(), pairs=collections.Counter(), refusals=collections.Counter(),
+               first=collections.defaultdict(set), refresh=collections.defaultdict(collections.Counter), chain=collections.Counter(),
+               life=collections.Counter(), concat=collections.Counter())
+    for seed in sg.SEEDS2:
+        walk2(sg.program(seed, sg.STEPS), cov, sg.context_kind(seed))
+    return cov
+
+
+REFRESH_CONDITIONS = ("times", "after a refresh of another kind", "after set_values", "holding another structure")
+
+
+def table2(cov):
+    lines = [f"sequence test coverage, second set: {len(sg.SEEDS2)} seeds x {sg.STEPS} steps = {cov['steps']} steps, "
+             f"{sum(cov['refusals'].values())} deliberate refusals"]
+    lines.append("operation kind            f64   f32")
+    for k in sg.KINDS2_T + sg.KINDS_T + sg.KINDS_P:
+        lines.append(f"  {k:24s}{cov['ops'][(k, 'f64')]:5d} {cov['ops'][(k, 'f32')]:5d}")
+    lines += [f"  {k:24s}{cov['ops'][(k, None)]:5d}" for k in sg.KINDS_CTX]
+    lines.append("writer -> reader          " + " ".join(f"{r:>10s}" for r in READERS + READERS2))
+    for w in WRITERS + WRITERS2:
+        lines.append(f"  {w:24s}" + " ".join(f"{cov['pairs'][(w, r)]:10d}" for r in READERS + READERS2))
+    lines.append("refreshes                 " + "; ".join(REFRESH_CONDITIONS))
+    lines += [f"  {k:24s}" + " ".join(f"{cov['refresh'][k][c]:5d}" for c in REFRESH_CONDITIONS) for k in sm.KINDS2 + ("build",)]
+    lines.append("first built by")
+    lines += [f"  {s:24s}{', '.join(sorted(cov['first'][s]))}" for s in SCHEDULES + MAPS2]
+    lines.append("refusals                  " + ", ".join(f"{k} {cov['refusals'][k]}" for k in sg.REFUSALS2 + sg.REFUSALS))
+    for what, name in (("chain", "chain of depth 3 refreshed link by link, then read"), ("life", "factor life"), ("concat", "concat between refreshes")):
+        lines.append(f"{name}: " + ", ".join(f"{k}: {cov[what][k]} programs" for k in sg.CONTEXT_KINDS))
+    return "\n".join(lines)
+
+
+def test_second_set_seeds_and_text():
+    assert len(sg.SEEDS2) == 24 and len(set(sg.SEEDS2) | set(sg.SEEDS)) == 48 and all(sg.op_set(s) == 2 for s in sg.SEEDS2)
+    assert all(sg.op_set(s) == 1 for s in sg.SEEDS)
+    assert [sg.context_kind(s) for s in sg.SEEDS2[:3]] == list(sg.CONTEXT_KINDS)
+    for seed in (sg.SEEDS2[0], sg.SEEDS2[11]):
+        a = sg.program(seed, 60)
+        assert a == sg.program(seed, 60) and sg.loads(sg.dumps(a)) == a and sg.program(seed, 30) == a[:30]
+
+
+def test_second_set_coverage_conditions():
+    """the model runs every program of SEEDS2, every record is well-typed and none is skipped (walk2 asserts both), and the
+    conditions the seed list must meet hold"""
+    cov = coverage2()
+    print("\n" + table2(cov))
+    assert cov["steps"] == len(sg.SEEDS2) * sg.STEPS
+    assert sum(cov["ops"].values()) + sum(cov["refusals"].values()) == cov["steps"]
+    for k in sg.KINDS2_T:
+        for d in ("f64", "f32"):
+            assert cov["ops"][(k, d)] >= 10, f"{k} in {d}: {cov['ops'][(k, d)]} times"
+    for k in sm.KINDS2:
+        r = cov["refresh"][k]
+        assert r["times"] >= 4, f"{k}: refreshed {r['times']} times"
+        for c in REFRESH_CONDITIONS[1:]:
+            assert r[c] >= 1, f"{k}: never refreshed {c}"
+    r = cov["refresh"]["build"]              # (a build has no source tiling: the two conditions on its source's writer do not apply)
+    assert r["times"] >= 4 and r["holding another structure"] >= 1, f"build: {dict(r)}"
+    for k in sg.CONTEXT_KINDS:
+        assert cov["chain"][k] >= 1, f"no chain on {k}"
+        assert cov["life"][k] >= 1, f"no factor life on {k}"
+    assert sum(cov["concat"].values()) >= 1
+    for w in WRITERS2:
+        for r in READERS:
+            assert cov["pairs"][(w, r)] >= 1, f"{w} -> {r}"
+    for r in READERS2:
+        assert len([w for w in WRITERS + WRITERS2 if cov["pairs"][(w, r)]]) >= 3, f"{r} reads after too few writer kinds"
+    for s in SCHEDULES:
+        assert len(cov["first"][s]) >= 2, f"{s}: first built only by {sorted(cov['first'][s])}"
+    assert sum(cov["refusals"].values()) * 10 <= cov["steps"]
+    for k in sg.REFUSALS2:
         assert cov["refusals"][k] >= 3, f"refusal {k}: {cov['refusals'][k]} times"
 
 

@@ -2,6 +2,7 @@
 """Replay one program of the sequence test (tests/test_gpu_seq.py) with per-step output.
 
     python tools/seq_replay.py --seed 107 [--steps 120] [--context session|torch_stream|graph_replay]
+    python tools/seq_replay.py --seed 1203            (a seed from seqgen.SET2_FROM on draws from the second operation set)
     python tools/seq_replay.py --program failing.txt [--context ...]
 
 --program reads the text a failing test printed (one JSON record per line; other lines are ignored), --seed regenerates the
@@ -26,12 +27,16 @@ def handles(rec):
     wrote = {a["out"]} if "out" in a else set()
     if op.startswith("set_values") or op in ("step1", "step2", "step3", "spgemm", "set_semiring", "set_option"):
         wrote.add(ids[0])
+    if op in ("trsv", "trsv_info", "lu_solve"):   # (the first of them builds the triangle's schedule, which stays with the tiling)
+        wrote.add(ids[0])
     return read, wrote
 
 
 def closure(prog, step, live=None):
     """indices of the steps that created or wrote a handle step `step` reads (live: every handle, for an audit), transitively"""
     operands = {r[2]["out"]: {h for h in r[1] if h is not None} for r in prog[:step + 1] if r[0] == "plan_create"}
+    # (a derived tiling's refresh names its sources itself -- a concat every cell -- so they are among the handles that step reads;
+    # the solves count as writers of their tiling: the kept schedule a later solve uses was built by one of them)
 
     def with_operands(hs):   # (a plan reads its operands' values whenever it runs, not only when it is made)
         return set(hs) | {t for h in hs for t in operands.get(h, ())}
