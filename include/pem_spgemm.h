@@ -881,6 +881,40 @@ typedef struct {
 } pem_ilu0_info;
 pem_status pem_tiled_ilu0_info(pem_ctx *ctx, const pem_tiled *F, pem_ilu0_info *out);
 
+/* Graph colouring: the greedy colouring of a square tiling's pattern, and the permutation that sorts the
+ * vertices by colour -- what reorders a matrix so that pem_tiled_trsv and pem_tiled_ilu0 have few levels -- on the device.
+ *   pem_tiled_colour  A is square (n = A.rows) and of either value type; values are never read.  The vertices are 0 .. n - 1; every
+ *       stored entry (i, j) with i != j, explicit zeros and NaN included, is an UNDIRECTED edge {i, j}; diagonal entries are ignored.
+ *       symmetric = 0: both directions are seen whatever is stored, so an edge stored one way counts.  symmetric = 1: the caller
+ *       promises a symmetric pattern and only the row orientation is walked; on a symmetric pattern the result is identical to
+ *       symmetric = 0.  Where the promise is false the call still ends and writes a colour in [0, n) everywhere; the colours are
+ *       otherwise unspecified.
+ *     Priorities.  d_priority == NULL: the priority of v is fmix32((uint32_t)v + seed * 0x9E3779B9u) in 32-bit wrap-around
+ *       arithmetic, fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16 -- a bijection, so no two
+ *       vertices tie.  It is computed in registers: no priority array exists.  d_priority != NULL: n uint32 on the device, larger
+ *       first; seed is ignored.  Ties go to the LOWER index, so all-equal priorities give the natural-order greedy colouring.
+ *     The result is fully determined: d_colour[v] (n int32 on the device) is the smallest colour >= 0 that no neighbour of higher
+ *       priority holds -- the sequential greedy colouring in descending (priority, -index) order.  *ncolours = the largest colour
+ *       + 1; *rounds = the number of vertices on the longest chain of neighbours with strictly falling priority (an isolated vertex
+ *       is coloured in round 1); both 0 for n = 0.  Two calls give identical arrays.
+ *     Rounds (Jones-Plassmann).  In a round every uncoloured vertex that no uncoloured neighbour beats takes its colour.  A round
+ *       reads one colour buffer and writes another: no kernel reads a colour the same launch writes, nothing waits on another
+ *       workgroup.  One 4-byte read-back per round; waits.  The second buffer is a grow-only allocation of the context (4 n bytes,
+ *       carved from its arena): a later call of the same or a smaller size allocates nothing.  symmetric = 0 builds
+ *       pem_tiled_mxv's column schedule on first use.
+ *     PEM_E_INVALID, before the device is touched: a null ctx, A, d_colour, ncolours or rounds; a tiling that is not square;
+ *       symmetric not 0 or 1; d_priority overlapping d_colour.  An empty tiling and n = 0 are legal.
+ *   pem_colour_order  the stable counting sort by colour.  d_colour: n int32 in [0, ncolours).  d_perm: n int32, the vertices
+ *       colour by colour, ascending inside a colour (numpy's argsort(colour, kind="stable")); d_offsets: ncolours + 1 int32, colour c
+ *       is d_perm[d_offsets[c] .. d_offsets[c + 1]).  d_perm goes straight into pem_tiled_extract_device as both lists.  One wait; the
+ *       sort's buffers (24 n bytes) share the context's grow-only allocation with pem_tiled_colour.
+ *     PEM_E_INVALID, before the device is touched: a null argument; n < 0 or n > INT32_MAX; ncolours < 0; ncolours = 0 with n > 0;
+ *       overlapping arrays.  A colour outside [0, ncolours) is found on the device and gives PEM_E_INVALID after the call's wait; the
+ *       outputs are then unspecified, but nothing is written outside them. */
+pem_status pem_tiled_colour(pem_ctx *ctx, const pem_tiled *A, int symmetric, uint32_t seed, const uint32_t *d_priority, int32_t *d_colour,
+                            int32_t *ncolours, int32_t *rounds);
+pem_status pem_colour_order(pem_ctx *ctx, int64_t n, const int32_t *d_colour, int32_t ncolours, int32_t *d_perm, int32_t *d_offsets);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

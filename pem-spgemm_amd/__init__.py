@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "pem_tiled_sampled_mxm", "pem_tiled_set_values_sampled_mxm",
     "pem_tiled_trsv", "pem_tiled_trsv_f32", "pem_tiled_trsv_info", "pem_test_trsv_split",
     "pem_tiled_ilu0", "pem_tiled_set_values_from_ilu0", "pem_tiled_ilu0_info",
+    "pem_tiled_colour", "pem_colour_order",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -771,6 +772,41 @@ class Tiled:
         _check(lib().pem_tiled_ilu0_info(self.ctx._h, self._h, C.byref(i)))
         return {k: int(getattr(i, k)) for k, _ in Ilu0Info._fields_}
 
+    def colour(self, seed=0, priority=None, symmetric=False, out=None):
+        """Greedy colouring of this square tiling's pattern: every stored off-diagonal (i, j) is an
+        undirected edge, values are never read.  Returns (colours, ncolours, rounds): colours an int32 device torch tensor (out,
+        written in place, when given) with colours[v] the smallest colour no neighbour of higher priority holds.  The priority of v is
+        a hash of v and seed (an integer in [0, 2^32)), or priority[v] -- a contiguous uint32 / int32 (read as uint32) torch tensor on
+        the context's device, or a host array of integers in [0, 2^32), uploaded -- larger first, ties to the lower index: equal
+        priorities give the natural-order greedy colouring.  symmetric=True promises a symmetric pattern (only the rows are walked;
+        the same result there).  Fully determined: two calls give identical tensors.  Waits (one small read-back per round)."""
+        seed = _colour_seed(seed)
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        pp = None
+        if priority is not None:
+            if hasattr(priority, "data_ptr"):
+                if (not priority.is_cuda or priority.device.index != self.ctx.device or priority.dim() != 1 or priority.numel() != self.rows
+                        or not priority.is_contiguous() or str(priority.dtype) not in ("torch.int32", "torch.uint32")):
+                    raise ValueError(f"colour: want a contiguous device tensor of {self.rows} uint32 or int32 values on cuda:{self.ctx.device} "
+                                     f"for priority, got {priority.dtype} of shape {tuple(priority.shape)} on {priority.device}")
+            else:
+                priority = torch.from_numpy(_colour_priority(priority, self.rows).view(np.int32)).to(dev)
+                torch.cuda.current_stream(dev).synchronize()   # (the priorities are read on the context's stream)
+            pp = C.c_void_p(priority.data_ptr() or 1)
+        out, pc = self._index_out("colour", "out", out, self.rows)
+        ncolours, rounds = C.c_int32(), C.c_int32()
+        _check(lib().pem_tiled_colour(self.ctx._h, self._h, int(bool(symmetric)), C.c_uint32(seed), pp, pc, C.byref(ncolours), C.byref(rounds)))
+        return out, ncolours.value, rounds.value
+
+    def reorder_by_colour(self, seed=0, symmetric=False):
+        """The colour reordering: (R, perm, offsets) with perm, offsets = colour_order of self.colour(seed,
+        symmetric=symmetric) and R = self.extract(perm, perm) -- inside a colour no vertex waits for another, so R.trsv and R.ilu0 have
+        few levels.  Composed from colour, colour_order and extract: R.set_values_from_extract(self) refreshes R.  Waits."""
+        colours, ncolours, _ = self.colour(seed=seed, symmetric=symmetric)
+        perm, offsets = colour_order(self.ctx, colours, ncolours)
+        return self.extract(perm, perm), perm, offsets
+
     def lu_solve(self, b, out=None, work=None):
         """z = U^-1 L^-1 b with this tiling an ILU(0) factor: trsv(b, "lower", unit_diag=True, out=work), then trsv(work, "upper",
         out=out).  b, out, work: as trsv's vectors; out and work are allocated when None.  Never waits once both schedules exist.
@@ -1087,6 +1123,48 @@ def triangle_count(A):
     per_row = R.reduce("plus", "rows")
     A.ctx.synchronize()
     return int(round(float(per_row.double().sum().item())))
+
+
+def _colour_seed(seed):
+    """Tiled.colour's seed: an integer in [0, 2^32)"""
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError(f"colour: seed must be an integer in [0, 2^32), not {seed!r}")
+    return int(seed)
+
+
+def _colour_priority(priority, n):
+    """Tiled.colour's host priorities -> a contiguous uint32 array of n entries"""
+    a = np.asarray(priority)
+    if a.ndim != 1 or a.size != n:
+        raise ValueError(f"colour: priority must hold {n} entries, one per vertex, not shape {a.shape}")
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"colour: priority must hold integers, not {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
+        raise ValueError("colour: priority holds a value outside [0, 2^32)")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def colour_order(ctx, colours, ncolours):
+    """The stable counting sort by colour: (perm, offsets), int32 device torch tensors -- perm the
+    vertices colour by colour, ascending inside a colour (np.argsort(colours, kind="stable")), offsets (ncolours + 1 entries) with
+    colour c = perm[offsets[c]:offsets[c + 1]].  colours: a contiguous 1-d int32 torch tensor on the context's device with values
+    in [0, ncolours) -- a value outside raises PemError; ncolours: an integer >= 0, at least 1 where colours has entries.  perm goes
+    straight into Tiled.extract as both lists.  Waits."""
+    if isinstance(ncolours, bool) or not isinstance(ncolours, numbers.Integral) or not 0 <= int(ncolours) < 2 ** 31:
+        raise ValueError(f"colour_order: ncolours must be an integer in [0, 2^31), not {ncolours!r}")
+    if (not hasattr(colours, "data_ptr") or not colours.is_cuda or colours.device.index != ctx.device or colours.dim() != 1
+            or not colours.is_contiguous() or str(colours.dtype) != "torch.int32"):
+        got = f"{colours.dtype} of shape {tuple(colours.shape)} on {colours.device}" if hasattr(colours, "data_ptr") else type(colours).__name__
+        raise ValueError(f"colour_order: want a contiguous 1-d int32 tensor on cuda:{ctx.device} for colours, got {got}")
+    n = colours.numel()
+    if n and not ncolours:
+        raise ValueError(f"colour_order: ncolours = 0 for {n} vertices")
+    import torch
+    perm = torch.empty(n, dtype=torch.int32, device=colours.device)
+    offsets = torch.empty(int(ncolours) + 1, dtype=torch.int32, device=colours.device)
+    _check(lib().pem_colour_order(ctx._h, C.c_int64(n), C.c_void_p(colours.data_ptr() or 1), C.c_int32(int(ncolours)),
+                                  C.c_void_p(perm.data_ptr() or 1), C.c_void_p(offsets.data_ptr())))
+    return perm, offsets
 
 
 class CPlan:

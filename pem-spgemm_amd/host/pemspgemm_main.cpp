@@ -111,6 +111,8 @@ struct Options {
     bool sampled_bt = false, triangles = false;                     // --triangles: see sampled_stage
     const char *trsv_spec = nullptr, *rhs_path = nullptr;           // --trsv lower|upper[:unit] [--rhs b.mtx]: see trsv_stage
     bool ilu0 = false;                                              // --ilu0: see ilu0_stage
+    const char *colour_spec = nullptr;                              // --colour SEED: see colour_stage
+    bool colour_natural = false;                                    // --colour-natural: equal priorities
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -142,6 +144,8 @@ struct Options {
     int trsv_uplo = -1;                                   // PEM_TRSV_LOWER / PEM_TRSV_UPPER
     bool trsv_unit = false;
     std::vector<double> rhs;                              // --rhs' values
+    uint32_t colour_seed = 0;
+    const char *colour_flag() const { return colour_spec ? "--colour" : colour_natural ? "--colour-natural" : nullptr; }
 };
 
 // Strips the flags above out of argv; what is not one of them (or is one without its value) stays positional.
@@ -161,12 +165,13 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
                   {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
                   {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path},
-                  {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}};
+                  {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}, {"--colour", &o->colour_spec}};
     const struct {
         const char *name;
         bool *flag, value;
     } plain[] = {{"--fp32", &o->fp32, true}, {"--mask-complement", &o->mask_complement, true}, {"--no-tune-split", &o->tune_split, false},
-                 {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}, {"--ilu0", &o->ilu0, true}};
+                 {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}, {"--ilu0", &o->ilu0, true},
+                 {"--colour-natural", &o->colour_natural, true}};
     o->args.assign(1, argv[0]);
     for (int r = 1; r < argc; ++r) {
         bool taken = false;
@@ -190,7 +195,7 @@ static void parse_args(int argc, char *argv[], Options *o)
 
 // The clash rules: a flag and what it refuses, the first one present being the one named.
 static const struct ClashRule {
-    const char *flag, *refused[8], *why;
+    const char *flag, *refused[10], *why;
 } clash_rules[] = {
     {"--power", {"--gpus", "--mask", "--B", "the A*A^T argument"}, " (A^K multiplies A by itself on one device)"},
     {"--add", {"--gpus", "--mask", "--power"}, ""},
@@ -205,6 +210,8 @@ static const struct ClashRule {
     {"--argreduce", {"--gpus", "--power", "--reduce", "--bfs", "--spmm", "--sddmm"}, ""},
     {"--bfs-parents", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
     {"--trsv", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
+    {"--colour", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
+    {"--colour-natural", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
@@ -227,7 +234,8 @@ static bool clashes(const Options &o, const char *flag)
                  {"--B", o.b_path != nullptr}, {"the A*A^T argument", o.aat},      {"--reduce", o.reduce_spec != nullptr},
                  {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr},
                  {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr},
-                 {"--bfs", o.bfs_spec != nullptr}, {"--argreduce", o.argreduce_spec != nullptr}};
+                 {"--bfs", o.bfs_spec != nullptr}, {"--argreduce", o.argreduce_spec != nullptr},
+                 {"--bfs-parents", o.bfs_parents_spec != nullptr}, {"--trsv", o.trsv_spec != nullptr}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -440,9 +448,24 @@ static int validate_dense(Options *o)
 }
 
 // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source; --argreduce:
-// the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front; --ilu0: what it does not combine with
+// the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front; --ilu0: what it does not combine with;
+// --colour: the seed, --colour-natural: nothing to read; either refuses every other vector output
 static int validate_vectors(Options *o)
 {
+    if (o->colour_spec && o->colour_natural) {
+        printf("--colour does not combine with --colour-natural (a seed hashes the priorities, --colour-natural makes them equal). Exiting.\n");
+        return 1;
+    }
+    if (o->colour_flag() && clashes(*o, o->colour_flag())) return 1;
+    if (o->colour_spec) {
+        char *end = nullptr;
+        const unsigned long long seed = strtoull(o->colour_spec, &end, 10);
+        if (end == o->colour_spec || *end != '\0' || o->colour_spec[0] == '-' || seed > 0xFFFFFFFFull) {
+            printf("--colour %s: want a seed in 0 .. 4294967295. Exiting.\n", o->colour_spec);
+            return 1;
+        }
+        o->colour_seed = (uint32_t)seed;
+    }
     if (o->ilu0 && clashes(*o, "--ilu0")) return 1;
     if (o->rhs_path && !o->trsv_spec) {
         printf("--rhs needs --trsv lower|upper[:unit]. Exiting.\n");
@@ -665,7 +688,8 @@ static int validate_sampled(Options *o)
                      {"--hstack", o->stack_paths[0] != nullptr}, {"--vstack", o->stack_paths[1] != nullptr}, {"--reduce", o->reduce_spec != nullptr},
                      {"--bfs", o->bfs_spec != nullptr}, {"--argreduce", o->argreduce_spec != nullptr}, {"--bfs-parents", o->bfs_parents_spec != nullptr},
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
-                     {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0},
+                     {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0}, {"--colour", o->colour_spec != nullptr},
+                     {"--colour-natural", o->colour_natural},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1307,6 +1331,7 @@ struct Result {
     const char *last_name = "C";        // ... and what the report lines call it
     std::vector<double> red, bfs_levels, spmm_y;   // --reduce's vector, --bfs' levels, --spmm's Y (row-major), on the host
     std::vector<double> arg_idx, bfs_parents;      // --argreduce's indices, --bfs-parents' parents: 1-based, 0 for none
+    std::vector<double> colours;                   // --colour's colours, 1-based
     std::vector<double> trsv_x;                    // --trsv's solution
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
@@ -2030,6 +2055,43 @@ static int bfs_parents_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--colour SEED` / `--colour-natural` colours the graph of the final result's pattern (what --reduce
+// would fold; it must be square; every stored off-diagonal entry is an undirected edge) on the device (pem_tiled_colour): the greedy
+// colouring in the order of the priorities SEED hashes, or in natural order (equal priorities).  One line reports colours, rounds
+// and the time; --out then writes the colours (Matrix-Market `array integer general`, 1-based) instead of the matrix.  The CSV
+// row describes the product.
+static int colour_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("%s: %s is %d x %d; a colouring needs a square matrix. Exiting.\n", o.colour_flag(), r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    DevBuf dc, dp;
+    if (!dc.alloc(n, 4) || (o.colour_natural && !dp.alloc(n, 4))) {
+        fprintf(stderr, "pemspgemm: %s: device allocation of %zu colours failed\n", o.colour_flag(), n);
+        return 2;
+    }
+    // (the fill runs on the null stream, the colouring on the context's: wait for it)
+    if (o.colour_natural && n && (hipMemset(dp.p, 0, 4 * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return 2;
+    CHECK(pem_ctx_synchronize(ctx));
+    int32_t ncolours = 0, rounds = 0;
+    auto c0 = Clock::now();
+    CHECK(pem_tiled_colour(ctx, src.t, 0, o.colour_seed, o.colour_natural ? (const uint32_t *)dp.p : nullptr, (int32_t *)dc.p, &ncolours, &rounds));
+    const double colour_ms = ms_since(c0);
+    std::vector<int32_t> colours(n);
+    if (n && hipMemcpy(colours.data(), dc.p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    r->colours.resize(n);
+    for (size_t v = 0; v < n; ++v) r->colours[v] = (double)(colours[v] + 1);
+    printf("colour: %s of %s: %d colours in %d rounds, %zu vertices, colour %.3fms\n",
+           o.colour_natural ? "natural order" : (std::string("seed ") + o.colour_spec).c_str(), r->last_name, ncolours, rounds, n, colour_ms);
+    return 0;
+}
+
 // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
 // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
 // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
@@ -2187,6 +2249,9 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     } else if (o.bfs_parents_spec) {
         rc = write_mm_array(o.out_path, "integer", "bfs parents from " + std::to_string(o.bfs_parents_src) + " (1-based, 0: unreachable)",
                             (int64_t)r->bfs_parents.size(), 1, r->bfs_parents, 1, false, "the ", "parents");
+    } else if (o.colour_flag()) {
+        rc = write_mm_array(o.out_path, "integer", std::string("greedy colours of the pattern of C = A*B, ") + (o.colour_natural ? "natural order" : std::string("seed ") + o.colour_spec) + " (1-based)",
+                            (int64_t)r->colours.size(), 1, r->colours, 1, false, "the ", "colours");
     } else if (o.argreduce_dim >= 0) {
         rc = write_mm_array(o.out_path, "integer", std::string("argreduce ") + o.argreduce_spec + " of C = A*B (1-based, 0: no entry)",
                             (int64_t)r->arg_idx.size(), 1, r->arg_idx, 1, false, "the ", "indices");
@@ -2251,6 +2316,7 @@ int main(int argc, char *argv[])
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
     if (!rc && o.argreduce_dim >= 0) rc = argreduce_stage(o, ctx, &r);
     if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
+    if (!rc && o.colour_flag()) rc = colour_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
     if (!rc && o.sddmm_path) rc = sddmm_stage(o, ctx, &r);
     if (!rc) rc = save_stage(o, ctx, &r);
