@@ -907,13 +907,46 @@ pem_status pem_tiled_ilu0_info(pem_ctx *ctx, const pem_tiled *F, pem_ilu0_info *
  *   pem_colour_order  the stable counting sort by colour.  d_colour: n int32 in [0, ncolours).  d_perm: n int32, the vertices
  *       colour by colour, ascending inside a colour (numpy's argsort(colour, kind="stable")); d_offsets: ncolours + 1 int32, colour c
  *       is d_perm[d_offsets[c] .. d_offsets[c + 1]).  d_perm goes straight into pem_tiled_extract_device as both lists.  One wait; the
- *       sort's buffers (24 n bytes) share the context's grow-only allocation with pem_tiled_colour.
+ *       sort's buffers (24 n bytes) share the context's grow-only allocation with pem_tiled_colour.  Any int32 key in [0, ncolours)
+ *       sorts: the component ids of pem_tiled_components with ncolours = its *ncomponents give the component order (the radix
+ *       sort takes the bits of ncolours, whatever its size).
  *     PEM_E_INVALID, before the device is touched: a null argument; n < 0 or n > INT32_MAX; ncolours < 0; ncolours = 0 with n > 0;
  *       overlapping arrays.  A colour outside [0, ncolours) is found on the device and gives PEM_E_INVALID after the call's wait; the
  *       outputs are then unspecified, but nothing is written outside them. */
 pem_status pem_tiled_colour(pem_ctx *ctx, const pem_tiled *A, int symmetric, uint32_t seed, const uint32_t *d_priority, int32_t *d_colour,
                             int32_t *ncolours, int32_t *rounds);
 pem_status pem_colour_order(pem_ctx *ctx, int64_t n, const int32_t *d_colour, int32_t ncolours, int32_t *d_perm, int32_t *d_offsets);
+
+/* Connected components: the components of a square tiling's pattern -- what splits a matrix that falls
+ * apart into independent blocks before pem_tiled_ilu0 and pem_tiled_trsv -- on the device.
+ *   pem_tiled_components  A is square (n = A.rows) and of either value type; values are never read.  The vertices are 0 .. n - 1;
+ *       every stored entry (i, j), explicit zeros and NaN included, is the UNDIRECTED edge {i, j}; a diagonal entry changes nothing.
+ *       symmetric = 0: both orientations are walked, as in pem_tiled_colour, so an edge stored one way counts: the weakly connected
+ *       components.  symmetric = 1: the caller promises a symmetric pattern and only the row orientation is walked; on a symmetric
+ *       pattern labels, ids, count and rounds are identical to symmetric = 0.  Where the promise is false the call still ends,
+ *       returns PEM_OK and writes 0 <= d_label[v] <= v everywhere; the values are otherwise unspecified.
+ *     The result is fully determined: d_label[v] (n int32 on the device) is the smallest vertex number in v's component.  d_id[v]
+ *       (n int32 on the device; d_id may be NULL) is the number of components whose smallest vertex is below d_label[v]: the dense
+ *       ids 0 .. *ncomponents - 1 in order of smallest vertex.  *ncomponents = the number of v with d_label[v] == v.  *rounds = the
+ *       number of rounds below that ran, the last one (which changes nothing) included: 1 for a graph without off-diagonal entries.
+ *       Both counts are 0 for n = 0.  Two calls give identical arrays and counts.
+ *     A round.  The state is a parent array f, started at f[v] = v.  gp[v] = f[f[v]]; m[v] = the minimum of gp[u] over the
+ *       neighbours u of v (none for a vertex without entries); f'[x] = min(gp[x], m[x], min{m[v] : f[v] == x}) -- FastSV's
+ *       shortcutting, aggressive hooking and hooking onto the parent, taken on one snapshot.  The call ends after the first round
+ *       with f' == f.  f' is a minimum over a fixed set, so it does not depend on any order: the rounds are determined although
+ *       the hooks are integer atomicMins.  No kernel plain-reads an array the same launch writes or hits with atomics, nothing
+ *       waits on another workgroup.  With both orientations walked f after t rounds is at most the smallest vertex within distance
+ *       t, so at most n rounds run; the loop never runs more: with symmetric = 0 a round n that still changed something is
+ *       PEM_E_HIP ("internal"), with symmetric = 1 the loop stops there with PEM_OK (the promise was false).
+ *     One 4-byte read-back per round; waits.  The scratch -- two buffers of n + 1 int32 (with d_label the three a round reads and
+ *       writes; the first then holds the root flags the ids' scan takes, in place) and the round words -- is the context's grow-only
+ *       allocation that pem_tiled_colour and pem_colour_order use (carved from its arena): a later call of the same or a smaller
+ *       size allocates nothing.  symmetric = 0 builds pem_tiled_mxv's column schedule on first use.
+ *     PEM_E_INVALID, before the device is touched: a null ctx, A, d_label, ncomponents or rounds; a tiling that is not square;
+ *       symmetric not 0 or 1; d_id overlapping d_label.  An empty tiling and n = 0 are legal.
+ *   The component order is pem_colour_order(ctx, n, d_id, ncomponents, d_perm, d_offsets): the ids are valid keys (see above). */
+pem_status pem_tiled_components(pem_ctx *ctx, const pem_tiled *A, int symmetric, int32_t *d_label, int32_t *d_id /* may be NULL */,
+                                int64_t *ncomponents, int32_t *rounds);
 
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only

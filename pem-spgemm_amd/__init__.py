@@ -64,7 +64,7 @@ ABI_SYMBOLS = [
     "pem_tiled_sampled_mxm", "pem_tiled_set_values_sampled_mxm",
     "pem_tiled_trsv", "pem_tiled_trsv_f32", "pem_tiled_trsv_info", "pem_test_trsv_split",
     "pem_tiled_ilu0", "pem_tiled_set_values_from_ilu0", "pem_tiled_ilu0_info",
-    "pem_tiled_colour", "pem_colour_order",
+    "pem_tiled_colour", "pem_colour_order", "pem_tiled_components",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -807,6 +807,33 @@ class Tiled:
         perm, offsets = colour_order(self.ctx, colours, ncolours)
         return self.extract(perm, perm), perm, offsets
 
+    def components(self, symmetric=False, out=None, ids=True, out_ids=None):
+        """Connected components of this square tiling's pattern: every stored entry (i, j) is the
+        undirected edge {i, j}, values are never read.  Returns (labels, ids, ncomponents, rounds): labels an int32 device torch
+        tensor (out, written in place, when given) with labels[v] the smallest vertex of v's component; ids likewise (out_ids) the
+        dense component ids 0 .. ncomponents - 1 in order of smallest vertex, or None with ids=False (the library then gets NULL);
+        rounds the rounds of the label propagation, the last one, which changes nothing, included.  symmetric=True promises a
+        symmetric pattern (only the rows are walked; the same result there; on another pattern 0 <= labels[v] <= v and nothing
+        more).  Fully determined: two calls give identical tensors.  Waits (one small read-back per round)."""
+        if not ids and out_ids is not None:
+            raise ValueError("components: out_ids given with ids=False")
+        out, pl = self._index_out("components", "out", out, self.rows)
+        pi = None
+        if ids:
+            out_ids, pi = self._index_out("components", "out_ids", out_ids, self.rows)
+        ncomponents, rounds = C.c_int64(), C.c_int32()
+        _check(lib().pem_tiled_components(self.ctx._h, self._h, int(bool(symmetric)), pl, pi, C.byref(ncomponents), C.byref(rounds)))
+        return out, (out_ids if ids else None), ncomponents.value, rounds.value
+
+    def reorder_by_component(self, symmetric=False):
+        """The component reordering: (R, perm, offsets) with perm, offsets = colour_order of the ids of
+        self.components(symmetric=symmetric) and R = self.extract(perm, perm) -- block diagonal, the blocks in order of their
+        smallest vertex, the vertices ascending inside a block; block c is R.extract(slice(offsets[c], offsets[c + 1]), the same).
+        Composed from components, colour_order and extract: R.set_values_from_extract(self) refreshes R.  Waits."""
+        _, ids, ncomponents, _ = self.components(symmetric=symmetric)
+        perm, offsets = colour_order(self.ctx, ids, ncomponents)
+        return self.extract(perm, perm), perm, offsets
+
     def lu_solve(self, b, out=None, work=None):
         """z = U^-1 L^-1 b with this tiling an ILU(0) factor: trsv(b, "lower", unit_diag=True, out=work), then trsv(work, "upper",
         out=out).  b, out, work: as trsv's vectors; out and work are allocated when None.  Never waits once both schedules exist.
@@ -1148,7 +1175,8 @@ def colour_order(ctx, colours, ncolours):
     """The stable counting sort by colour: (perm, offsets), int32 device torch tensors -- perm the
     vertices colour by colour, ascending inside a colour (np.argsort(colours, kind="stable")), offsets (ncolours + 1 entries) with
     colour c = perm[offsets[c]:offsets[c + 1]].  colours: a contiguous 1-d int32 torch tensor on the context's device with values
-    in [0, ncolours) -- a value outside raises PemError; ncolours: an integer >= 0, at least 1 where colours has entries.  perm goes
+    in [0, ncolours) (any such key sorts: Tiled.components' ids with its ncomponents give the component order) -- a value outside
+    raises PemError; ncolours: an integer >= 0, at least 1 where colours has entries.  perm goes
     straight into Tiled.extract as both lists.  Waits."""
     if isinstance(ncolours, bool) or not isinstance(ncolours, numbers.Integral) or not 0 <= int(ncolours) < 2 ** 31:
         raise ValueError(f"colour_order: ncolours must be an integer in [0, 2^31), not {ncolours!r}")

@@ -113,6 +113,7 @@ struct Options {
     bool ilu0 = false;                                              // --ilu0: see ilu0_stage
     const char *colour_spec = nullptr;                              // --colour SEED: see colour_stage
     bool colour_natural = false;                                    // --colour-natural: equal priorities
+    bool components = false;                                        // --components: see components_stage
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -171,7 +172,7 @@ static void parse_args(int argc, char *argv[], Options *o)
         bool *flag, value;
     } plain[] = {{"--fp32", &o->fp32, true}, {"--mask-complement", &o->mask_complement, true}, {"--no-tune-split", &o->tune_split, false},
                  {"--sampled-bt", &o->sampled_bt, true}, {"--triangles", &o->triangles, true}, {"--ilu0", &o->ilu0, true},
-                 {"--colour-natural", &o->colour_natural, true}};
+                 {"--colour-natural", &o->colour_natural, true}, {"--components", &o->components, true}};
     o->args.assign(1, argv[0]);
     for (int r = 1; r < argc; ++r) {
         bool taken = false;
@@ -195,7 +196,7 @@ static void parse_args(int argc, char *argv[], Options *o)
 
 // The clash rules: a flag and what it refuses, the first one present being the one named.
 static const struct ClashRule {
-    const char *flag, *refused[10], *why;
+    const char *flag, *refused[12], *why;
 } clash_rules[] = {
     {"--power", {"--gpus", "--mask", "--B", "the A*A^T argument"}, " (A^K multiplies A by itself on one device)"},
     {"--add", {"--gpus", "--mask", "--power"}, ""},
@@ -212,6 +213,9 @@ static const struct ClashRule {
     {"--trsv", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
     {"--colour", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
     {"--colour-natural", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
+    {"--components",
+     {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm", "--colour", "--colour-natural"},
+     ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
@@ -235,7 +239,8 @@ static bool clashes(const Options &o, const char *flag)
                  {"--spmm", o.spmm_path != nullptr}, {"--sddmm", o.sddmm_path != nullptr},
                  {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr},
                  {"--bfs", o.bfs_spec != nullptr}, {"--argreduce", o.argreduce_spec != nullptr},
-                 {"--bfs-parents", o.bfs_parents_spec != nullptr}, {"--trsv", o.trsv_spec != nullptr}};
+                 {"--bfs-parents", o.bfs_parents_spec != nullptr}, {"--trsv", o.trsv_spec != nullptr},
+                 {"--colour", o.colour_spec != nullptr}, {"--colour-natural", o.colour_natural}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -449,9 +454,10 @@ static int validate_dense(Options *o)
 
 // --reduce: the dimension and the op (pem_binop; default: the semiring's additive op); --bfs: the 1-based source; --argreduce:
 // the dimension and min or max; --bfs-parents: the 1-based source; --trsv: the triangle and :unit, --rhs read up front; --ilu0: what it does not combine with;
-// --colour: the seed, --colour-natural: nothing to read; either refuses every other vector output
+// --colour: the seed, --colour-natural: nothing to read; either refuses every other vector output; --components: those and the two
 static int validate_vectors(Options *o)
 {
+    if (o->components && clashes(*o, "--components")) return 1;
     if (o->colour_spec && o->colour_natural) {
         printf("--colour does not combine with --colour-natural (a seed hashes the priorities, --colour-natural makes them equal). Exiting.\n");
         return 1;
@@ -689,7 +695,7 @@ static int validate_sampled(Options *o)
                      {"--bfs", o->bfs_spec != nullptr}, {"--argreduce", o->argreduce_spec != nullptr}, {"--bfs-parents", o->bfs_parents_spec != nullptr},
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
                      {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0}, {"--colour", o->colour_spec != nullptr},
-                     {"--colour-natural", o->colour_natural},
+                     {"--colour-natural", o->colour_natural}, {"--components", o->components},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1332,6 +1338,7 @@ struct Result {
     std::vector<double> red, bfs_levels, spmm_y;   // --reduce's vector, --bfs' levels, --spmm's Y (row-major), on the host
     std::vector<double> arg_idx, bfs_parents;      // --argreduce's indices, --bfs-parents' parents: 1-based, 0 for none
     std::vector<double> colours;                   // --colour's colours, 1-based
+    std::vector<double> labels;                    // --components' labels, 1-based
     std::vector<double> trsv_x;                    // --trsv's solution
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
@@ -2092,6 +2099,41 @@ static int colour_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--components` labels the connected components of the graph of the final result's pattern (what
+// --colour would colour; it must be square; every stored entry is an undirected edge, stored one way or both) on the device
+// (pem_tiled_components): every vertex gets the smallest vertex of its component.  One line reports components, rounds and the
+// time; --out then writes the labels (Matrix-Market `array integer general`, 1-based) instead of the matrix.  The CSV row describes
+// the product.
+static int components_stage(const Options &, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("--components: %s is %d x %d; the components need a square matrix. Exiting.\n", r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    DevBuf dl;
+    if (!dl.alloc(n, 4)) {
+        fprintf(stderr, "pemspgemm: --components: device allocation of %zu labels failed\n", n);
+        return 2;
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    int64_t ncomponents = 0;
+    int32_t rounds = 0;
+    auto c0 = Clock::now();
+    CHECK(pem_tiled_components(ctx, src.t, 0, (int32_t *)dl.p, nullptr, &ncomponents, &rounds));
+    const double components_ms = ms_since(c0);
+    std::vector<int32_t> labels(n);
+    if (n && hipMemcpy(labels.data(), dl.p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    r->labels.resize(n);
+    for (size_t v = 0; v < n; ++v) r->labels[v] = (double)(labels[v] + 1);
+    printf("components: %lld components in %d rounds, %zu vertices, %.3fms\n", (long long)ncomponents, rounds, n, components_ms);
+    return 0;
+}
+
 // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
 // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
 // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
@@ -2215,7 +2257,7 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
+// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the colours of --colour, else the labels of --components, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
 // matrix: the sampled product of --sddmm, the final result when it is a tiling (its CSR export), or the plan's C (CSR export:
 // rows ascending, columns ascending).  The comment line says how the matrix came about.
 static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
@@ -2252,6 +2294,9 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     } else if (o.colour_flag()) {
         rc = write_mm_array(o.out_path, "integer", std::string("greedy colours of the pattern of C = A*B, ") + (o.colour_natural ? "natural order" : std::string("seed ") + o.colour_spec) + " (1-based)",
                             (int64_t)r->colours.size(), 1, r->colours, 1, false, "the ", "colours");
+    } else if (o.components) {
+        rc = write_mm_array(o.out_path, "integer", "connected components of the pattern of C = A*B: the smallest vertex of every vertex's component (1-based)",
+                            (int64_t)r->labels.size(), 1, r->labels, 1, false, "the ", "labels");
     } else if (o.argreduce_dim >= 0) {
         rc = write_mm_array(o.out_path, "integer", std::string("argreduce ") + o.argreduce_spec + " of C = A*B (1-based, 0: no entry)",
                             (int64_t)r->arg_idx.size(), 1, r->arg_idx, 1, false, "the ", "indices");
@@ -2317,6 +2362,7 @@ int main(int argc, char *argv[])
     if (!rc && o.argreduce_dim >= 0) rc = argreduce_stage(o, ctx, &r);
     if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
     if (!rc && o.colour_flag()) rc = colour_stage(o, ctx, &r);
+    if (!rc && o.components) rc = components_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
     if (!rc && o.sddmm_path) rc = sddmm_stage(o, ctx, &r);
     if (!rc) rc = save_stage(o, ctx, &r);
