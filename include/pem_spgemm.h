@@ -948,6 +948,45 @@ pem_status pem_colour_order(pem_ctx *ctx, int64_t n, const int32_t *d_colour, in
 pem_status pem_tiled_components(pem_ctx *ctx, const pem_tiled *A, int symmetric, int32_t *d_label, int32_t *d_id /* may be NULL */,
                                 int64_t *ncomponents, int32_t *rounds);
 
+/* Independent sets and aggregation: a maximal independent set at distance 1 or 2 of a square tiling's
+ * pattern and the MIS(2) aggregation (Bell, Dalton, Olson) on top of it -- the first step of an algebraic-multigrid level, what
+ * makes the P of P^T (A P) -- on the device.
+ *   The graph, the priorities and "beats" are pem_tiled_colour's: A is square (n = A.rows) and of either value type, values are
+ *       never read; every stored off-diagonal (i, j), explicit zeros and NaN included, is the UNDIRECTED edge {i, j}.  symmetric = 0
+ *       walks the row line and the column line (pem_tiled_mxv's column schedule, built on first use); symmetric = 1 is the caller's
+ *       promise of a symmetric pattern and only rows are walked.  The priority of v is fmix32(v + seed * 0x9E3779B9) computed in
+ *       registers when d_priority is NULL, else d_priority[v] (n uint32 on the device).  u BEATS v when prio[u] > prio[v], or the two
+ *       are equal and u < v.  Distance is path length in this undirected graph.
+ *   pem_tiled_mis  d_in_set (n bytes on the device, 0 / 1) is the set the sequential greedy pass builds: the vertices are taken in
+ *       "beats" order and v enters iff no vertex already in the set lies within `distance` (1 or 2) of v.  It is independent and
+ *       maximal at that distance; a vertex without off-diagonal entries is always in it.  *count is its size.
+ *     The device runs rounds on a three-valued state -- undecided, in, out; all start undecided -- every round taken from one
+ *       snapshot: an undecided v with an in vertex within `distance` turns out; otherwise an undecided v that no undecided vertex
+ *       within `distance` beats turns in; everything else stays.  Out vertices still relay: distance 2 through an out (or in) middle
+ *       vertex counts.  The call ends after the first round that leaves no undecided vertex; *rounds counts the rounds that ran: 1
+ *       for a graph without edges, 0 for n = 0.  The rounds reproduce the greedy set exactly and every decision is a maximum over a
+ *       fixed set, so set, count and rounds are fully determined.  Every round decides at least the best undecided vertex, so at
+ *       most n rounds run: with symmetric = 0 a round n that leaves an undecided vertex is PEM_E_HIP ("internal"); with
+ *       symmetric = 1 (a false promise) the loop stops there with PEM_OK, and every byte of d_in_set is 0 or 1.
+ *   pem_tiled_aggregate  The roots are pem_tiled_mis at distance 2 with the same arguments; *rounds is its rounds.  The roots are
+ *       numbered densely in ascending vertex order; *naggregates is their number; d_root[c] (n int32 on the device, may be NULL) is
+ *       the root of aggregate c, entries from *naggregates up to n are -1.  Pass 1: a non-root v with a root neighbour joins that
+ *       root's aggregate (on an undirected graph there is at most one; where a false promise shows several, the one that beats the
+ *       others).  Pass 2: a v still without an aggregate takes, of its neighbours that pass 1 placed, the u that beats the others and
+ *       joins d_aggregate[u]; what pass 2 itself places is not seen.  On an undirected graph every vertex is placed, every
+ *       aggregate holds exactly one root, is connected and has radius <= 2 around its root, and a vertex without edges is an
+ *       aggregate of one.  Under a false symmetric = 1 promise a vertex may keep -1; everything written lies in [-1, *naggregates).
+ *   Both: PEM_E_INVALID, before the device is touched: a null ctx, A, output array (d_in_set, d_aggregate) or count pointer; a
+ *       tiling that is not square; distance not 1 or 2; symmetric not 0 or 1; d_priority overlapping an output; d_aggregate
+ *       overlapping d_root.  An empty tiling and n = 0 are legal.  One 4-byte read-back per round; waits.  No kernel plain-reads, at
+ *       another vertex, an array the same launch writes; nothing waits on another workgroup.  The scratch (state bytes, the 8-byte
+ *       first-hop maxima, the scan's flags, a second aggregate buffer, the round words) is the context's grow-only allocation
+ *       pem_tiled_colour uses: a later call of the same or a smaller size allocates nothing. */
+pem_status pem_tiled_mis(pem_ctx *ctx, const pem_tiled *A, int distance /* 1 or 2 */, int symmetric, uint32_t seed,
+                         const uint32_t *d_priority /* may be NULL */, uint8_t *d_in_set /* n bytes, 0 / 1 */, int64_t *count, int32_t *rounds);
+pem_status pem_tiled_aggregate(pem_ctx *ctx, const pem_tiled *A, int symmetric, uint32_t seed, const uint32_t *d_priority /* may be NULL */,
+                               int32_t *d_aggregate /* n */, int32_t *d_root /* n, may be NULL */, int64_t *naggregates, int32_t *rounds);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "pem_tiled_trsv", "pem_tiled_trsv_f32", "pem_tiled_trsv_info", "pem_test_trsv_split",
     "pem_tiled_ilu0", "pem_tiled_set_values_from_ilu0", "pem_tiled_ilu0_info",
     "pem_tiled_colour", "pem_colour_order", "pem_tiled_components",
+    "pem_tiled_mis", "pem_tiled_aggregate",
 ]
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -174,6 +175,13 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.pem_last_error.restype = C.c_char_p
         L.pem_version.restype = C.c_char_p
+        # (ctx, A, distance, symmetric, seed, d_priority, d_in_set, count, rounds) and
+        # (ctx, A, symmetric, seed, d_priority, d_aggregate, d_root, naggregates, rounds): include/pem_spgemm.h
+        L.pem_tiled_mis.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int32)]
+        L.pem_tiled_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.pem_tiled_mis.restype = L.pem_tiled_aggregate.restype = C.c_int
         _lib = L
     return _lib
 
@@ -781,23 +789,66 @@ class Tiled:
         priorities give the natural-order greedy colouring.  symmetric=True promises a symmetric pattern (only the rows are walked;
         the same result there).  Fully determined: two calls give identical tensors.  Waits (one small read-back per round)."""
         seed = _colour_seed(seed)
-        import torch
-        dev = torch.device("cuda", self.ctx.device)
-        pp = None
-        if priority is not None:
-            if hasattr(priority, "data_ptr"):
-                if (not priority.is_cuda or priority.device.index != self.ctx.device or priority.dim() != 1 or priority.numel() != self.rows
-                        or not priority.is_contiguous() or str(priority.dtype) not in ("torch.int32", "torch.uint32")):
-                    raise ValueError(f"colour: want a contiguous device tensor of {self.rows} uint32 or int32 values on cuda:{self.ctx.device} "
-                                     f"for priority, got {priority.dtype} of shape {tuple(priority.shape)} on {priority.device}")
-            else:
-                priority = torch.from_numpy(_colour_priority(priority, self.rows).view(np.int32)).to(dev)
-                torch.cuda.current_stream(dev).synchronize()   # (the priorities are read on the context's stream)
-            pp = C.c_void_p(priority.data_ptr() or 1)
+        priority, pp = self._priority_arg("colour", priority)
         out, pc = self._index_out("colour", "out", out, self.rows)
         ncolours, rounds = C.c_int32(), C.c_int32()
         _check(lib().pem_tiled_colour(self.ctx._h, self._h, int(bool(symmetric)), C.c_uint32(seed), pp, pc, C.byref(ncolours), C.byref(rounds)))
         return out, ncolours.value, rounds.value
+
+    def _priority_arg(self, fn, priority):
+        """(tensor kept alive, device pointer or None) of colour's / mis' / aggregate's priority: a device tensor as it is, a host
+        array uploaded"""
+        if priority is None:
+            return None, None
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if hasattr(priority, "data_ptr"):
+            if (not priority.is_cuda or priority.device.index != self.ctx.device or priority.dim() != 1 or priority.numel() != self.rows
+                    or not priority.is_contiguous() or str(priority.dtype) not in ("torch.int32", "torch.uint32")):
+                raise ValueError(f"{fn}: want a contiguous device tensor of {self.rows} uint32 or int32 values on cuda:{self.ctx.device} "
+                                 f"for priority, got {priority.dtype} of shape {tuple(priority.shape)} on {priority.device}")
+        else:
+            priority = torch.from_numpy(_colour_priority(priority, self.rows, fn).view(np.int32)).to(dev)
+            torch.cuda.current_stream(dev).synchronize()   # (the priorities are read on the context's stream)
+        return priority, C.c_void_p(priority.data_ptr() or 1)
+
+    def mis(self, distance=2, seed=0, priority=None, symmetric=False, out=None):
+        """Maximal independent set at distance 1 or 2 of this square tiling's pattern: the graph, seed,
+        priority and symmetric are colour's.  Returns (in_set, count, rounds): in_set a torch.uint8 device tensor of 0 / 1 (out,
+        written in place, when given) -- the set the sequential greedy pass in "beats" order builds: v enters iff no vertex already
+        in the set lies within `distance` of it; count its size; rounds the rounds the device ran.  Fully determined: two calls give
+        identical tensors.  Waits (one small read-back per round)."""
+        if isinstance(distance, bool) or distance not in (1, 2):
+            raise ValueError(f"mis: distance must be 1 or 2, not {distance!r}")
+        seed = _colour_seed(seed, "mis")
+        import torch
+        priority, pp = self._priority_arg("mis", priority)
+        if out is None:
+            out = torch.empty(self.rows, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+        if (not hasattr(out, "data_ptr") or not out.is_cuda or out.device.index != self.ctx.device or out.numel() != self.rows
+                or out.dim() != 1 or not out.is_contiguous() or out.dtype != torch.uint8):
+            got = f"{out.dtype} of shape {tuple(out.shape)} on {out.device}" if hasattr(out, "data_ptr") else type(out).__name__
+            raise ValueError(f"mis: want a contiguous device tensor of {self.rows} uint8 values on cuda:{self.ctx.device} for out, got {got}")
+        count, rounds = C.c_int64(), C.c_int32()
+        _check(lib().pem_tiled_mis(self.ctx._h, self._h, int(distance), int(bool(symmetric)), C.c_uint32(seed), pp,
+                                   C.c_void_p(out.data_ptr() or 1), C.byref(count), C.byref(rounds)))
+        return out, count.value, rounds.value
+
+    def aggregate(self, seed=0, priority=None, symmetric=False, out=None, roots=True):
+        """MIS(2) aggregation of this square tiling's pattern: the roots are self.mis(2, ...), numbered
+        in ascending vertex order; a root's neighbours join it, then every vertex still free joins the aggregate of the placed
+        neighbour that beats the others.  Returns (agg, roots, naggregates, rounds): agg an int32 device tensor (out, written in
+        place, when given) with agg[v] in [0, naggregates); roots the int32 device tensor of naggregates root vertices, or None with
+        roots=False (the library then gets NULL); rounds those of the set.  Under a false symmetric=True promise agg may hold -1.
+        Fully determined.  Waits (one small read-back per round)."""
+        seed = _colour_seed(seed, "aggregate")
+        priority, pp = self._priority_arg("aggregate", priority)
+        out, pa = self._index_out("aggregate", "out", out, self.rows)
+        root_t, pr = (self._index_out("aggregate", "roots", None, self.rows) if roots else (None, None))
+        nagg, rounds = C.c_int64(), C.c_int32()
+        _check(lib().pem_tiled_aggregate(self.ctx._h, self._h, int(bool(symmetric)), C.c_uint32(seed), pp, pa, pr, C.byref(nagg),
+                                         C.byref(rounds)))
+        return out, (root_t[:nagg.value] if roots else None), nagg.value, rounds.value
 
     def reorder_by_colour(self, seed=0, symmetric=False):
         """The colour reordering: (R, perm, offsets) with perm, offsets = colour_order of self.colour(seed,
@@ -1152,23 +1203,53 @@ def triangle_count(A):
     return int(round(float(per_row.double().sum().item())))
 
 
-def _colour_seed(seed):
-    """Tiled.colour's seed: an integer in [0, 2^32)"""
+def _colour_seed(seed, fn="colour"):
+    """Tiled.colour's (mis', aggregate's) seed: an integer in [0, 2^32)"""
     if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 2 ** 32:
-        raise ValueError(f"colour: seed must be an integer in [0, 2^32), not {seed!r}")
+        raise ValueError(f"{fn}: seed must be an integer in [0, 2^32), not {seed!r}")
     return int(seed)
 
 
-def _colour_priority(priority, n):
-    """Tiled.colour's host priorities -> a contiguous uint32 array of n entries"""
+def _colour_priority(priority, n, fn="colour"):
+    """Tiled.colour's (mis', aggregate's) host priorities -> a contiguous uint32 array of n entries"""
     a = np.asarray(priority)
     if a.ndim != 1 or a.size != n:
-        raise ValueError(f"colour: priority must hold {n} entries, one per vertex, not shape {a.shape}")
+        raise ValueError(f"{fn}: priority must hold {n} entries, one per vertex, not shape {a.shape}")
     if a.size and a.dtype.kind not in "iu":
-        raise ValueError(f"colour: priority must hold integers, not {a.dtype}")
+        raise ValueError(f"{fn}: priority must hold integers, not {a.dtype}")
     if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
-        raise ValueError("colour: priority holds a value outside [0, 2^32)")
+        raise ValueError(f"{fn}: priority holds a value outside [0, 2^32)")
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def prolongator(ctx, agg, naggregates, values=None, dtype=np.float64):
+    """The piecewise-constant prolongator of an aggregation: the n x naggregates tiling P with one entry
+    per row, at (v, agg[v]), of value 1 -- or values[v], a near-null-space vector.  agg: Tiled.aggregate's contiguous 1-d int32
+    tensor on the context's device; an entry outside [0, naggregates) (the -1 a false symmetric=True promise leaves) is refused.
+    values: a contiguous device tensor of n values of `dtype`, or None.  Made by Tiled.from_coo_device: nothing leaves the device
+    but the one flag of the range check.  Waits."""
+    if isinstance(naggregates, bool) or not isinstance(naggregates, numbers.Integral) or not 0 <= int(naggregates) < 2 ** 31:
+        raise ValueError(f"prolongator: naggregates must be an integer in [0, 2^31), not {naggregates!r}")
+    if (not hasattr(agg, "data_ptr") or not agg.is_cuda or agg.device.index != ctx.device or agg.dim() != 1 or not agg.is_contiguous()
+            or str(agg.dtype) != "torch.int32"):
+        got = f"{agg.dtype} of shape {tuple(agg.shape)} on {agg.device}" if hasattr(agg, "data_ptr") else type(agg).__name__
+        raise ValueError(f"prolongator: want a contiguous 1-d int32 tensor on cuda:{ctx.device} for agg, got {got}")
+    import torch
+    n = agg.numel()
+    tdtype = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    if values is None:
+        values = torch.ones(n, dtype=tdtype, device=agg.device)
+    elif (not hasattr(values, "data_ptr") or not values.is_cuda or values.device != agg.device or values.dim() != 1 or values.numel() != n
+            or not values.is_contiguous() or values.dtype != tdtype):
+        got = f"{values.dtype} of shape {tuple(values.shape)} on {values.device}" if hasattr(values, "data_ptr") else type(values).__name__
+        raise ValueError(f"prolongator: want a contiguous device tensor of {n} {tdtype} values on {agg.device} for values, got {got}")
+    if n and bool(((agg < 0) | (agg >= int(naggregates))).any()):
+        raise ValueError(f"prolongator: agg holds an entry outside [0, {int(naggregates)}): a vertex without an aggregate has no row of P")
+    rows = torch.arange(n, dtype=torch.int32, device=agg.device)
+    torch.cuda.current_stream(agg.device).synchronize()   # (the triplets are read on the context's stream)
+    P = Tiled.from_coo_device(ctx, n, int(naggregates), n, rows.data_ptr() or 1, agg.data_ptr() or 1, values.data_ptr() or 1, dtype=dtype)
+    ctx.synchronize()   # (rows and a default values are freed on return)
+    return P
 
 
 def colour_order(ctx, colours, ncolours):

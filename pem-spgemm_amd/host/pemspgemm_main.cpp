@@ -114,6 +114,7 @@ struct Options {
     const char *colour_spec = nullptr;                              // --colour SEED: see colour_stage
     bool colour_natural = false;                                    // --colour-natural: equal priorities
     bool components = false;                                        // --components: see components_stage
+    const char *aggregate_spec = nullptr;                           // --aggregate SEED: see aggregate_stage
 
     // what is left for the reference's grammar: args[0] the program, args[1] the input, then [0|1] and the A*A^T argument
     std::string standin_path;
@@ -146,6 +147,7 @@ struct Options {
     bool trsv_unit = false;
     std::vector<double> rhs;                              // --rhs' values
     uint32_t colour_seed = 0;
+    uint32_t aggregate_seed = 0;
     const char *colour_flag() const { return colour_spec ? "--colour" : colour_natural ? "--colour-natural" : nullptr; }
 };
 
@@ -166,7 +168,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--kron", &o->kron_path}, {"--kron-op", &o->kron_op_name}, {"--topk", &o->topk_spec},
                   {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
                   {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path},
-                  {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}, {"--colour", &o->colour_spec}};
+                  {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}, {"--colour", &o->colour_spec},
+                  {"--aggregate", &o->aggregate_spec}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -216,6 +219,10 @@ static const struct ClashRule {
     {"--components",
      {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm", "--colour", "--colour-natural"},
      ""},
+    {"--aggregate",
+     {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm", "--colour", "--colour-natural",
+      "--components"},
+     ""},
     {"--gpus", {"--mask"}, " (masked products run on one device)"},
     {"--apply", {"--gpus", "--power"}, ""},
     {"--row-scale", {"--gpus", "--power"}, ""},
@@ -240,7 +247,8 @@ static bool clashes(const Options &o, const char *flag)
                  {"--cache", o.cache_dir != nullptr}, {"--vstack", o.stack_paths[1] != nullptr},
                  {"--bfs", o.bfs_spec != nullptr}, {"--argreduce", o.argreduce_spec != nullptr},
                  {"--bfs-parents", o.bfs_parents_spec != nullptr}, {"--trsv", o.trsv_spec != nullptr},
-                 {"--colour", o.colour_spec != nullptr}, {"--colour-natural", o.colour_natural}};
+                 {"--colour", o.colour_spec != nullptr}, {"--colour-natural", o.colour_natural},
+                 {"--components", o.components}};
     for (const ClashRule &rule : clash_rules) {
         if (strcmp(rule.flag, flag)) continue;
         for (const char *other : rule.refused)
@@ -472,6 +480,16 @@ static int validate_vectors(Options *o)
         }
         o->colour_seed = (uint32_t)seed;
     }
+    if (o->aggregate_spec) {
+        if (clashes(*o, "--aggregate")) return 1;
+        char *end = nullptr;
+        const unsigned long long seed = strtoull(o->aggregate_spec, &end, 10);
+        if (end == o->aggregate_spec || *end != '\0' || o->aggregate_spec[0] == '-' || seed > 0xFFFFFFFFull) {
+            printf("--aggregate %s: want a seed in 0 .. 4294967295. Exiting.\n", o->aggregate_spec);
+            return 1;
+        }
+        o->aggregate_seed = (uint32_t)seed;
+    }
     if (o->ilu0 && clashes(*o, "--ilu0")) return 1;
     if (o->rhs_path && !o->trsv_spec) {
         printf("--rhs needs --trsv lower|upper[:unit]. Exiting.\n");
@@ -696,6 +714,7 @@ static int validate_sampled(Options *o)
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
                      {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0}, {"--colour", o->colour_spec != nullptr},
                      {"--colour-natural", o->colour_natural}, {"--components", o->components},
+                     {"--aggregate", o->aggregate_spec != nullptr},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1339,6 +1358,7 @@ struct Result {
     std::vector<double> arg_idx, bfs_parents;      // --argreduce's indices, --bfs-parents' parents: 1-based, 0 for none
     std::vector<double> colours;                   // --colour's colours, 1-based
     std::vector<double> labels;                    // --components' labels, 1-based
+    std::vector<double> aggregates;                // --aggregate's aggregate ids, 1-based
     std::vector<double> trsv_x;                    // --trsv's solution
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
@@ -2134,6 +2154,41 @@ static int components_stage(const Options &, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--aggregate SEED` aggregates the graph of the final result's pattern (what --colour would colour; it
+// must be square; both directions of every stored entry count) on the device (pem_tiled_aggregate): the MIS(2) aggregation in the
+// order of the priorities SEED hashes.  One line reports aggregates, rounds and the time; --out then writes the aggregate ids
+// (Matrix-Market `array integer general`, 1-based) instead of the matrix.  The CSV row describes the product.
+static int aggregate_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("--aggregate: %s is %d x %d; an aggregation needs a square matrix. Exiting.\n", r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    DevBuf da;
+    if (!da.alloc(n, 4)) {
+        fprintf(stderr, "pemspgemm: --aggregate: device allocation of %zu aggregate ids failed\n", n);
+        return 2;
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    int64_t naggregates = 0;
+    int32_t rounds = 0;
+    auto c0 = Clock::now();
+    CHECK(pem_tiled_aggregate(ctx, src.t, 0, o.aggregate_seed, nullptr, (int32_t *)da.p, nullptr, &naggregates, &rounds));
+    const double aggregate_ms = ms_since(c0);
+    std::vector<int32_t> agg(n);
+    if (n && hipMemcpy(agg.data(), da.p, 4 * n, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    r->aggregates.resize(n);
+    for (size_t v = 0; v < n; ++v) r->aggregates[v] = (double)(agg[v] + 1);
+    printf("aggregate: seed %s of %s: %lld aggregates in %d rounds, %zu vertices, %.3fms\n", o.aggregate_spec, r->last_name,
+           (long long)naggregates, rounds, n, aggregate_ms);
+    return 0;
+}
+
 // `--spmm X.mtx` computes Y = R (+).(x) X on the device (pem_tiled_spmm), R the final result (C, the
 // sum of --add, or what --select kept) and X a Matrix-Market `array real general` file of R.cols rows (read as float with
 // --fp32); --out then writes Y (an array, R.rows x k) instead of the matrix.  The CSV row describes the product.
@@ -2257,7 +2312,7 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the colours of --colour, else the labels of --components, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
+// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the colours of --colour, else the labels of --components, else the aggregate ids of --aggregate, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
 // matrix: the sampled product of --sddmm, the final result when it is a tiling (its CSR export), or the plan's C (CSR export:
 // rows ascending, columns ascending).  The comment line says how the matrix came about.
 static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
@@ -2297,6 +2352,9 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     } else if (o.components) {
         rc = write_mm_array(o.out_path, "integer", "connected components of the pattern of C = A*B: the smallest vertex of every vertex's component (1-based)",
                             (int64_t)r->labels.size(), 1, r->labels, 1, false, "the ", "labels");
+    } else if (o.aggregate_spec) {
+        rc = write_mm_array(o.out_path, "integer", std::string("MIS(2) aggregates of the pattern of C = A*B, seed ") + o.aggregate_spec + " (1-based)",
+                            (int64_t)r->aggregates.size(), 1, r->aggregates, 1, false, "the ", "aggregates");
     } else if (o.argreduce_dim >= 0) {
         rc = write_mm_array(o.out_path, "integer", std::string("argreduce ") + o.argreduce_spec + " of C = A*B (1-based, 0: no entry)",
                             (int64_t)r->arg_idx.size(), 1, r->arg_idx, 1, false, "the ", "indices");
@@ -2363,6 +2421,7 @@ int main(int argc, char *argv[])
     if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
     if (!rc && o.colour_flag()) rc = colour_stage(o, ctx, &r);
     if (!rc && o.components) rc = components_stage(o, ctx, &r);
+    if (!rc && o.aggregate_spec) rc = aggregate_stage(o, ctx, &r);
     if (!rc && o.spmm_path) rc = spmm_stage(o, ctx, &r);
     if (!rc && o.sddmm_path) rc = sddmm_stage(o, ctx, &r);
     if (!rc) rc = save_stage(o, ctx, &r);
