@@ -987,6 +987,97 @@ pem_status pem_tiled_mis(pem_ctx *ctx, const pem_tiled *A, int distance /* 1 or 
 pem_status pem_tiled_aggregate(pem_ctx *ctx, const pem_tiled *A, int symmetric, uint32_t seed, const uint32_t *d_priority /* may be NULL */,
                                int32_t *d_aggregate /* n */, int32_t *d_root /* n, may be NULL */, int64_t *naggregates, int32_t *rounds);
 
+/* Krylov solvers: A x = b by preconditioned conjugate gradients (CG, for symmetric positive definite A)
+ * or right-preconditioned BiCGStab, on the device.  The whole loop runs on the context's stream; the host reads one small state block
+ * back every check_every iterations.
+ *   pem_krylov_create  A is square (n = A.rows).  precond: PEM_PRECOND_NONE (z = r), PEM_PRECOND_DIAG (z_i = minv_i * r_i, minv an
+ *       argument of every solve) or PEM_PRECOND_LU: F is a square tiling of A's size and value type with a stored diagonal -- usually
+ *       pem_tiled_ilu0(A) -- applied as pem_tiled_trsv(F, LOWER, unit_diag = 1, r, w) then pem_tiled_trsv(F, UPPER, 0, w, z).  The
+ *       call builds the trsv schedules of both triangles of F, so no solve builds one, and carves every work vector (CG: r, p, q,
+ *       with LU also z and the trsv work vector w; BiCGStab: r, rhat, p, v, s, t, with DIAG or LU also y and z, with LU also w), seven
+ *       partial slots of 1024 doubles and two 128-byte state blocks from the context's arena in one block.  May wait.
+ *     The object holds handles, not copies: every solve reads the current values of A and F, so pem_tiled_set_values* on A or
+ *       pem_tiled_set_values_from_ilu0 on F between solves needs nothing rebuilt.  A and F must outlive it (the rule of plans).
+ *     PEM_E_INVALID, before the device is touched (*out stays NULL): a null ctx, A, opts or out; rows != cols; an unknown method or
+ *       preconditioner; F missing under LU, or F given under another preconditioner; F of another size or value type; max_iters
+ *       < 0; check_every < 1; rtol or atol negative or NaN.  A row of F without a stored diagonal entry gives pem_tiled_trsv's
+ *       message (PEM_E_INVALID, after the schedule was built).
+ *   pem_krylov_solve  db, dx (in: the guess x0; out: x), d_minv (DIAG only; ignored otherwise) hold n values of the tiling's value
+ *       type on the device; d_history, if not NULL, max_iters + 1 doubles on the device.  Allocates nothing; ordered on the context's
+ *       stream; waits only for its state read-backs.  PEM_E_INVALID: a null ctx, solver or res; another context than create's; the fp64
+ *       form on an fp32 tiling or the reverse; a null db or dx where n > 0; d_minv null under DIAG; any two of db, dx, d_minv,
+ *       d_history overlapping.  n = 0 is legal: CONVERGED, 0 iterations, nothing launched.
+ *   pem_krylov_destroy  frees the object (its block goes back to the arena).
+ *
+ *   THE ORDER IS THE CONTRACT: x and the written part of d_history are fully determined, bit for bit.
+ *     Arithmetic.  VT = the tiling's value type.  The vector updates use no fma: every product and every sum below is rounded once
+ *       in VT, in the order the parentheses give.  All scalars (dots, alpha, beta, omega, rho, the threshold) are fp64, computed with
+ *       one IEEE operation per operator written; a scalar is rounded once to VT before it multiplies a vector.  A x is
+ *       pem_tiled_mxv's fma chain, the LU preconditioner pem_tiled_trsv's.
+ *     dot(u, v).  fp64 for both value types (an fp32 product is exact in fp64).  The partition depends on n alone: chunks of 4096
+ *       elements; G = min(ceil(n / 4096), 1024) workgroups of 256 threads; workgroup g takes the chunks g, g + G, ...; thread t of it
+ *       the elements chunk * 4096 + t + 256 j, j = 0 .. 15 (one element per load).  A thread keeps ONE chain acc = acc + u_i * v_i
+ *       from +0.0 in ascending i.  Lane l of a wave (t = 64 w + l) then does acc = acc + (acc of lane l xor m) for m = 32, 16, 8, 4,
+ *       2, 1; the four waves combine as (w0 + w1) + (w2 + w3): partial[g].  The total: thread t chains partial[t], partial[t + 256],
+ *       partial[t + 512], partial[t + 768] (those below G) from +0.0 in that order, then the same wave and workgroup tree.
+ *     Launch rules.  No floating-point atomics; no kernel reads what the same launch writes; nothing waits on another workgroup.  A
+ *       dot's partials are written by one kernel and totalled in the prologue of the next solver kernel, by every workgroup in the
+ *       same order; workgroup 0 alone writes the scalars and the state, into the state block the launch does not read.
+ *     Start (both methods).  q = A x; r_i = b_i - q_i; bb = dot(b, b); rr = dot(r, r); t1 = (rtol * rtol) * bb; t2 = atol * atol;
+ *       threshold = t1 > t2 ? t1 : t2; history[0] = rr.  CHECK(k): rr not finite -> NONFINITE; else rr <= threshold -> CONVERGED; else
+ *       k == max_iters -> MAX_ITERS; iters = k in all three.  The start ends with CHECK(0).
+ *     CG.  z = M^-1 r; rz = dot(r, z); p = z.  For k = 1, 2, ...:
+ *         q = A p; pq = dot(p, q); not (pq > 0) or pq not finite -> BREAKDOWN, iters = k - 1, x as after k - 1;
+ *         alpha = rz / pq; x_i = x_i + alpha * p_i; r_i = r_i - alpha * q_i; z = M^-1 r; rr = dot(r, r); rz' = dot(r, z);
+ *         history[k] = rr; CHECK(k); beta = rz' / rz; p_i = z_i + beta * p_i; rz = rz'.
+ *     BiCGStab, right-preconditioned.  rhat = r; rho' = rr; rho' == 0 or not finite -> BREAKDOWN (iters 0); p = r.  For k = 1, 2, ...:
+ *         y = M^-1 p; v = A y; rv = dot(rhat, v); rv == 0 or not finite -> BREAKDOWN (iters k - 1, x as after k - 1);
+ *         alpha = rho' / rv; s_i = r_i - alpha * v_i; ss = dot(s, s);
+ *         ss <= threshold -> x_i = x_i + alpha * y_i; history[k] = ss; rr = ss; CONVERGED, iters = k;
+ *         z = M^-1 s; t = A z; ts = dot(t, s); tt = dot(t, t); not (tt > 0) or tt not finite -> BREAKDOWN (iters k - 1, x as after k - 1);
+ *         omega = ts / tt; x_i = (x_i + alpha * y_i) + omega * z_i; r_i = s_i - omega * t_i; rr = dot(r, r); rho = rho';
+ *         rho' = dot(rhat, r); history[k] = rr; CHECK(k); omega == 0 -> BREAKDOWN (iters k); rho' == 0 or not finite -> BREAKDOWN
+ *         (iters k); beta = (rho' / rho) * (alpha / omega); p_i = r_i + beta * (p_i - omega * v_i).
+ *     The preconditioner.  NONE: z = r, no copy.  DIAG: z_i = minv_i * r_i, one product in VT.  LU: the two solves above.
+ *     Stopping.  The decision is taken on the device.  Once a status is set every later solver kernel of the call leaves x, r, p,
+ *       the scalars and d_history untouched (the mxv and trsv launches in between write scratch vectors only).  The host enqueues
+ *       min(check_every, what is left of max_iters) iterations, reads the 128-byte state block back (one read-back) and stops when
+ *       the status is set: x, iters, status and the written part of d_history are identical for every check_every; entries of
+ *       d_history after iters are not written, entries 0 .. iters all are.  With E = min(max_iters, check_every * readbacks) the iterations enqueued and T the launches of the
+ *       two trsv calls (pem_tiled_trsv_info): res->readbacks = max(1, ceil(K / check_every)), K the iteration during which the status
+ *       was set (0: at the start); res->launches = S + E * I, the start S = 3 (CG with LU: 4 + T) and an iteration I = 4 for CG
+ *       (LU: 5 + T) and 7 for BiCGStab (LU: 7 + 2 T), the mxv launches included.
+ *     The solver's own kernels per iteration (kernel_stats names krylov_*): CG 3 (krylov_dot, krylov_cg_update, krylov_cg_p), with
+ *       LU 4 (a second krylov_dot after the solve); BiCGStab 5 (krylov_dot, krylov_bi_s, krylov_bi_ts, krylov_bi_xr, krylov_bi_p).
+ *   res: iters, status (a PEM_KRYLOV_* value), bb, rr (the last residual norm squared the recurrence computed), threshold,
+ *       readbacks, launches.  A non-converged status is not an error: the call returns PEM_OK.
+ *   Not covered: GMRES and other long-recurrence methods; symmetric Gauss-Seidel, polynomial and AMG preconditioners; left
+ *       preconditioning; several right-hand sides; graph capture of the iteration; a pem_mgpu_* path; mixed precision beyond the
+ *       fp64 scalars. */
+enum { PEM_KRYLOV_CG = 0, PEM_KRYLOV_BICGSTAB = 1 };
+enum { PEM_PRECOND_NONE = 0, PEM_PRECOND_DIAG = 1, PEM_PRECOND_LU = 2 };
+enum { PEM_KRYLOV_CONVERGED = 0, PEM_KRYLOV_MAX_ITERS = 1, PEM_KRYLOV_BREAKDOWN = 2, PEM_KRYLOV_NONFINITE = 3 };
+typedef struct {
+    int method, precond;
+    int64_t max_iters, check_every;
+    double rtol, atol;
+} pem_krylov_opts;
+typedef struct {
+    int64_t iters;
+    int status;
+    double bb, rr, threshold;
+    int64_t readbacks, launches;
+} pem_krylov_result;
+typedef struct pem_krylov pem_krylov;
+pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_tiled *F /* PRECOND_LU, else NULL */,
+                             pem_krylov **out);
+pem_status pem_krylov_solve(pem_ctx *ctx, pem_krylov *K, const double *db, double *dx /* in: x0, out: x */,
+                            const double *d_minv /* PRECOND_DIAG, else NULL */, double *d_history /* max_iters + 1 doubles or NULL */,
+                            pem_krylov_result *res);
+pem_status pem_krylov_solve_f32(pem_ctx *ctx, pem_krylov *K, const float *db, float *dx, const float *d_minv, double *d_history,
+                                pem_krylov_result *res);
+pem_status pem_krylov_destroy(pem_ctx *ctx, pem_krylov *K);
+
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only
  * *nnz is set.  The fp64 form refuses an fp32 tiling and vice versa (PEM_E_INVALID).  Waits. */

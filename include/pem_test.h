@@ -69,6 +69,11 @@ pem_status pem_test_frontier_line_flags(pem_ctx *ctx, uint8_t *host_dst, int64_t
  * whatever its width; on = 0 (default) restores the merged launch of narrow levels.  The results are bit for bit the same. */
 pem_status pem_test_trsv_split(pem_ctx *ctx, int on);
 
+/* The Krylov solvers' dot product (pem_krylov_solve, pem_spgemm.h) on its own: *host_out = dot(du, dv) of n values of value_bytes
+ * (4 or 8) on the device, by the partial kernel and the total exactly as the solver runs them, so the reduction can be tested at
+ * its boundaries without a matrix of that size.  Carves 8200 bytes from the context's arena; waits. */
+pem_status pem_test_krylov_dot(pem_ctx *ctx, int64_t n, int value_bytes, const void *du, const void *dv, double *host_out);
+
 #ifdef __cplusplus
 }
 #endif

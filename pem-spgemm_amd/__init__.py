@@ -66,7 +66,14 @@ ABI_SYMBOLS = [
     "pem_tiled_ilu0", "pem_tiled_set_values_from_ilu0", "pem_tiled_ilu0_info",
     "pem_tiled_colour", "pem_colour_order", "pem_tiled_components",
     "pem_tiled_mis", "pem_tiled_aggregate",
+    "pem_krylov_create", "pem_krylov_solve", "pem_krylov_solve_f32", "pem_krylov_destroy", "pem_test_krylov_dot",
 ]
+
+# PEM_KRYLOV_CG / _BICGSTAB, PEM_PRECOND_NONE / _DIAG / _LU and the PEM_KRYLOV_* statuses (include/pem_spgemm.h, INTEGRATION.md
+# section 3zc), by value
+KRYLOV_METHODS = ("cg", "bicgstab")
+KRYLOV_PRECONDS = ("none", "diag", "lu")
+KRYLOV_STATUS = ("converged", "max_iters", "breakdown", "nonfinite")
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
 EWISE_PATTERNS = dict(union=0, intersect=1)
@@ -150,6 +157,16 @@ class Ilu0Info(C.Structure):
                 ("zero_pivots", C.c_int64), ("first_zero_pivot_row", C.c_int64)]
 
 
+class KrylovOpts(C.Structure):
+    _fields_ = [("method", C.c_int), ("precond", C.c_int), ("max_iters", C.c_int64), ("check_every", C.c_int64), ("rtol", C.c_double),
+                ("atol", C.c_double)]
+
+
+class KrylovResult(C.Structure):
+    _fields_ = [("iters", C.c_int64), ("status", C.c_int), ("bb", C.c_double), ("rr", C.c_double), ("threshold", C.c_double),
+                ("readbacks", C.c_int64), ("launches", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [("step1_ms", C.c_double), ("step2_ms", C.c_double), ("step3_ms", C.c_double), ("spgemm_wall_ms", C.c_double),
                 ("export_ms", C.c_double)]
@@ -182,6 +199,14 @@ def lib():
         L.pem_tiled_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.pem_tiled_mis.restype = L.pem_tiled_aggregate.restype = C.c_int
+        # (ctx, A, opts, F, out), (ctx, K, db, dx, d_minv, d_history, res), (ctx, K) and the dot hook (ctx, n, value_bytes, du, dv, out)
+        L.pem_krylov_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KrylovOpts), C.c_void_p, C.POINTER(C.c_void_p)]
+        L.pem_krylov_solve.argtypes = L.pem_krylov_solve_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                         C.c_void_p, C.POINTER(KrylovResult)]
+        L.pem_krylov_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.pem_test_krylov_dot.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.pem_krylov_create.restype = L.pem_krylov_solve.restype = L.pem_krylov_solve_f32.restype = C.c_int
+        L.pem_krylov_destroy.restype = L.pem_test_krylov_dot.restype = C.c_int
         _lib = L
     return _lib
 
@@ -892,6 +917,37 @@ class Tiled:
         work = self.trsv(b, "lower", unit_diag=True, out=work)
         return self.trsv(work, "upper", out=out)
 
+    def solve(self, b, method="cg", precond=None, x=None, max_iters=1000, check_every=8, rtol=1e-8, atol=0.0, history=False):
+        """A x = b in one call: makes a Krylov solver, solves, closes it; returns (x, info) as
+        Krylov.solve.  precond: None, "jacobi" (minv = 1 / self.select("diag", 0).reduce("plus"), the DIAG preconditioner), "ilu0"
+        (makes and closes its own factor), a tiling (an LU factor), or a device tensor (minv itself)."""
+        minv, F, own = None, None, None
+        if isinstance(precond, str):
+            if precond == "jacobi":
+                D = self.select("diag", 0)
+                try:
+                    minv = 1 / D.reduce("plus")
+                finally:
+                    D.close()
+                import torch
+                torch.cuda.current_stream(minv.device).synchronize()   # (torch's division; minv is read on the context's stream)
+                precond = "diag"
+            elif precond == "ilu0":
+                precond = own = self.ilu0()
+            elif precond != "none":
+                raise ValueError(f"solve: unknown precond {precond!r}; None, 'none', 'jacobi', 'ilu0', a tiling or a device tensor")
+        elif hasattr(precond, "data_ptr"):
+            minv, precond = precond, "diag"
+        try:
+            K = Krylov(self, method=method, precond=precond, max_iters=max_iters, check_every=check_every, rtol=rtol, atol=atol)
+            try:
+                return K.solve(b, x=x, minv=minv, history=history)
+            finally:
+                K.close()
+        finally:
+            if own is not None:
+                own.close()
+
     def _bytes(self, fn, name, v, n):
         """the device pointer of a contiguous torch.bool / torch.uint8 tensor of n bytes on the context's device; None passes as NULL"""
         if v is None:
@@ -1171,6 +1227,95 @@ class Tiled:
             self.close()
         except Exception:
             pass
+
+
+class Krylov:
+    """pem_krylov: preconditioned CG or BiCGStab on a square tiling A, the whole loop on the context's
+    stream.  method: one of KRYLOV_METHODS.  precond: None or "none"; "diag" (every solve then takes minv); or a tiling F, an LU
+    factor such as A.ilu0(), applied by two trsv.  The host reads a 128-byte state block back every check_every iterations; x, iters,
+    status and the history do not depend on check_every.  Stops at rr <= max(rtol^2 * bb, atol^2), after max_iters iterations, on
+    a breakdown or on a residual that is not finite.  The object keeps A and F alive and reads their current values in every solve.
+    Wrong arguments raise ValueError; what the library refuses raises PemError."""
+
+    def __init__(self, A, method="cg", precond=None, max_iters=1000, check_every=8, rtol=1e-8, atol=0.0):
+        if method not in KRYLOV_METHODS:
+            raise ValueError(f"Krylov: unknown method {method!r}; one of {KRYLOV_METHODS}")
+        F = None
+        if precond is None or precond == "none":
+            pc = 0
+        elif precond == "diag":
+            pc = 1
+        elif isinstance(precond, Tiled):
+            pc, F = 2, precond
+        else:
+            raise ValueError(f"Krylov: precond must be None, 'none', 'diag' or a tiling (an LU factor), not {precond!r}")
+        for name, v in (("max_iters", max_iters), ("check_every", check_every)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not -2 ** 63 <= int(v) < 2 ** 63:
+                raise ValueError(f"Krylov: {name} must be an integer, not {v!r}")
+        for name, v in (("rtol", rtol), ("atol", atol)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise ValueError(f"Krylov: {name} must be a real number, not {v!r}")
+        self.A, self.F, self.ctx = A, F, A.ctx
+        self.method, self.precond, self.max_iters, self.check_every = method, KRYLOV_PRECONDS[pc], int(max_iters), int(check_every)
+        opts = KrylovOpts(KRYLOV_METHODS.index(method), pc, int(max_iters), int(check_every), float(rtol), float(atol))
+        self._h = C.c_void_p()
+        _check(lib().pem_krylov_create(self.ctx._h, A._h, C.byref(opts), F._h if F is not None else None, C.byref(self._h)))
+
+    def solve(self, b, x=None, minv=None, history=False):
+        """(x, info).  b: a contiguous device torch tensor of A's dtype with A.rows entries; x: the guess, overwritten with the
+        solution and returned (None: a zero guess); minv: the inverse diagonal, required under "diag" and refused otherwise; history:
+        True records the squared residual norm of every iteration.  info: iters, status (one of KRYLOV_STATUS), status_code, bb, rr,
+        threshold, rnorm = sqrt(rr), readbacks, launches and, with history=True, history -- a float64 device tensor of iters + 1
+        entries.  A status other than "converged" is no error.  Waits for its read-backs only; torch reads x with no extra sync on a
+        context created on torch's stream."""
+        import torch
+        A = self.A
+        pb = A._vector("Krylov.solve", "b", b, A.rows)
+        if x is None:
+            x = torch.zeros(A.rows, dtype=b.dtype, device=b.device)
+            if A.rows:
+                torch.cuda.current_stream(b.device).synchronize()   # (torch's fill; x is read on the context's stream)
+        px = A._vector("Krylov.solve", "x", x, A.rows)
+        if (minv is not None) != (self.precond == "diag"):
+            raise ValueError("Krylov.solve: minv is required with precond='diag' and refused without it")
+        pm = A._vector("Krylov.solve", "minv", minv, A.rows) if minv is not None else None
+        hist = None
+        if hasattr(history, "data_ptr"):   # the caller's buffer: max_iters + 1 float64 on the device; entries past iters stay as they are
+            hist = history
+            if not hist.is_cuda or hist.dtype != torch.float64 or hist.numel() != self.max_iters + 1 or not hist.is_contiguous():
+                raise ValueError(f"Krylov.solve: want a contiguous device tensor of {self.max_iters + 1} float64 values for history")
+        elif history:
+            hist = torch.empty(self.max_iters + 1, dtype=torch.float64, device=b.device)
+        res = KrylovResult()
+        fn = lib().pem_krylov_solve_f32 if A.value_bytes == 4 else lib().pem_krylov_solve
+        _check(fn(self.ctx._h, self._h, pb, px, pm, C.c_void_p(hist.data_ptr()) if hist is not None else None, C.byref(res)))
+        info = dict(iters=int(res.iters), status=KRYLOV_STATUS[res.status], status_code=int(res.status), bb=res.bb, rr=res.rr,
+                    threshold=res.threshold, rnorm=float(np.sqrt(res.rr)) if res.rr >= 0 else float("nan"), readbacks=int(res.readbacks),
+                    launches=int(res.launches))
+        if hist is not None:
+            info["history"] = hist[:info["iters"] + 1]
+        return x, info
+
+    def close(self):
+        if self._h:
+            lib().pem_krylov_destroy(self.ctx._h, self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def krylov_dot(ctx, u, v):
+    """test hook (pem_test.h): the solvers' dot product of two contiguous device tensors of one dtype (float32 / float64), as a float"""
+    if u.dtype != v.dtype or u.numel() != v.numel() or str(u.dtype) not in ("torch.float32", "torch.float64"):
+        raise ValueError("krylov_dot: want two device tensors of one length and dtype (float32 or float64)")
+    out = C.c_double()
+    _check(lib().pem_test_krylov_dot(ctx._h, u.numel(), u.element_size(), C.c_void_p(u.data_ptr() or 1), C.c_void_p(v.data_ptr() or 1),
+                                     C.byref(out)))
+    return out.value
 
 
 def flop_count(ctx, A, B):

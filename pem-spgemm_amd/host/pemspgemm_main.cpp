@@ -111,6 +111,8 @@ struct Options {
     bool sampled_bt = false, triangles = false;                     // --triangles: see sampled_stage
     const char *trsv_spec = nullptr, *rhs_path = nullptr;           // --trsv lower|upper[:unit] [--rhs b.mtx]: see trsv_stage
     bool ilu0 = false;                                              // --ilu0: see ilu0_stage
+    const char *solve_spec = nullptr, *precond_name = nullptr;      // --solve cg|bicgstab [--precond none|jacobi|ilu0]: see solve_stage
+    const char *rtol_spec = nullptr, *max_iters_spec = nullptr;     // --rtol R, --max-iters N
     const char *colour_spec = nullptr;                              // --colour SEED: see colour_stage
     bool colour_natural = false;                                    // --colour-natural: equal priorities
     bool components = false;                                        // --components: see components_stage
@@ -146,6 +148,10 @@ struct Options {
     int trsv_uplo = -1;                                   // PEM_TRSV_LOWER / PEM_TRSV_UPPER
     bool trsv_unit = false;
     std::vector<double> rhs;                              // --rhs' values
+    int solve_method = -1;                                // PEM_KRYLOV_CG / PEM_KRYLOV_BICGSTAB
+    int solve_precond = 0;                                // 0 none, 1 jacobi, 2 ilu0
+    double solve_rtol = 1e-8;
+    long long solve_max_iters = 1000;
     uint32_t colour_seed = 0;
     uint32_t aggregate_seed = 0;
     const char *colour_flag() const { return colour_spec ? "--colour" : colour_natural ? "--colour-natural" : nullptr; }
@@ -169,7 +175,8 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--dup", &o->dup_name}, {"--hstack", &o->stack_paths[0]}, {"--vstack", &o->stack_paths[1]},
                   {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path},
                   {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}, {"--colour", &o->colour_spec},
-                  {"--aggregate", &o->aggregate_spec}};
+                  {"--aggregate", &o->aggregate_spec}, {"--solve", &o->solve_spec}, {"--precond", &o->precond_name},
+                  {"--rtol", &o->rtol_spec}, {"--max-iters", &o->max_iters_spec}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -214,6 +221,7 @@ static const struct ClashRule {
     {"--argreduce", {"--gpus", "--power", "--reduce", "--bfs", "--spmm", "--sddmm"}, ""},
     {"--bfs-parents", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
     {"--trsv", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--spmm", "--sddmm"}, ""},
+    {"--solve", {"--gpus", "--power", "--trsv", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--spmm", "--sddmm"}, ""},
     {"--colour", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
     {"--colour-natural", {"--gpus", "--power", "--reduce", "--bfs", "--argreduce", "--bfs-parents", "--trsv", "--spmm", "--sddmm"}, ""},
     {"--components",
@@ -491,9 +499,62 @@ static int validate_vectors(Options *o)
         o->aggregate_seed = (uint32_t)seed;
     }
     if (o->ilu0 && clashes(*o, "--ilu0")) return 1;
-    if (o->rhs_path && !o->trsv_spec) {
+    if (o->rhs_path && !o->trsv_spec && !o->solve_spec) {
         printf("--rhs needs --trsv lower|upper[:unit]. Exiting.\n");
         return 1;
+    }
+    if (!o->solve_spec && (o->precond_name || o->rtol_spec || o->max_iters_spec)) {
+        printf("--precond / --rtol / --max-iters need --solve cg|bicgstab. Exiting.\n");
+        return 1;
+    }
+    if (o->solve_spec) {
+        if (clashes(*o, "--solve")) return 1;
+        for (const char *other : {o->colour_flag(), o->components ? "--components" : nullptr, o->aggregate_spec ? "--aggregate" : nullptr})
+            if (other) {
+                printf("--solve does not combine with %s. Exiting.\n", other);
+                return 1;
+            }
+        o->solve_method = !strcmp(o->solve_spec, "cg") ? PEM_KRYLOV_CG : !strcmp(o->solve_spec, "bicgstab") ? PEM_KRYLOV_BICGSTAB : -1;
+        if (o->solve_method < 0) {
+            printf("--solve %s: unknown method (cg, bicgstab). Exiting.\n", o->solve_spec);
+            return 1;
+        }
+        if (o->precond_name) {
+            static const char *const names[] = {"none", "jacobi", "ilu0"};
+            o->solve_precond = -1;
+            for (int k = 0; k < 3; ++k)
+                if (!strcmp(o->precond_name, names[k])) o->solve_precond = k;
+            if (o->solve_precond < 0) {
+                printf("--precond %s: unknown preconditioner (none, jacobi, ilu0). Exiting.\n", o->precond_name);
+                return 1;
+            }
+        }
+        if (o->rtol_spec) {
+            char *end = nullptr;
+            o->solve_rtol = strtod(o->rtol_spec, &end);
+            if (end == o->rtol_spec || *end != '\0' || !(o->solve_rtol >= 0.0)) {
+                printf("--rtol %s: want a number >= 0. Exiting.\n", o->rtol_spec);
+                return 1;
+            }
+        }
+        if (o->max_iters_spec) {
+            char *end = nullptr;
+            o->solve_max_iters = strtoll(o->max_iters_spec, &end, 10);
+            if (end == o->max_iters_spec || *end != '\0' || o->solve_max_iters < 0) {
+                printf("--max-iters %s: want an integer >= 0. Exiting.\n", o->max_iters_spec);
+                return 1;
+            }
+        }
+        if (!o->rhs_path) {
+            printf("--solve %s needs --rhs b.mtx. Exiting.\n", o->solve_spec);
+            return 1;
+        }
+        int64_t n = 0, k = 0;
+        if (read_dense_array("--rhs", o->rhs_path, &n, &k, &o->rhs)) return 1;
+        if (k != 1) {
+            printf("--rhs %s: an array of %lld columns, not of one. Exiting.\n", o->rhs_path, (long long)k);
+            return 1;
+        }
     }
     if (o->trsv_spec) {
         if (clashes(*o, "--trsv")) return 1;
@@ -714,7 +775,7 @@ static int validate_sampled(Options *o)
                      {"--spmm", o->spmm_path != nullptr}, {"--sddmm", o->sddmm_path != nullptr}, {"--cache", o->cache_dir != nullptr},
                      {"--trsv", o->trsv_spec != nullptr}, {"--ilu0", o->ilu0}, {"--colour", o->colour_spec != nullptr},
                      {"--colour-natural", o->colour_natural}, {"--components", o->components},
-                     {"--aggregate", o->aggregate_spec != nullptr},
+                     {"--aggregate", o->aggregate_spec != nullptr}, {"--solve", o->solve_spec != nullptr},
                      {"the 2nd argument 1 (the sorted COO files; use --out)", o->save}};
     for (const auto &f : plan_only)
         if (f.present) {
@@ -1360,6 +1421,7 @@ struct Result {
     std::vector<double> labels;                    // --components' labels, 1-based
     std::vector<double> aggregates;                // --aggregate's aggregate ids, 1-based
     std::vector<double> trsv_x;                    // --trsv's solution
+    std::vector<double> solve_x;                   // --solve's solution
     int64_t spmm_ny = 0;
     Csr sd_csr;               // --sddmm: the sampled product, which serves --out and the COO files
     int rc = 0;               // 2 once a result file could not be written (the run still finishes)
@@ -1973,6 +2035,83 @@ static int trsv_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
+// `--solve cg|bicgstab --rhs b.mtx [--precond none|jacobi|ilu0] [--rtol R] [--max-iters N]` solves
+// R x = b on the device (pem_krylov_*), R the final result (what --reduce would fold; it must be square), from a zero guess.
+// jacobi: the inverse of R's diagonal (pem_tiled_select + pem_tiled_reduce, inverted on the host in the value type); ilu0: the
+// stage's own pem_tiled_ilu0(R).  One line reports the time, the iterations, the status and sqrt(rr / bb); --out then writes x
+// (Matrix-Market array) instead of the matrix.  A status other than converged is reported, not refused.  The CSV row describes the
+// product.
+static int solve_stage(const Options &o, pem_ctx *ctx, Result *r)
+{
+    Operand src;
+    CHECK(src.open(ctx, *r));
+    const pem_tiled_info &si = src.info;
+    CHECK(pem_tiled_get_info(src.t, &src.info));
+    if (si.rows != si.cols) {
+        printf("--solve %s: %s is %d x %d; a Krylov solver needs a square matrix. Exiting.\n", o.solve_spec, r->last_name, si.rows, si.cols);
+        return 1;
+    }
+    const size_t n = (size_t)si.rows;
+    if (o.rhs.size() != n) {
+        printf("--rhs %s: the vector has %zu values; %s has %d rows. Exiting.\n", o.rhs_path, o.rhs.size(), r->last_name, si.rows);
+        return 1;
+    }
+    const std::vector<double> zeros(n, 0.0);
+    DevBuf db, dx, dm;
+    if (!db.upload(o.rhs, n, o.fp32) || !dx.upload(zeros, n, o.fp32)) {
+        fprintf(stderr, "pemspgemm: --solve: device allocation of %zu values failed\n", n);
+        return 2;
+    }
+    CHECK(pem_ctx_synchronize(ctx));
+    auto t0 = Clock::now();
+    Tiled F;
+    if (o.solve_precond == 1) {
+        Tiled D;
+        CHECK(pem_tiled_select(ctx, src.t, PEM_SELECT_DIAG, 0.0, out(ctx, D)));
+        if (!dm.alloc(n, o.fp32 ? 4 : 8)) return 2;
+        CHECK(o.fp32 ? pem_tiled_reduce_f32(ctx, D.get(), PEM_BINOP_PLUS, PEM_REDUCE_ROWS, (float *)dm.p, 0)
+                     : pem_tiled_reduce(ctx, D.get(), PEM_BINOP_PLUS, PEM_REDUCE_ROWS, (double *)dm.p, 0));
+        CHECK(pem_ctx_synchronize(ctx));
+        std::vector<double> d;
+        if (!dm.download(&d, n, o.fp32)) return 2;
+        for (double &v : d) v = o.fp32 ? (double)(1.0f / (float)v) : 1.0 / v;
+        DevBuf inv;
+        if (!inv.upload(d, n, o.fp32)) return 2;
+        std::swap(dm.p, inv.p);
+    } else if (o.solve_precond == 2) {
+        if (pem_tiled_ilu0(ctx, src.t, out(ctx, F)) != PEM_OK) {
+            printf("--precond ilu0: %s. Exiting.\n", pem_last_error());
+            return 1;
+        }
+    }
+    const double setup_ms = ms_since(t0);
+    pem_krylov_opts ko;
+    ko.method = o.solve_method;
+    ko.precond = o.solve_precond == 1 ? PEM_PRECOND_DIAG : o.solve_precond == 2 ? PEM_PRECOND_LU : PEM_PRECOND_NONE;
+    ko.max_iters = o.solve_max_iters;
+    ko.check_every = 8;
+    ko.rtol = o.solve_rtol;
+    ko.atol = 0.0;
+    pem_krylov *K = nullptr;
+    if (pem_krylov_create(ctx, src.t, &ko, F.get(), &K) != PEM_OK) {
+        printf("--solve %s: %s. Exiting.\n", o.solve_spec, pem_last_error());
+        return 1;
+    }
+    pem_krylov_result res;
+    t0 = Clock::now();
+    const pem_status st = o.fp32 ? pem_krylov_solve_f32(ctx, K, (const float *)db.p, (float *)dx.p, (const float *)dm.p, nullptr, &res)
+                                 : pem_krylov_solve(ctx, K, (const double *)db.p, (double *)dx.p, (const double *)dm.p, nullptr, &res);
+    const double solve_ms = ms_since(t0);
+    pem_krylov_destroy(ctx, K);
+    CHECK(st);
+    if (!dx.download(&r->solve_x, n, o.fp32)) return 2;
+    static const char *const status[] = {"converged", "max_iters", "breakdown", "nonfinite"};
+    printf("solve: %s with %s of %s: solve %.3fms (preconditioner %.3fms), %lld iterations, %s, relative residual %.3e, %lld read-backs, host sum %.17g\n",
+           o.solve_spec, o.precond_name ? o.precond_name : "none", r->last_name, solve_ms, setup_ms, (long long)res.iters, status[res.status],
+           sqrt(res.rr / res.bb), (long long)res.readbacks, sum_of(r->solve_x));
+    return 0;
+}
+
 // `--bfs SRC` runs a breadth-first search from the 1-based vertex SRC over the pattern of the final
 // result (what --reduce would fold; it must be square) on the device (pem_tiled_bfs): a stored entry (i, j) is an edge i -> j.
 // One line reports depth, reached and the time; --out then writes the levels (Matrix-Market `array integer general`, -1 for
@@ -2312,7 +2451,7 @@ static int save_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--out <file>`: x of --trsv, else the levels of --bfs, else the parents of --bfs-parents, else the colours of --colour, else the labels of --components, else the aggregate ids of --aggregate, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
+// `--out <file>`: x of --trsv, else x of --solve, else the levels of --bfs, else the parents of --bfs-parents, else the colours of --colour, else the labels of --components, else the aggregate ids of --aggregate, else the indices of --argreduce, else Y of --spmm, else the vector of --reduce (Matrix-Market dense arrays), else the
 // matrix: the sampled product of --sddmm, the final result when it is a tiling (its CSR export), or the plan's C (CSR export:
 // rows ascending, columns ascending).  The comment line says how the matrix came about.
 static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result *r)
@@ -2340,6 +2479,9 @@ static int out_stage(const Options &o, pem_ctx *ctx, const Operands &in, Result 
     if (o.trsv_uplo >= 0) {
         rc = write_mm_array(o.out_path, "real", std::string("x of T x = b, T the ") + o.trsv_spec + " triangle of C = A*B" + (o.rhs_path ? std::string(", b ") + o.rhs_path : std::string(", b all ones")),
                             (int64_t)r->trsv_x.size(), 1, r->trsv_x, 1, o.fp32, "the ", "solution");
+    } else if (o.solve_method >= 0) {
+        rc = write_mm_array(o.out_path, "real", std::string("x of C x = b by ") + o.solve_spec + ", C = A*B, b " + o.rhs_path, (int64_t)r->solve_x.size(), 1,
+                            r->solve_x, 1, o.fp32, "the ", "solution");
     } else if (o.bfs_spec) {
         rc = write_mm_array(o.out_path, "integer", "bfs levels from " + std::to_string(o.bfs_src), (int64_t)r->bfs_levels.size(), 1, r->bfs_levels, 1,
                             false, "the ", "levels");
@@ -2416,6 +2558,7 @@ int main(int argc, char *argv[])
     if (!rc && o.ilu0) rc = ilu0_stage(o, ctx, &r);
     if (!rc && o.reduce_dim >= 0) rc = reduce_stage(o, ctx, &r);
     if (!rc && o.trsv_uplo >= 0) rc = trsv_stage(o, ctx, &r);
+    if (!rc && o.solve_method >= 0) rc = solve_stage(o, ctx, &r);
     if (!rc && o.bfs_spec) rc = bfs_stage(o, ctx, &r);
     if (!rc && o.argreduce_dim >= 0) rc = argreduce_stage(o, ctx, &r);
     if (!rc && o.bfs_parents_spec) rc = bfs_parents_stage(o, ctx, &r);
