@@ -1051,7 +1051,13 @@ pem_status pem_tiled_aggregate(pem_ctx *ctx, const pem_tiled *A, int symmetric, 
  *       LU 4 (a second krylov_dot after the solve); BiCGStab 5 (krylov_dot, krylov_bi_s, krylov_bi_ts, krylov_bi_xr, krylov_bi_p).
  *   res: iters, status (a PEM_KRYLOV_* value), bb, rr (the last residual norm squared the recurrence computed), threshold,
  *       readbacks, launches.  A non-converged status is not an error: the call returns PEM_OK.
- *   Not covered: GMRES and other long-recurrence methods; symmetric Gauss-Seidel, polynomial and AMG preconditioners; left
+ *   pem_krylov_create_amg  (declared with pem_amg_* below) the same solver with PEM_PRECOND_AMG: z = one V-cycle of the hierarchy M,
+ *       pem_amg_apply on the solver's stream, where LU runs its two solves -- z is read from an array, every formula above holds with
+ *       T replaced by V = pem_amg_info::launches (CG: S = 4 + V, I = 5 + V; BiCGStab: S = 3, I = 7 + 2 V), and the trsv work vector w
+ *       is not carved.  opts->precond must be PEM_PRECOND_AMG; M must have been created on the same context and the same A handle
+ *       (PEM_E_INVALID otherwise).  The solver holds M as a handle: pem_amg_refresh between solves needs nothing rebuilt; M must outlive
+ *       it.  pem_krylov_create itself refuses precond = 3.
+ *   Not covered: GMRES and other long-recurrence methods; symmetric Gauss-Seidel and polynomial preconditioners; left
  *       preconditioning; several right-hand sides; graph capture of the iteration; a pem_mgpu_* path; mixed precision beyond the
  *       fp64 scalars. */
 enum { PEM_KRYLOV_CG = 0, PEM_KRYLOV_BICGSTAB = 1 };
@@ -1077,6 +1083,84 @@ pem_status pem_krylov_solve(pem_ctx *ctx, pem_krylov *K, const double *db, doubl
 pem_status pem_krylov_solve_f32(pem_ctx *ctx, pem_krylov *K, const float *db, float *dx, const float *d_minv, double *d_history,
                                 pem_krylov_result *res);
 pem_status pem_krylov_destroy(pem_ctx *ctx, pem_krylov *K);
+
+/* Aggregation algebraic multigrid: a hierarchy A_0 = A, A_{l+1} = R_l (A_l P_l) built from MIS(2)
+ * aggregates, one V-cycle with weighted-Jacobi smoothing as z = M r, and that cycle as the preconditioner of pem_krylov_*.
+ *   pem_amg_create  A is square, of either value type VT, with every diagonal entry stored.  THE SETUP IS A SEQUENCE OF PUBLIC
+ *       CALLS, so every level is bit for bit what a caller gets by making them.  Level 0 is A itself, held as a handle and not copied
+ *       (the rule of plans).  At level l, with n_l rows:
+ *         weights    w_i = (VT)omega / d_i, d_i the stored (i, i) value of A_l: omega rounded once to VT, one division.  A row of any
+ *                    A_l without a stored diagonal entry is PEM_E_INVALID (the message names the level, the first such row, 1-based,
+ *                    and their number).  A stored zero is legal: an infinite weight, and a solver stops on what is not finite
+ *                    (NONFINITE, or BREAKDOWN where a dot product is tested first).
+ *         stop       level l is the coarsest when l + 1 == max_levels, or n_l <= coarse_size, or the aggregation below returns
+ *                    naggregates == n_l (nothing coarsens: a diagonal matrix).
+ *         aggregate  pem_tiled_aggregate(A_l, symmetric, seed, NULL).  An entry of -1 (a false symmetric = 1 promise) is
+ *                    PEM_E_INVALID; the message says to pass symmetric = 0.
+ *         P_t        the n_l x naggregates tiling with a 1 at (v, agg[v]): pem_tiled_from_coo_device of triplets made on the device.
+ *         P_l        smooth = 0: P_t.  smooth = 1: T = A_l P_t (pem_cplan_create, pem_spgemm, pem_tiled_from_cplan);
+ *                    W = pem_tiled_scale(T, PEM_BINOP_TIMES, d_row = w, NULL); P_l = pem_tiled_ewise(P_t, W, PEM_EWISE_UNION,
+ *                    PEM_BINOP_PLUS, alpha = 1, beta = -1) = (I - omega D^-1 A_l) P_t.
+ *         A_{l+1}    R_l = pem_tiled_transpose(P_l); AP = A_l P_l; A_{l+1} = R_l AP, each a plan under plus_times with default
+ *                    options and pem_tiled_from_cplan.  Structural zeros stay entries, so they are edges of the next aggregation.
+ *       All device memory comes from the context's arena; the work vectors of all levels (w and the product vector q per level, x and
+ *       b below level 0) are one block.  With refreshable = 0 the plans and T, W, AP (and P_t when smoothed) are destroyed before the
+ *       call returns; with refreshable = 1 they are kept for pem_amg_refresh.  Waits.
+ *       PEM_E_INVALID, before the device is touched (*out stays NULL): a null argument; rows != cols; smooth, symmetric or refreshable
+ *       not 0 / 1; max_levels outside 1 .. PEM_AMG_MAX_LEVELS; coarse_size, sweeps or coarse_sweeps < 1; omega not positive and finite.
+ *   pem_amg_refresh  after new values on A (same pattern): the aggregates and every pattern stay.  Level by level: w again, then step 3
+ *       of each plan and the matching pem_tiled_set_values_from_cplan / _from_scale / _from_ewise / _from_transpose.  The result
+ *       equals a fresh pem_amg_create on the new values, array for array.  Stream-ordered, reads nothing back; the first refresh may
+ *       allocate (the refresh maps of ewise and transpose), later ones allocate nothing.  PEM_E_STATE on a hierarchy made with
+ *       refreshable = 0.
+ *   pem_amg_apply  z = cycle(0) with b_0 = d_r: one V-cycle on A z = r from z = 0.  All arithmetic in VT, one rounding per operation,
+ *       no fma in the cycle's own kernels; every A x is pem_tiled_mxv's chain.  cycle(l):
+ *         coarsest   x_i = w_i * b_i; then coarse_sweeps - 1 times: q = A_l x; x_i = x_i + w_i * (b_i - q_i).
+ *         otherwise  x_i = w_i * b_i; sweeps - 1 such Jacobi sweeps; q = A_l x; r_i = b_i - q_i; b_{l+1} = R_l r (plus_times mxv);
+ *                    cycle(l + 1); x = x + P_l x_{l+1} (mxv of P_l with accumulate = 1: the chain starts from the old x_i); sweeps
+ *                    Jacobi sweeps.  Pre- and post-smoothing are equal, so the cycle is a symmetric operator for a symmetric A.
+ *       No reduction, no atomic; every element is written by the thread that computed it, and no kernel reads at another index an
+ *       array its own launch writes: the bits do not depend on the launch shape.  Allocates nothing, never waits, reads nothing back.
+ *       PEM_E_INVALID: a null ctx or hierarchy; another context than create's; the fp64 form on an fp32 tiling or the reverse; a null
+ *       vector where n > 0; d_r overlapping d_z.  n = 0 is legal and launches nothing.
+ *   pem_amg_get_info  levels; rows, nnz of every A_l; p_nnz of every P_l (0 at the coarsest); aggregate_rounds (0 where no aggregation
+ *       ran); launches = the kernel launches of ONE pem_amg_apply, the mxv launches included: 2 coarse_sweeps - 1 at the coarsest
+ *       level, 4 sweeps + 3 at every other; bytes = what create added to the arena's bytes in use (the hierarchy beyond A itself, and
+ *       whatever its calls grew the context's scratch by), as of create's return.
+ *   pem_amg_get_level  borrowed handles, valid until pem_amg_destroy: A_l, P_l and R_l = P_l^T as a tiling (P and R NULL at the
+ *       coarsest level).  Any of the three pointers may be NULL.
+ *   Not covered: strength-of-connection filtering; a spectral-radius estimate for omega; W- and K-cycles; Chebyshev and Gauss-Seidel
+ *       smoothers; a direct coarsest solve; graph capture of the cycle; fusing the smoother into the mxv kernel; a pem_mgpu_* path. */
+enum { PEM_AMG_MAX_LEVELS = 16 };
+typedef struct {
+    int      smooth;         /* 0: piecewise-constant P (one 1 per row); 1: Jacobi-smoothed P */
+    int      symmetric;      /* handed to pem_tiled_aggregate at every level */
+    uint32_t seed;           /* pem_tiled_aggregate's seed, the same at every level; d_priority = NULL */
+    int32_t  max_levels;     /* 1 .. PEM_AMG_MAX_LEVELS */
+    int64_t  coarse_size;    /* >= 1: a level with n_l <= coarse_size is the coarsest */
+    int32_t  sweeps;         /* >= 1: Jacobi sweeps before and after the coarse correction */
+    int32_t  coarse_sweeps;  /* >= 1: Jacobi sweeps on the coarsest level */
+    double   omega;          /* > 0 and finite: the Jacobi weight, of the smoother and of the smoothed P alike */
+    int      refreshable;    /* 1: keep the plans and intermediates pem_amg_refresh needs; 0: free them after setup */
+} pem_amg_opts;
+typedef struct {
+    int32_t levels;
+    int64_t rows[PEM_AMG_MAX_LEVELS], nnz[PEM_AMG_MAX_LEVELS];     /* of A_l */
+    int64_t p_nnz[PEM_AMG_MAX_LEVELS];                             /* of P_l, 0 at the coarsest */
+    int32_t aggregate_rounds[PEM_AMG_MAX_LEVELS];
+    int64_t launches;        /* kernel launches of ONE pem_amg_apply, the mxv launches included */
+    int64_t bytes;           /* device bytes the object holds beyond A itself */
+} pem_amg_info;
+typedef struct pem_amg pem_amg;
+pem_status pem_amg_create(pem_ctx *ctx, const pem_tiled *A, const pem_amg_opts *opts, pem_amg **out);
+pem_status pem_amg_refresh(pem_ctx *ctx, pem_amg *M);
+pem_status pem_amg_apply(pem_ctx *ctx, pem_amg *M, const double *d_r, double *d_z);
+pem_status pem_amg_apply_f32(pem_ctx *ctx, pem_amg *M, const float *d_r, float *d_z);
+pem_status pem_amg_get_info(const pem_amg *M, pem_amg_info *info);
+pem_status pem_amg_get_level(const pem_amg *M, int level, const pem_tiled **A_l, const pem_tiled **P_l, const pem_tiled **R_l);
+pem_status pem_amg_destroy(pem_ctx *ctx, pem_amg *M);
+enum { PEM_PRECOND_AMG = 3 };
+pem_status pem_krylov_create_amg(pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_amg *M, pem_krylov **out);
 
 /* A tiling as CSR (host arrays, the calling convention of pem_c_export_csr): rowptr has rows + 1 entries, column indices ascend
  * inside a row, values are copied bit for bit.  Any tiling works; one built with transpose = 1 exports M^T.  rowptr == NULL: only

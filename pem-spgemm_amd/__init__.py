@@ -67,12 +67,16 @@ ABI_SYMBOLS = [
     "pem_tiled_colour", "pem_colour_order", "pem_tiled_components",
     "pem_tiled_mis", "pem_tiled_aggregate",
     "pem_krylov_create", "pem_krylov_solve", "pem_krylov_solve_f32", "pem_krylov_destroy", "pem_test_krylov_dot",
+    "pem_amg_create", "pem_amg_refresh", "pem_amg_apply", "pem_amg_apply_f32", "pem_amg_get_info", "pem_amg_get_level", "pem_amg_destroy",
+    "pem_krylov_create_amg",
 ]
 
 # PEM_KRYLOV_CG / _BICGSTAB, PEM_PRECOND_NONE / _DIAG / _LU and the PEM_KRYLOV_* statuses (include/pem_spgemm.h, INTEGRATION.md
 # section 3zc), by value
 KRYLOV_METHODS = ("cg", "bicgstab")
 KRYLOV_PRECONDS = ("none", "diag", "lu")
+PRECOND_AMG = 3       # PEM_PRECOND_AMG: through pem_krylov_create_amg only (Krylov.precond then reads "amg")
+AMG_MAX_LEVELS = 16   # PEM_AMG_MAX_LEVELS
 KRYLOV_STATUS = ("converged", "max_iters", "breakdown", "nonfinite")
 
 # enum pem_ewise_pattern / pem_binop (include/pem_spgemm.h): Tiled.ewise
@@ -167,6 +171,17 @@ class KrylovResult(C.Structure):
                 ("readbacks", C.c_int64), ("launches", C.c_int64)]
 
 
+class AmgOpts(C.Structure):
+    _fields_ = [("smooth", C.c_int), ("symmetric", C.c_int), ("seed", C.c_uint32), ("max_levels", C.c_int32), ("coarse_size", C.c_int64),
+                ("sweeps", C.c_int32), ("coarse_sweeps", C.c_int32), ("omega", C.c_double), ("refreshable", C.c_int)]
+
+
+class AmgInfo(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("rows", C.c_int64 * AMG_MAX_LEVELS), ("nnz", C.c_int64 * AMG_MAX_LEVELS),
+                ("p_nnz", C.c_int64 * AMG_MAX_LEVELS), ("aggregate_rounds", C.c_int32 * AMG_MAX_LEVELS), ("launches", C.c_int64),
+                ("bytes", C.c_int64)]
+
+
 class Timings(C.Structure):
     _fields_ = [("step1_ms", C.c_double), ("step2_ms", C.c_double), ("step3_ms", C.c_double), ("spgemm_wall_ms", C.c_double),
                 ("export_ms", C.c_double)]
@@ -207,6 +222,15 @@ def lib():
         L.pem_test_krylov_dot.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.pem_krylov_create.restype = L.pem_krylov_solve.restype = L.pem_krylov_solve_f32.restype = C.c_int
         L.pem_krylov_destroy.restype = L.pem_test_krylov_dot.restype = C.c_int
+        # (ctx, A, opts, out), (ctx, M), (ctx, M, d_r, d_z), (M, info), (M, level, A_l, P_l, R_l), (ctx, M) and (ctx, A, opts, M, out)
+        L.pem_amg_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AmgOpts), C.POINTER(C.c_void_p)]
+        L.pem_amg_refresh.argtypes = L.pem_amg_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.pem_amg_apply.argtypes = L.pem_amg_apply_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pem_amg_get_info.argtypes = [C.c_void_p, C.POINTER(AmgInfo)]
+        L.pem_amg_get_level.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.pem_krylov_create_amg.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KrylovOpts), C.c_void_p, C.POINTER(C.c_void_p)]
+        L.pem_amg_create.restype = L.pem_amg_refresh.restype = L.pem_amg_destroy.restype = L.pem_amg_apply.restype = C.c_int
+        L.pem_amg_apply_f32.restype = L.pem_amg_get_info.restype = L.pem_amg_get_level.restype = L.pem_krylov_create_amg.restype = C.c_int
         _lib = L
     return _lib
 
@@ -303,8 +327,9 @@ class Context:
 class Tiled:
     """pem_tiled: a matrix in 16x16 tiled-CSR form on the device (spgemm.cu:832-1066)."""
 
-    def __init__(self, ctx, handle):
+    def __init__(self, ctx, handle, owner=None):
         self.ctx, self._h = ctx, handle
+        self._owner = owner   # not None: a view of a handle that object owns (Amg.level); close() then only drops the view
         info = TiledInfo()
         _check(lib().pem_tiled_get_info(self._h, C.byref(info)))
         for k, _ in TiledInfo._fields_:
@@ -920,7 +945,8 @@ class Tiled:
     def solve(self, b, method="cg", precond=None, x=None, max_iters=1000, check_every=8, rtol=1e-8, atol=0.0, history=False):
         """A x = b in one call: makes a Krylov solver, solves, closes it; returns (x, info) as
         Krylov.solve.  precond: None, "jacobi" (minv = 1 / self.select("diag", 0).reduce("plus"), the DIAG preconditioner), "ilu0"
-        (makes and closes its own factor), a tiling (an LU factor), or a device tensor (minv itself)."""
+        (makes and closes its own factor), "amg" (makes and closes its own default Amg), a tiling (an LU factor), an Amg made on this
+        tiling, or a device tensor (minv itself)."""
         minv, F, own = None, None, None
         if isinstance(precond, str):
             if precond == "jacobi":
@@ -934,8 +960,11 @@ class Tiled:
                 precond = "diag"
             elif precond == "ilu0":
                 precond = own = self.ilu0()
+            elif precond == "amg":
+                precond = own = Amg(self)
             elif precond != "none":
-                raise ValueError(f"solve: unknown precond {precond!r}; None, 'none', 'jacobi', 'ilu0', a tiling or a device tensor")
+                raise ValueError(f"solve: unknown precond {precond!r}; None, 'none', 'jacobi', 'ilu0', 'amg', a tiling, an Amg or a device "
+                                 "tensor")
         elif hasattr(precond, "data_ptr"):
             minv, precond = precond, "diag"
         try:
@@ -1219,7 +1248,90 @@ class Tiled:
 
     def close(self):
         if self._h:
-            lib().pem_tiled_destroy(self.ctx._h, self._h)
+            if self._owner is None:
+                lib().pem_tiled_destroy(self.ctx._h, self._h)
+            self._h, self._owner = C.c_void_p(), None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Amg:
+    """pem_amg: the aggregation-multigrid hierarchy of a square tiling A with a stored diagonal, and
+    one V-cycle of it as z = M r.  smooth: the Jacobi-smoothed prolongator (True) or the piecewise-constant one; symmetric, seed:
+    Tiled.aggregate's, at every level; max_levels (1 .. AMG_MAX_LEVELS) and coarse_size (a level of at most that many rows is the
+    coarsest) bound the hierarchy; sweeps: Jacobi sweeps before and after the coarse correction; coarse_sweeps: those on the coarsest
+    level; omega: the Jacobi weight, of the smoother and of the smoothed prolongator; refreshable: keep what refresh() needs.  The
+    object keeps A alive and reads its current values in refresh().  Wrong arguments raise ValueError; what the library refuses (a row
+    without a stored diagonal entry, a pattern that is not symmetric under symmetric=True) raises PemError.  Waits."""
+
+    def __init__(self, A, smooth=True, symmetric=False, seed=0, max_levels=16, coarse_size=40, sweeps=1, coarse_sweeps=4, omega=2 / 3,
+                 refreshable=True):
+        if not isinstance(A, Tiled):
+            raise ValueError(f"Amg: A must be a tiling, not {type(A).__name__}")
+        seed = _colour_seed(seed, "Amg")
+        for name, v, lo, hi in (("max_levels", max_levels, 1, AMG_MAX_LEVELS), ("coarse_size", coarse_size, 1, 2 ** 63 - 1),
+                                ("sweeps", sweeps, 1, 2 ** 31 - 1), ("coarse_sweeps", coarse_sweeps, 1, 2 ** 31 - 1)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+                raise ValueError(f"Amg: {name} must be an integer in [{lo}, {hi}], not {v!r}")
+        if isinstance(omega, bool) or not isinstance(omega, numbers.Real) or not (float(omega) > 0 and np.isfinite(float(omega))):
+            raise ValueError(f"Amg: omega must be a positive finite number, not {omega!r}")
+        self.A, self.ctx = A, A.ctx
+        self.opts = dict(smooth=bool(smooth), symmetric=bool(symmetric), seed=seed, max_levels=int(max_levels), coarse_size=int(coarse_size),
+                         sweeps=int(sweeps), coarse_sweeps=int(coarse_sweeps), omega=float(omega), refreshable=bool(refreshable))
+        o = AmgOpts(int(bool(smooth)), int(bool(symmetric)), seed, int(max_levels), int(coarse_size), int(sweeps), int(coarse_sweeps),
+                    float(omega), int(bool(refreshable)))
+        self._h = C.c_void_p()
+        _check(lib().pem_amg_create(self.ctx._h, A._h, C.byref(o), C.byref(self._h)))
+
+    @property
+    def info(self):
+        """dict: levels; rows, nnz (of every A_l), p_nnz (of every P_l, 0 at the coarsest), aggregate_rounds: lists of `levels`
+        entries; launches (of one apply, the mxv launches included); bytes (device bytes beyond A itself);
+        operator_complexity = sum(nnz) / nnz[0]"""
+        m = AmgInfo()
+        _check(lib().pem_amg_get_info(self._h, C.byref(m)))
+        n = int(m.levels)
+        out = dict(levels=n, rows=list(m.rows[:n]), nnz=list(m.nnz[:n]), p_nnz=list(m.p_nnz[:n]),
+                   aggregate_rounds=list(m.aggregate_rounds[:n]), launches=int(m.launches), bytes=int(m.bytes))
+        out["operator_complexity"] = sum(out["nnz"]) / out["nnz"][0] if out["nnz"][0] else 1.0
+        return out
+
+    @property
+    def levels(self):
+        return self.info["levels"]
+
+    def level(self, l):
+        """(A_l, P_l, R_l): non-owning Tiled views, valid while this object is open (each keeps it alive); P_l and R_l = P_l^T are
+        None at the coarsest level.  close() on a view does not destroy the tiling."""
+        if isinstance(l, bool) or not isinstance(l, numbers.Integral):
+            raise ValueError(f"Amg.level: the level must be an integer, not {l!r}")
+        h = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        _check(lib().pem_amg_get_level(self._h, int(l), *(C.byref(x) for x in h)))
+        return tuple(Tiled(self.ctx, x, owner=self) if x.value else None for x in h)
+
+    def apply(self, r, out=None):
+        """out = one V-cycle on A z = r from z = 0.  r: a contiguous device torch tensor of A's dtype with A.rows entries; out: one
+        like it, not overlapping r, allocated when None.  Ordered on the context's stream, never waits (see Tiled.mxv).  Returns out."""
+        A = self.A
+        pr = A._vector("Amg.apply", "r", r, A.rows)
+        out, pz = A._out("Amg.apply", out, A.rows, like=r)
+        fn = lib().pem_amg_apply_f32 if A.value_bytes == 4 else lib().pem_amg_apply
+        _check(fn(self.ctx._h, self._h, pr, pz))
+        return out
+
+    def refresh(self):
+        """After new values on A (same pattern): every level's values again on the patterns and aggregates the setup found -- what
+        a fresh Amg on the new values holds, array for array.  Ordered on the context's stream, reads nothing back; allocates nothing
+        from the second call on.  PemError (PEM_E_STATE) with refreshable=False."""
+        _check(lib().pem_amg_refresh(self.ctx._h, self._h))
+
+    def close(self):
+        if self._h:
+            lib().pem_amg_destroy(self.ctx._h, self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1231,35 +1343,42 @@ class Tiled:
 
 class Krylov:
     """pem_krylov: preconditioned CG or BiCGStab on a square tiling A, the whole loop on the context's
-    stream.  method: one of KRYLOV_METHODS.  precond: None or "none"; "diag" (every solve then takes minv); or a tiling F, an LU
-    factor such as A.ilu0(), applied by two trsv.  The host reads a 128-byte state block back every check_every iterations; x, iters,
+    stream.  method: one of KRYLOV_METHODS.  precond: None or "none"; "diag" (every solve then takes minv); a tiling F, an LU
+    factor such as A.ilu0(), applied by two trsv; or an Amg made on A, applied as one V-cycle (Krylov.precond then reads "amg").  The host reads a 128-byte state block back every check_every iterations; x, iters,
     status and the history do not depend on check_every.  Stops at rr <= max(rtol^2 * bb, atol^2), after max_iters iterations, on
-    a breakdown or on a residual that is not finite.  The object keeps A and F alive and reads their current values in every solve.
+    a breakdown or on a residual that is not finite.  The object keeps A, F and the Amg alive and reads their current values in every
+    solve.
     Wrong arguments raise ValueError; what the library refuses raises PemError."""
 
     def __init__(self, A, method="cg", precond=None, max_iters=1000, check_every=8, rtol=1e-8, atol=0.0):
         if method not in KRYLOV_METHODS:
             raise ValueError(f"Krylov: unknown method {method!r}; one of {KRYLOV_METHODS}")
-        F = None
-        if precond is None or precond == "none":
+        F = M = None
+        if precond is None or (isinstance(precond, str) and precond == "none"):
             pc = 0
-        elif precond == "diag":
+        elif isinstance(precond, str) and precond == "diag":
             pc = 1
         elif isinstance(precond, Tiled):
             pc, F = 2, precond
+        elif isinstance(precond, Amg):
+            pc, M = PRECOND_AMG, precond
         else:
-            raise ValueError(f"Krylov: precond must be None, 'none', 'diag' or a tiling (an LU factor), not {precond!r}")
+            raise ValueError(f"Krylov: precond must be None, 'none', 'diag', a tiling (an LU factor) or an Amg, not {precond!r}")
         for name, v in (("max_iters", max_iters), ("check_every", check_every)):
             if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not -2 ** 63 <= int(v) < 2 ** 63:
                 raise ValueError(f"Krylov: {name} must be an integer, not {v!r}")
         for name, v in (("rtol", rtol), ("atol", atol)):
             if isinstance(v, bool) or not isinstance(v, numbers.Real):
                 raise ValueError(f"Krylov: {name} must be a real number, not {v!r}")
-        self.A, self.F, self.ctx = A, F, A.ctx
-        self.method, self.precond, self.max_iters, self.check_every = method, KRYLOV_PRECONDS[pc], int(max_iters), int(check_every)
+        self.A, self.F, self.M, self.ctx = A, F, M, A.ctx
+        self.method, self.precond = method, "amg" if M is not None else KRYLOV_PRECONDS[pc]
+        self.max_iters, self.check_every = int(max_iters), int(check_every)
         opts = KrylovOpts(KRYLOV_METHODS.index(method), pc, int(max_iters), int(check_every), float(rtol), float(atol))
         self._h = C.c_void_p()
-        _check(lib().pem_krylov_create(self.ctx._h, A._h, C.byref(opts), F._h if F is not None else None, C.byref(self._h)))
+        if M is not None:
+            _check(lib().pem_krylov_create_amg(self.ctx._h, A._h, C.byref(opts), M._h, C.byref(self._h)))
+        else:
+            _check(lib().pem_krylov_create(self.ctx._h, A._h, C.byref(opts), F._h if F is not None else None, C.byref(self._h)))
 
     def solve(self, b, x=None, minv=None, history=False):
         """(x, info).  b: a contiguous device torch tensor of A's dtype with A.rows entries; x: the guess, overwritten with the

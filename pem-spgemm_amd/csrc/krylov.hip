@@ -1,5 +1,6 @@
 // krylov.hip -- preconditioned CG and BiCGStab on a tiling (include/pem_spgemm.h, pem_krylov_*): A x = b solved on the context's
-// stream, the preconditioner none, a diagonal or an LU factor (two pem_tiled_trsv per application).
+// stream, the preconditioner none, a diagonal, an LU factor (two pem_tiled_trsv per application) or a multigrid hierarchy (one
+// pem_amg_apply per application, where LU runs its solves: the [LU: ...] launches below with T = pem_amg_info::launches).
 //
 // The order is the contract; the header states it in full.  What this file adds to it is the launch structure:
 //   Every vector kernel runs the SAME partition of [0, n): chunks of KR_CHUNK = 4096 elements, G = min(ceil(n / 4096), 1024)
@@ -430,6 +431,7 @@ enum { SLOT_BB = 0, SLOT_RR, SLOT_RZ, SLOT_A, SLOT_B, SLOT_C, SLOT_D, KR_SLOTS }
 struct pem_krylov {
     pem_ctx *owner = nullptr;
     const pem_tiled *A = nullptr, *F = nullptr;
+    const pem_amg *M = nullptr;  // PEM_PRECOND_AMG: z = one V-cycle, on the LU path
     pem_krylov_opts opts = {};
     DevBuf buf;                 // the work vectors, the partial slots, the two state blocks
     void *vec[9] = {};          // CG: r p q z w;  BiCGStab: r rhat p v s t y z w
@@ -466,10 +468,15 @@ struct Run {
         ++K->launches;
         return mxv_semiring(ctx, K->A, PEM_SEMIRING_PLUS_TIMES, false, xin, y, 0);
     }
-    // dst = U^-1 L^-1 src through the work vector w
+    // dst = U^-1 L^-1 src through the work vector w; with a hierarchy dst = one V-cycle on src (w is not carved)
     pem_status lu(const VT *src, VT *w, VT *dst)
     {
         K->launches += trsv_launches;
+        if (K->M) {
+            pem_amg *M = const_cast<pem_amg *>(K->M);
+            if constexpr (sizeof(VT) == 8) return pem_amg_apply(ctx, M, src, dst);
+            else return pem_amg_apply_f32(ctx, M, src, dst);
+        }
         if constexpr (sizeof(VT) == 8) {
             PEM_TRY(pem_tiled_trsv(ctx, K->F, PEM_TRSV_LOWER, 1, src, w));
             return pem_tiled_trsv(ctx, K->F, PEM_TRSV_UPPER, 0, w, dst);
@@ -593,6 +600,11 @@ pem_status krylov_run(pem_ctx *ctx, pem_krylov *K, const VT *b, VT *x, const VT 
         PEM_TRY(pem_tiled_trsv_info(ctx, K->F, PEM_TRSV_UPPER, &up));
         R.trsv_launches = lo.launches + up.launches;
     }
+    if (K->M) {
+        pem_amg_info mi;
+        PEM_TRY(pem_amg_get_info(K->M, &mi));
+        R.trsv_launches = mi.launches;
+    }
     K->launches = 0;
     PEM_TRY(R.start());
     KState S;
@@ -676,11 +688,12 @@ pem_status krylov_solve(pem_ctx *ctx, pem_krylov *K, const void *db, void *dx, c
 
 }  // namespace
 
-extern "C" pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_tiled *F, pem_krylov **out)
+// pem_krylov_create (M null) and pem_krylov_create_amg (F null; amg: a hierarchy is expected)
+static pem_status krylov_create(const char *fn, pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_tiled *F,
+                                const pem_amg *M, bool amg, pem_krylov **out)
 {
-    const char *fn = "pem_krylov_create";
     if (out) *out = nullptr;
-    if (!ctx || !A || !opts || !out) {
+    if (!ctx || !A || !opts || !out || (amg && !M)) {
         set_error("%s: null argument", fn);
         return PEM_E_INVALID;
     }
@@ -692,7 +705,16 @@ extern "C" pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const 
         set_error("%s: unknown method %d (PEM_KRYLOV_CG = 0, PEM_KRYLOV_BICGSTAB = 1)", fn, opts->method);
         return PEM_E_INVALID;
     }
-    if (opts->precond < PEM_PRECOND_NONE || opts->precond > PEM_PRECOND_LU) {
+    if (amg) {
+        if (opts->precond != PEM_PRECOND_AMG) {
+            set_error("%s: the preconditioner must be PEM_PRECOND_AMG = 3 (got %d)", fn, opts->precond);
+            return PEM_E_INVALID;
+        }
+        if (amg_owner(M) != ctx || amg_operator(M) != A) {
+            set_error("%s: the hierarchy was created on another %s", fn, amg_owner(M) != ctx ? "context" : "tiling than A");
+            return PEM_E_INVALID;
+        }
+    } else if (opts->precond < PEM_PRECOND_NONE || opts->precond > PEM_PRECOND_LU) {
         set_error("%s: unknown preconditioner %d (PEM_PRECOND_NONE, _DIAG, _LU = 0, 1, 2)", fn, opts->precond);
         return PEM_E_INVALID;
     }
@@ -731,10 +753,12 @@ extern "C" pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const 
     K->owner = ctx;
     K->A = A;
     K->F = F;
+    K->M = M;
     K->opts = *opts;
     const bool cg = opts->method == PEM_KRYLOV_CG;
     int nvec;
-    if (cg) nvec = opts->precond == PEM_PRECOND_LU ? 5 : 3;
+    if (amg) nvec = cg ? 4 : 8;   // LU's vectors without the trsv work vector w
+    else if (cg) nvec = opts->precond == PEM_PRECOND_LU ? 5 : 3;
     else nvec = opts->precond == PEM_PRECOND_LU ? 9 : (opts->precond == PEM_PRECOND_DIAG ? 8 : 6);
     const size_t vbytes = (n * (size_t)A->value_bytes + 255) & ~size_t(255);
     const size_t sbytes = sizeof(double) * KR_MAXG;
@@ -745,6 +769,16 @@ extern "C" pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const 
     for (int i = 0; i < 2; ++i, p += 256) K->state[i] = reinterpret_cast<KState *>(p);
     *out = K.release();
     return PEM_OK;
+}
+
+extern "C" pem_status pem_krylov_create(pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_tiled *F, pem_krylov **out)
+{
+    return krylov_create("pem_krylov_create", ctx, A, opts, F, nullptr, false, out);
+}
+
+extern "C" pem_status pem_krylov_create_amg(pem_ctx *ctx, const pem_tiled *A, const pem_krylov_opts *opts, const pem_amg *M, pem_krylov **out)
+{
+    return krylov_create("pem_krylov_create_amg", ctx, A, opts, nullptr, M, true, out);
 }
 
 extern "C" pem_status pem_krylov_solve(pem_ctx *ctx, pem_krylov *K, const double *db, double *dx, const double *d_minv, double *d_history,

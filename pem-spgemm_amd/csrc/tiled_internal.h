@@ -125,7 +125,11 @@ int64_t trsv_for_launches(const TrsvSched &S, int mw, Fn fn)
     return launches;
 }
 
-// ---- device: tile lookups in a tiling's tile CSR (mask.hip, ewise.hip) ----
+// ---- what pem_krylov_create_amg checks of a hierarchy (amg.hip): the context and the operator handle it was created on ----
+pem_ctx *amg_owner(const pem_amg *M);
+const pem_tiled *amg_operator(const pem_amg *M);
+
+// ---- device: tile lookups in a tiling's tile CSR (mask.hip, ewise.hip; amg.hip) ----
 // M's tile id at (i, j), -1 where M has none: binary search in M's tile row i (tile_colidx is sorted inside a row)
 __device__ __forceinline__ int mask_find_tile(const int *__restrict__ m_rowptr, const int *__restrict__ m_colidx, const int i, const int j)
 {

@@ -113,6 +113,7 @@ struct Options {
     bool ilu0 = false;                                              // --ilu0: see ilu0_stage
     const char *solve_spec = nullptr, *precond_name = nullptr;      // --solve cg|bicgstab [--precond none|jacobi|ilu0]: see solve_stage
     const char *rtol_spec = nullptr, *max_iters_spec = nullptr;     // --rtol R, --max-iters N
+    const char *amg_kind = nullptr;                                 // --amg smoothed|plain: --solve's multigrid preconditioner
     const char *colour_spec = nullptr;                              // --colour SEED: see colour_stage
     bool colour_natural = false;                                    // --colour-natural: equal priorities
     bool components = false;                                        // --components: see components_stage
@@ -152,6 +153,7 @@ struct Options {
     int solve_precond = 0;                                // 0 none, 1 jacobi, 2 ilu0
     double solve_rtol = 1e-8;
     long long solve_max_iters = 1000;
+    int amg_smooth = -1;                                  // --amg: 1 smoothed, 0 plain
     uint32_t colour_seed = 0;
     uint32_t aggregate_seed = 0;
     const char *colour_flag() const { return colour_spec ? "--colour" : colour_natural ? "--colour-natural" : nullptr; }
@@ -176,7 +178,7 @@ static void parse_args(int argc, char *argv[], Options *o)
                   {"--argreduce", &o->argreduce_spec}, {"--bfs-parents", &o->bfs_parents_spec}, {"--sampled", &o->sampled_path},
                   {"--trsv", &o->trsv_spec}, {"--rhs", &o->rhs_path}, {"--colour", &o->colour_spec},
                   {"--aggregate", &o->aggregate_spec}, {"--solve", &o->solve_spec}, {"--precond", &o->precond_name},
-                  {"--rtol", &o->rtol_spec}, {"--max-iters", &o->max_iters_spec}};
+                  {"--rtol", &o->rtol_spec}, {"--max-iters", &o->max_iters_spec}, {"--amg", &o->amg_kind}};
     const struct {
         const char *name;
         bool *flag, value;
@@ -506,6 +508,21 @@ static int validate_vectors(Options *o)
     if (!o->solve_spec && (o->precond_name || o->rtol_spec || o->max_iters_spec)) {
         printf("--precond / --rtol / --max-iters need --solve cg|bicgstab. Exiting.\n");
         return 1;
+    }
+    if (o->amg_kind) {
+        if (!o->solve_spec) {
+            printf("--amg needs --solve cg|bicgstab. Exiting.\n");
+            return 1;
+        }
+        if (o->precond_name) {
+            printf("--amg does not combine with --precond. Exiting.\n");
+            return 1;
+        }
+        o->amg_smooth = !strcmp(o->amg_kind, "smoothed") ? 1 : !strcmp(o->amg_kind, "plain") ? 0 : -1;
+        if (o->amg_smooth < 0) {
+            printf("--amg %s: unknown kind (smoothed, plain). Exiting.\n", o->amg_kind);
+            return 1;
+        }
     }
     if (o->solve_spec) {
         if (clashes(*o, "--solve")) return 1;
@@ -2035,10 +2052,13 @@ static int trsv_stage(const Options &o, pem_ctx *ctx, Result *r)
     return 0;
 }
 
-// `--solve cg|bicgstab --rhs b.mtx [--precond none|jacobi|ilu0] [--rtol R] [--max-iters N]` solves
+// `--solve cg|bicgstab --rhs b.mtx [--precond none|jacobi|ilu0 | --amg smoothed|plain] [--rtol R] [--max-iters N]` (INTEGRATION.md
+// sections 3zc, 3zd) solves
 // R x = b on the device (pem_krylov_*), R the final result (what --reduce would fold; it must be square), from a zero guess.
 // jacobi: the inverse of R's diagonal (pem_tiled_select + pem_tiled_reduce, inverted on the host in the value type); ilu0: the
-// stage's own pem_tiled_ilu0(R).  One line reports the time, the iterations, the status and sqrt(rr / bb); --out then writes x
+// stage's own pem_tiled_ilu0(R); --amg: the stage's own pem_amg_create(R) with the defaults of the Python binding's Amg (symmetric
+// = 0, seed 0, 16 levels, coarse_size 40, one sweep, four coarse sweeps, omega 2/3, not refreshable), reported on an `amg:` line --
+// levels, rows level by level, the operator complexity sum nnz(A_l) / nnz(A_0), setup ms.  One line reports the time, the iterations, the status and sqrt(rr / bb); --out then writes x
 // (Matrix-Market array) instead of the matrix.  A status other than converged is reported, not refused.  The CSV row describes the
 // product.
 static int solve_stage(const Options &o, pem_ctx *ctx, Result *r)
@@ -2084,16 +2104,49 @@ static int solve_stage(const Options &o, pem_ctx *ctx, Result *r)
             return 1;
         }
     }
+    struct AmgHandle {
+        pem_ctx *ctx;
+        pem_amg *M = nullptr;
+        ~AmgHandle() { pem_amg_destroy(ctx, M); }
+    } amg{ctx};
+    if (o.amg_smooth >= 0) {
+        pem_amg_opts ao;
+        ao.smooth = o.amg_smooth;
+        ao.symmetric = 0;
+        ao.seed = 0;
+        ao.max_levels = PEM_AMG_MAX_LEVELS;
+        ao.coarse_size = 40;
+        ao.sweeps = 1;
+        ao.coarse_sweeps = 4;
+        ao.omega = 2.0 / 3.0;
+        ao.refreshable = 0;
+        if (pem_amg_create(ctx, src.t, &ao, &amg.M) != PEM_OK) {
+            printf("--amg %s: %s. Exiting.\n", o.amg_kind, pem_last_error());
+            return 1;
+        }
+    }
     const double setup_ms = ms_since(t0);
+    if (amg.M) {
+        pem_amg_info ai;
+        CHECK(pem_amg_get_info(amg.M, &ai));
+        std::string rows;
+        int64_t nnz_all = 0;
+        for (int l = 0; l < ai.levels; ++l) {
+            rows += (l ? ", " : "") + std::to_string((long long)ai.rows[l]);
+            nnz_all += ai.nnz[l];
+        }
+        printf("amg: %s of %s: %d levels, rows %s, operator complexity %.4f, %lld launches per cycle, setup %.3fms\n", o.amg_kind, r->last_name,
+               (int)ai.levels, rows.c_str(), ai.nnz[0] ? (double)nnz_all / (double)ai.nnz[0] : 1.0, (long long)ai.launches, setup_ms);
+    }
     pem_krylov_opts ko;
     ko.method = o.solve_method;
-    ko.precond = o.solve_precond == 1 ? PEM_PRECOND_DIAG : o.solve_precond == 2 ? PEM_PRECOND_LU : PEM_PRECOND_NONE;
+    ko.precond = amg.M ? (int)PEM_PRECOND_AMG : o.solve_precond == 1 ? PEM_PRECOND_DIAG : o.solve_precond == 2 ? PEM_PRECOND_LU : PEM_PRECOND_NONE;
     ko.max_iters = o.solve_max_iters;
     ko.check_every = 8;
     ko.rtol = o.solve_rtol;
     ko.atol = 0.0;
     pem_krylov *K = nullptr;
-    if (pem_krylov_create(ctx, src.t, &ko, F.get(), &K) != PEM_OK) {
+    if ((amg.M ? pem_krylov_create_amg(ctx, src.t, &ko, amg.M, &K) : pem_krylov_create(ctx, src.t, &ko, F.get(), &K)) != PEM_OK) {
         printf("--solve %s: %s. Exiting.\n", o.solve_spec, pem_last_error());
         return 1;
     }
@@ -2107,7 +2160,7 @@ static int solve_stage(const Options &o, pem_ctx *ctx, Result *r)
     if (!dx.download(&r->solve_x, n, o.fp32)) return 2;
     static const char *const status[] = {"converged", "max_iters", "breakdown", "nonfinite"};
     printf("solve: %s with %s of %s: solve %.3fms (preconditioner %.3fms), %lld iterations, %s, relative residual %.3e, %lld read-backs, host sum %.17g\n",
-           o.solve_spec, o.precond_name ? o.precond_name : "none", r->last_name, solve_ms, setup_ms, (long long)res.iters, status[res.status],
+           o.solve_spec, amg.M ? "amg" : o.precond_name ? o.precond_name : "none", r->last_name, solve_ms, setup_ms, (long long)res.iters, status[res.status],
            sqrt(res.rr / res.bb), (long long)res.readbacks, sum_of(r->solve_x));
     return 0;
 }
