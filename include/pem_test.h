@@ -42,6 +42,10 @@ extern "C" {
                                                    forked bins); 2 (default): where a plan sorts 32-bit keys, has no oversized row and no more
                                                    segments than CUs (decided by its first pass), PEM_OPT_S1_SEGMENTS not set; 1: the same with any
                                                    number of segments, and with PEM_OPT_S1_SEGMENTS set as well                                  */
+#define PEM_OPT_S3_BATCH       ((pem_option)21) /* shallow step 3, trips whose pair range is staged: 0 (default) the third and later pairs one
+                                                   after the other; 1: their records land in a wave-private LDS strip three pairs at a time
+                                                   (LDS-direct loads, the first batch beside the value gathers of pairs 1 and 2) -- measured 5 %
+                                                   slower on the webbase-1M stand-in.  C is bit for bit the same           */
 
 /* a further value of pem_cplan_array: int32[T_C] of a masked plan (pem_cplan_create_masked), for every C tile M's tile id at its
  * (tile row, tile column), -1 where M has none (complement masks only); readable after step 1 */

@@ -87,6 +87,7 @@ extern "C" pem_status pem_cplan_create(pem_ctx *ctx, const pem_tiled *A, const p
     p->opt_s3_xcd = !env_is("PEM_S3_XCD", "0");
     p->opt_idx64 = env_is("PEM_S3_IDX64", "1");
     p->opt_mark = !env_is("PEM_S3_MARK", "0");
+    p->opt_s3_batch = env_is("PEM_S3_BATCH", "1");
     p->opt_s1_segments = env_is("PEM_S1_SEGMENTS", "1");
     p->opt_s1_class_scan = !env_is("PEM_S1_CLASS_SCAN", "0");
     p->opt_s2_tail_fold = !env_is("PEM_S2_TAIL_FOLD", "0");
@@ -210,6 +211,7 @@ static int *plan_option_slot(pem_cplan *p, pem_option which)
     case PEM_OPT_S1_CLASS_SCAN: return &p->opt_s1_class_scan;
     case PEM_OPT_S2_TAIL_FOLD: return &p->opt_s2_tail_fold;
     case PEM_OPT_S1_ONE_LAUNCH: return &p->opt_s1_one_launch;
+    case PEM_OPT_S3_BATCH: return &p->opt_s3_batch;
     default: return nullptr;
     }
 }
@@ -242,7 +244,7 @@ extern "C" pem_status pem_cplan_set_option(pem_cplan *plan, pem_option which, in
     case PEM_OPT_S1_SEGMENTS: case PEM_OPT_S1_CLASS_SCAN: case PEM_OPT_S1_ONE_LAUNCH: keep = 0; break;
     case PEM_OPT_WIDE: case PEM_OPT_S3_DECODE: case PEM_OPT_S2_TRANSPOSED: case PEM_OPT_S2_TAIL_FOLD: keep = 1; break;
     case PEM_OPT_S3_BAND: case PEM_OPT_S3_EPW: case PEM_OPT_S3_IDX64: case PEM_OPT_S3_MARK: case PEM_OPT_S3_XCD:
-    case PEM_OPT_S3_POISON: keep = 2; break;
+    case PEM_OPT_S3_POISON: case PEM_OPT_S3_BATCH: keep = 2; break;
     default: break;                                    // warm passes, the export variant, serial bins: no step's result changes
     }
     if (plan->state > keep) plan->state = keep;

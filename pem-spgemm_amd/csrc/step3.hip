@@ -84,7 +84,29 @@ template <bool IDX32, typename T> __device__ __forceinline__ T s3_ld(const T *__
 // without the six-step shuffle search -- the tiles that start inside the trip's 64 entries mark their first entry in a
 // 64-word LDS strip, one ballot turns the strip into a bit mask, and an entry's tile is (tiles started before the trip) +
 // (marks at or below its lane) - 1.
-template <typename VT, bool DEEP, bool BAND = false, bool DECODE = false, bool IDX32 = false, bool MARK = false, typename SR = SrPlusTimes>
+// BATCH (PEM_OPT_S3_BATCH; shallow, staged trips): the records of a trip's third and later pairs land in a wave-private strip of
+// LDS, S3_BATCH_R pairs at a time, through LDS-direct loads -- per-lane source address, no register destination, the words of
+// slot s at strip[s][lane].  The first batch is issued beside the value gathers of pairs 1 and 2, so the records of pairs 3-5
+// cost an entry no round trip of their own (records 1-2 | values 1-2 + records 3-5 | values 3, 4, 5) where the serial loop
+// pays one per pair; every later batch pays one for its three pairs.  Nothing in flight holds a register, and the words stay in
+// the strip until they are summed -- with them in registers, or with a batch's first products gathered together, every form
+// spills at 64 VGPRs (profiles/r05_s3_batch.txt).  The loads are unconditional: a lane without a q-th pair reads the record of
+// the trip's first pair (a valid tile; r and c are 0..15 in every lane) and its words are masked after the LDS read.
+constexpr int S3_BATCH_R = 3;        // pairs per batch: 2 * S3_BATCH_R * 256 bytes of LDS per wave (6 KB per workgroup, 19 KB with the decode's)
+// the first use of a gathered value, and with it the wait for the gather, stays below this point (an empty statement to the hardware)
+template <typename T> __device__ __forceinline__ void s3_pin(T &x) { asm volatile("" : "+v"(x)); }
+template <bool IDX32> __device__ __forceinline__ void s3_glds(const uint32_t *__restrict__ base, const long long idx, unsigned *strip_row)
+{
+    const char *src;
+    if constexpr (IDX32)
+        src = reinterpret_cast<const char *>(base) + (size_t)((unsigned)idx * 4u);
+    else
+        src = reinterpret_cast<const char *>(base + idx);
+    // (the LDS address is wave-uniform: the hardware adds lane * 4)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)strip_row, 4, 0, 0);
+}
+
+template <typename VT, bool DEEP, bool BAND = false, bool DECODE = false, bool IDX32 = false, bool MARK = false, typename SR = SrPlusTimes, bool BATCH = false>
 #ifndef PEM_S3_DEEP_WAVES
 #define PEM_S3_DEEP_WAVES 1   // (8 = at most 64 VGPRs for the deep variants too: 6 of them spill and a cage15 share's step 3 is 6.83 against 6.74 ms)
 #endif
@@ -99,9 +121,13 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
     __shared__ unsigned s_mw[DECODE ? 4 * 8 * 64 : 1];                                // [wave][word q][tile]: (row 2q) << 16 | row 2q+1
     static_assert(!(DEEP && (IDX32 || MARK)), "the shallow variant's options");
     __shared__ int s_head[MARK ? 4 * 64 : 1];                                         // [wave][entry of the trip]: a tile starts here
-    int *const my_head = s_head + (MARK ? (threadIdx.x >> 6) * 64 : 0);
-    uint4 *const my_rp = s_rp + (DECODE ? (threadIdx.x >> 6) * 64 : 0);
-    unsigned *const my_mw = s_mw + (DECODE ? (threadIdx.x >> 6) * 8 * 64 : 0);
+    static_assert(!(DEEP && BATCH), "the shallow variant's option");
+    __shared__ unsigned s_strip[BATCH ? 4 * 2 * S3_BATCH_R * 64 : 1];                 // [wave][slot 2j: A's word of pair j, 2j+1: B's][lane]
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                 // (a scalar: the wave's LDS bases then cost no vector register)
+    int *const my_head = s_head + (MARK ? wv * 64 : 0);
+    uint4 *const my_rp = s_rp + (DECODE ? wv * 64 : 0);
+    unsigned *const my_mw = s_mw + (DECODE ? wv * 8 * 64 : 0);
+    unsigned *const my_strip = s_strip + (BATCH ? wv * 2 * S3_BATCH_R * 64 : 0);
     // Work is dealt by ENTRIES, S3_EPW per wave, so hub rows (tiles with many entries and pairs) cannot pile
     // up in one wave.  The wave starts at the tile its first entry lies in (noted by step 2d; a 64-ary search over
     // the tile offsets -- three dependent gathers per wave -- before that), then walks the tiles 64 at a time:
@@ -265,10 +291,6 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 aw1 = s3_ld<IDX32>(a_rec, 16ll * a1 + r);
                 bw1 = s3_ld<IDX32>(b_rec_t, 16ll * b1 + c);
             }
-            if (SR::vals && staged && lane < Pn) {
-                sav = s3_ld<IDX32>(a_nnz_ptr, sa);
-                sbv = s3_ld<IDX32>(b_nnz_ptr, sb);
-            }
             const unsigned am = aw & 0xFFFFu, bm = bw & 0xFFFFu, am1 = aw1 & 0xFFFFu, bm1 = bw1 & 0xFFFFu;
             unsigned m = am & bm, m1 = am1 & bm1;
             const int ao = av0 + (int)(aw >> 16), bo = bv0 + (int)(bw >> 16), ao1 = av1 + (int)(aw1 >> 16), bo1 = bv1 + (int)(bw1 >> 16);
@@ -282,6 +304,43 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 const unsigned below = (1u << __builtin_ctz(m1)) - 1u;
                 x1 = s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below));
                 y1 = s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below));
+            }
+            // (the batched 64-bit forms on fp64 values have no registers left beside the four first products: their first batch and
+            // their value offsets go out after pairs 1 and 2 are summed, a round trip later)
+            constexpr bool BATCH_EARLY = IDX32 || sizeof(VT) == 4;
+            // the staged value offsets travel with the values of pairs 1 and 2 (the third pair is their first reader): in front of
+            // them, the wait for the records would wait for these too -- the loads return in order -- and cost a round trip
+            auto load_offsets = [&]() {
+                if (SR::vals && staged && lane < Pn) {
+                    sav = s3_ld<IDX32>(a_nnz_ptr, sa);
+                    sbv = s3_ld<IDX32>(b_nnz_ptr, sb);
+                }
+            };
+            if constexpr (!BATCH || BATCH_EARLY) load_offsets();
+            // the records of pairs qb .. qb + S3_BATCH_R - 1 of every lane, into the strip (rounds no lane needs are left out: the
+            // `on` lanes of a round are a superset of the next round's)
+            auto issue_batch = [&](const int qb) {
+#pragma unroll
+                for (int j = 0; j < S3_BATCH_R; ++j) {
+                    const bool on = p0 + qb + j < p1;
+                    if (__ballot(on) == 0ull) break;                            // wave-uniform
+                    const int src = on ? p0 + qb + j - P0 : 0;
+                    const int a = __shfl(sa, src, 64), b = __shfl(sb, src, 64);
+                    s3_glds<IDX32>(a_rec, 16ll * a + r, my_strip + (2 * j) * 64);
+                    s3_glds<IDX32>(b_rec_t, 16ll * b + c, my_strip + (2 * j + 1) * 64);
+                }
+            };
+            // the first batch goes out behind the value gathers of pairs 1 and 2, before they are used: one round trip for all of them
+            if constexpr (BATCH && BATCH_EARLY)
+                if (staged) issue_batch(2);
+            // Both pairs' first products (and the batch) are in flight before either is used.  Without this the compiler moves the
+            // first fma -- acc is still the start value, a constant -- up into pair 1's `if (m)` and waits for its operands there,
+            // in front of pair 2's gathers: three round trips for an entry with two pairs, not two.
+            if constexpr (SR::vals) {
+                s3_pin(x0);
+                s3_pin(y0);
+                s3_pin(x1);
+                s3_pin(y1);
             }
             if constexpr (!SR::vals) {
                 acc = SR::template count<VT>(m1, SR::template count<VT>(m, acc));
@@ -308,7 +367,46 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 }
             }
             p += has2 ? 2 : has1 ? 1 : 0;
-            if (staged) {
+            if constexpr (BATCH && !BATCH_EARLY) load_offsets();
+            if (BATCH && staged) {
+                for (int qb = 2;; qb += S3_BATCH_R) {
+                    if (__ballot(p0 + qb < p1) == 0ull) break;                  // wave-uniform
+                    if (qb > 2 || !BATCH_EARLY) issue_batch(qb);                // (else the first batch is on its way)
+                    // the batch has landed: the LDS writes of the loads are counted by vmcnt, not tracked by the compiler
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    // The records stay in the strip until the batch is summed (a lane's words cost it no register meanwhile); a lane
+                    // without a pair in a round holds the words of a pair it does not own: masked.
+#pragma unroll
+                    for (int j = 0; j < S3_BATCH_R; ++j) {
+                        const bool on = p0 + qb + j < p1;
+                        if (__ballot(on) == 0ull) break;                        // wave-uniform: the round was not fetched
+                        const unsigned awq = my_strip[(2 * j) * 64 + lane], bwq = my_strip[(2 * j + 1) * 64 + lane];
+                        const unsigned amq = on ? awq & 0xFFFFu : 0u, bmq = bwq & 0xFFFFu;
+                        unsigned mq = amq & bmq;
+                        if constexpr (!SR::vals) {
+                            acc = SR::template count<VT>(mq, acc);
+                        } else {
+                            if (__ballot(mq != 0u) == 0ull) continue;           // wave-uniform: the shuffles below need every lane
+                            const int src = on ? p0 + qb + j - P0 : 0;
+                            const int aoq = __shfl(sav, src, 64) + (int)(awq >> 16), boq = __shfl(sbv, src, 64) + (int)(bwq >> 16);
+                            while (mq) {
+                                const int kk = __builtin_ctz(mq);
+                                mq &= mq - 1;
+                                const unsigned below = (1u << kk) - 1u;
+                                acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)aoq + __popc(amq & below)), s3_ld<IDX32>(b_vals_t, (long long)boq + __popc(bmq & below)), acc);
+                            }
+                        }
+                    }
+                    // the strip has been read before the next batch (or the next trip's first) overwrites it
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+                p = p1;
+            } else if (staged) {
                 for (int q = 2;; ++q) {
                     const bool on = p0 + q < p1;
                     if (__ballot(on) == 0ull) break;                            // wave-uniform
@@ -586,18 +684,26 @@ static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, 
     const pem_tiled *A = p->A, *B = p->B;
     const size_t ntc = (size_t)p->ntiles_c;
     const bool wide = p->wide;   // step 2's choice: the entry-per-lane kernel needs the chunk index the fused path wrote
-#define PEM_S3_WIDE(DEEP, NAME)                                                                                                                \
-    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, DEEP, false, false, false, false, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
+#define PEM_S3_WIDE(DEEP, BT, NAME)                                                                                                            \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, DEEP, false, false, false, false, SR, BT>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
                      p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
                      (long long)p->nnz_c, p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),       \
                      A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
                      p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
-#define PEM_S3_DECODE(I32, MK, NAME)                                                                                                           \
-    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, false, false, true, I32, MK, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
+#define PEM_S3_DECODE_BT(I32, MK, BT, NAME)                                                                                                    \
+    PEM_LAUNCH_NAMED(ctx, NAME, (s3_accumulate_wide_kernel<VT, false, false, true, I32, MK, SR, BT>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256, \
                      p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),       \
                      (long long)p->nnz_c, (const uint8_t *)nullptr, p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),           \
                      A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>(),                  \
                      p->s3_chunk_tile.as<int>(), p->c_mask.as<uint32_t>(), (int)s3_epw, s3_xcd)
+    // PEM_OPT_S3_BATCH picks between two instantiations of a shallow form; both report the form's name
+#define PEM_S3_DECODE(I32, MK, NAME)                                                                                                           \
+    do {                                                                                                                                       \
+        if (p->opt_s3_batch)                                                                                                                   \
+            PEM_S3_DECODE_BT(I32, MK, true, NAME);                                                                                             \
+        else                                                                                                                                   \
+            PEM_S3_DECODE_BT(I32, MK, false, NAME);                                                                                            \
+    } while (0)
     if (wide && deep && p->opt_band) {
         PEM_LAUNCH_NAMED(ctx, nm.wide3, (s3_accumulate_wide_kernel<VT, true, true, false, false, false, SR>), (grid_for(((size_t)p->nnz_c + s3_epw - 1) / s3_epw * 64, 256) + 7u) & ~7u, 256,
                          p->pairs_offset.as<int>(), p->pairs_a.as<int>(), p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(),
@@ -609,7 +715,7 @@ static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, 
                          p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(),
                          A->tile_rec.as<uint32_t>(), B->tile_nnz_ptr.as<int>(), B->vals_t.as<VT>(), B->tile_rec_t.as<uint32_t>());
     } else if (wide && deep) {
-        PEM_S3_WIDE(true, nm.deep);
+        PEM_S3_WIDE(true, false, nm.deep);
     } else if (wide && p->s3_decode) {
         // The semirings other than plus-times skip the IDX32 and MARK specialisations (code size and build time): their shallow
         // plans always take the 64-bit, shuffle-search decode form.
@@ -626,7 +732,10 @@ static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, 
             PEM_S3_DECODE(false, false, nm.dec);
         }
     } else if (wide) {
-        PEM_S3_WIDE(false, nm.wide);
+        if (p->opt_s3_batch)
+            PEM_S3_WIDE(false, true, nm.wide);
+        else
+            PEM_S3_WIDE(false, false, nm.wide);
     } else {
         PEM_LAUNCH_NAMED(ctx, nm.base, (s3_accumulate_kernel<VT, SR>), grid_for(ntc * 16, 256), 256, p->pairs_offset.as<int>(), p->pairs_a.as<int>(),
                          p->pairs_b.as<int>(), (long long)ntc, p->c_tile_nnz_ptr.as<int>(), p->c_rowcolidx.as<uint8_t>(), p->c_vals.as<VT>(),
@@ -635,6 +744,7 @@ static void s3_launch(pem_ctx *ctx, pem_cplan *p, const S3Names &nm, bool deep, 
     }
 #undef PEM_S3_WIDE
 #undef PEM_S3_DECODE
+#undef PEM_S3_DECODE_BT
 }
 
 // PEM_OPT_S3_POISON (pem_test.h): C's values become a NaN bit pattern before step 3 runs, so that a test can tell an entry no
