@@ -8,9 +8,9 @@
 // with f' == f.
 //   gp     components_gp_kernel: element-wise, gp[v] = f[f[v]] into the gp buffer and into fnext, the buffer the hooks min into;
 //          raises the round's "changed" word where gp[v] < f[v] and clears the next round's word.
-//   hook   components_hook_kernel: the line walk of colour.hip -- one wave per line of 16 vertices, chunks of 64 entries,
-//          chunk_tile_of, the (major, minor) byte -- over the row line and, unless the caller promised a symmetric pattern, over the
-//          column line of the same 16 vertices (the column schedule of mxv.hip).  Every entry gathers gp[j] and mins it into its near
+//   hook   components_hook_kernel: the line walk of graph_internal.h (line_walk) -- one wave per line of 16 vertices, chunks of 64
+//          entries -- over the row line and, unless the caller promised a symmetric pattern, over the column line of the same 16
+//          vertices (the column schedule of mxv.hip).  Every entry gathers gp[j] and mins it into its near
 //          vertex's word of the wave's 16-word LDS area (LDS atomicMin).  After the walks lane v < 16 holds m[v] and, only where
 //          m[v] < gp[v], issues the global atomicMins into fnext[f[v]] and fnext[v]: fnext[f[v]] starts at gp[f[v]] <= gp[v], so a
 //          larger m[v] cannot lower either word.  The returning form raises "changed" only where a word really fell, so
@@ -19,23 +19,15 @@
 //          the three buffers rotating; nothing waits on another workgroup.  The host reads the round's word back (4 bytes per round).
 //   ids    components_roots_kernel: the flags label[v] == v; exclusive_scan_i32 turns them into ranks, its 64-bit total is the
 //          number of components; components_ids_kernel: id[v] = rank[label[v]].
-// The scratch is the colouring's (pem_ctx::colour_scratch, grow-only; every call that uses it waits before it returns): two buffers
-// of n + 1 int32 -- with d_label the three the rounds rotate through; the first then holds the flags and ranks -- and the two round
-// words.
+// The scratch is the graph routines' (pem_ctx::graph_scratch, carved by graph_carve): two buffers of n + 1 int32 -- with d_label the
+// three the rounds rotate through; the first then holds the flags and ranks -- and the two round words of graph_rounds.
 #include "spgemm_internal.h"
 #include "tiled_internal.h"
-#include "mx_internal.h"
-#include <climits>
+#include "graph_internal.h"
 
 using namespace pem;
 
 namespace {
-
-// what a walk reads of one orientation of a tiling: the arguments of frontier_kernel
-struct CompSide {
-    const int *lptr, *poff, *pbase, *pminor;
-    const uint8_t *rci;
-};
 
 __global__ void __launch_bounds__(256) components_iota_kernel(int *__restrict__ f, const long long n)
 {
@@ -57,59 +49,29 @@ __global__ void __launch_bounds__(256) components_gp_kernel(const int *__restric
     if (g < p) *changed = 1;
 }
 
-// One orientation's walk for line L: every entry's gp[far end] is folded into its near end's word of m (the wave's 16 words).
-template <bool COL>
-__device__ __forceinline__ void components_walk(const CompSide &S, const long long L, const int lane, const int *__restrict__ gp, int *m)
-{
-    const int p0 = S.lptr[L], p1 = S.lptr[L + 1];
-    if (p0 >= p1) return;
-    const int e_end = S.poff[p1];
-    int pc = p0;
-    for (int eb = S.poff[p0]; eb < e_end; eb += 64) {   // wave-uniform trip count
-        const int mp = pc + lane;
-        const bool lv = mp < p1;
-        const int my_off = lv ? S.poff[mp] : INT_MAX;
-        const int my_minor = lv ? S.pminor[mp] : 0;
-        int my_base = 0;
-        if constexpr (COL) my_base = lv ? S.pbase[mp] : 0;
-        const int e = eb + lane;
-        const int ti = chunk_tile_of(my_off, e);
-        const int t_off = __shfl(my_off, ti, 64), t_minor = __shfl(my_minor, ti, 64);
-        int t_base = 0;
-        if constexpr (COL) t_base = __shfl(my_base, ti, 64);
-        const int ti_last = __shfl(ti, 63, 64);
-        if (e < e_end) {
-            const unsigned rc = S.rci[COL ? t_base + (e - t_off) : e];
-            const long long j = 16 * (long long)t_minor + (rc & 15u);
-            atomicMin(&m[rc >> 4], gp[j]);
-        }
-        // the next chunk starts in the tile of entry eb + 63, or in the one after it
-        int pn = pc + ti_last;
-        if (eb + 64 < e_end && pn + 1 < p1 && S.poff[pn + 1] <= eb + 64) ++pn;
-        pc = pn;
-    }
-}
-
 // the hooks of one round: fnext (started as gp) takes m[v] at v and at f[v]; *changed is raised where a word fell
 template <bool SYM>
-__global__ void __launch_bounds__(256) components_hook_kernel(const CompSide R, const CompSide Cs, const long long nlines, const long long n,
-                                                              const int *__restrict__ f, const int *__restrict__ gp, int *fnext, int *changed)
+__global__ void __launch_bounds__(256) components_hook_kernel(const GraphArgs g, const int *__restrict__ f, const int *__restrict__ gp, int *fnext,
+                                                              int *changed)
 {
     __shared__ int s_m[4 * 16];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const long long L = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (L >= nlines) return;   // (wave-uniform)
-    bool any = R.lptr[L] < R.lptr[L + 1];
-    if constexpr (!SYM) any = any || Cs.lptr[L] < Cs.lptr[L + 1];
+    if (L >= g.nlines) return;   // (wave-uniform)
+    bool any = g.R.lptr[L] < g.R.lptr[L + 1];
+    if constexpr (!SYM) any = any || g.Cs.lptr[L] < g.Cs.lptr[L + 1];
     if (!any) return;   // (wave-uniform) no entry reaches this line: its words stay gp
     int *const m = s_m + wv * 16;
     if (lane < 16) m[lane] = INT_MAX;
     mx_wave_sync();
-    components_walk<false>(R, L, lane, gp, m);
-    if constexpr (!SYM) components_walk<true>(Cs, L, lane, gp, m);
+    // every entry's gp[far end] is folded into its near end's word of m (the wave's 16 words)
+    auto entry = [&](const unsigned major, const long long j) { atomicMin(&m[major], gp[j]); };
+    auto walk_on = [] { return false; };
+    line_walk<false>(g.R, L, lane, entry, walk_on);
+    if constexpr (!SYM) line_walk<true>(g.Cs, L, lane, entry, walk_on);
     mx_wave_sync();
     const long long v = 16 * L + lane;
-    if (lane < 16 && v < n) {
+    if (lane < 16 && v < g.n) {
         const int mv = m[lane];
         if (mv < gp[v]) {
             const int p = f[v];
@@ -139,18 +101,7 @@ extern "C" pem_status pem_tiled_components(pem_ctx *ctx, const pem_tiled *A, int
                                            int64_t *ncomponents, int32_t *rounds)
 {
     const char *fn = "pem_tiled_components";
-    if (!ctx || !A || !d_label || !ncomponents || !rounds) {
-        set_error("%s: null argument", fn);
-        return PEM_E_INVALID;
-    }
-    if (A->rows != A->cols) {
-        set_error("%s: the tiling is %d x %d; the components need a square one", fn, A->rows, A->cols);
-        return PEM_E_INVALID;
-    }
-    if (!fr_flag_ok(symmetric)) {
-        set_error("%s: symmetric must be 0 or 1 (got %d)", fn, symmetric);
-        return PEM_E_INVALID;
-    }
+    PEM_TRY(graph_enter(fn, ctx && A && d_label && ncomponents && rounds, A, "the components need", symmetric));
     const long long n = A->rows;
     if (Span(d_id, (size_t)n * 4).meets(Span(d_label, (size_t)n * 4))) {
         set_error("%s: d_id and d_label overlap", fn);
@@ -162,41 +113,27 @@ extern "C" pem_status pem_tiled_components(pem_ctx *ctx, const pem_tiled *A, int
     PEM_ENTER(ctx);
     if (!symmetric) PEM_TRY(ensure_mx_cols(ctx, A));
     // two buffers of n + 1 words (the scan writes its total behind the ranks), then the two round words
-    const size_t cbytes = (((size_t)n + 1) * sizeof(int) + 255) & ~size_t(255);
-    PEM_TRY(ctx->colour_scratch.reserve(2 * cbytes + 256));
-    char *const base = ctx->colour_scratch.as<char>();
-    int *buf[3] = {d_label, reinterpret_cast<int *>(base), reinterpret_cast<int *>(base + cbytes)};
-    int *const words = reinterpret_cast<int *>(base + 2 * cbytes);
-    const CompSide R{A->tile_rowptr.as<int>(), A->tile_nnz_ptr.as<int>(), nullptr, A->tile_colidx.as<int>(), A->rowcolidx.as<uint8_t>()};
-    const CompSide Cs{A->tile_colptr.as<int>(), A->mx_csc_off.as<int>(), A->mx_csc_base.as<int>(), A->tile_rowidx.as<int>(),
-                      A->mx_rci_t.as<uint8_t>()};
-    const long long nlines = A->tile_rows;
-    const unsigned egrid = grid_for((size_t)n, 256), lgrid = grid_for((size_t)nlines * 64, 256);
+    int *buf[3] = {d_label, nullptr, nullptr}, *words;
+    PEM_TRY(graph_carve(ctx, {{&buf[1], (size_t)n + 1}, {&buf[2], (size_t)n + 1}, {&words, 2}}));
+    const GraphArgs g = graph_args(A);
+    const unsigned egrid = grid_for((size_t)n, 256);
     PEM_TRY(zero_flags(ctx));
     PEM_LAUNCH(ctx, components_iota_kernel, egrid, 256, buf[0], n);
-    PEM_HIP(hipMemsetAsync(words, 0, 2 * sizeof(int), ctx->stream));
-    int *const h_changed = reinterpret_cast<int *>(ctx->h_scalars);
     int r = 0, at = 0;   // f is buf[at]
-    for (;;) {           // round r + 1 reads f, writes gp and fnext (the other two), raises words[r & 1] and clears the other word
-        int *const f = buf[at], *const gp = buf[(at + 1) % 3], *const fnext = buf[(at + 2) % 3];
-        int *const changed = words + (r & 1), *const changed_next = words + ((r + 1) & 1);
-        PEM_LAUNCH(ctx, components_gp_kernel, egrid, 256, f, gp, fnext, n, changed, changed_next);
-        if (symmetric)
-            PEM_LAUNCH_NAMED(ctx, "components_hook_kernel<rows>", (components_hook_kernel<true>), lgrid, 256, R, Cs, nlines, n, f, gp, fnext, changed);
-        else
-            PEM_LAUNCH_NAMED(ctx, "components_hook_kernel<both>", (components_hook_kernel<false>), lgrid, 256, R, Cs, nlines, n, f, gp, fnext, changed);
-        PEM_TRY(launch_status(ctx));
-        PEM_HIP(hipMemcpyAsync(h_changed, changed, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        PEM_HIP(hipStreamSynchronize(ctx->stream));
-        ++r;
-        at = (at + 2) % 3;
-        if (*h_changed == 0) break;
-        if (r >= n) {   // (with both orientations walked f_t[v] <= the smallest vertex within distance t of v)
-            if (symmetric) break;   // the promise was false
-            set_error("%s: internal: the labels still changed in round %d of at most %lld", fn, r, n);
-            return PEM_E_HIP;
-        }
-    }
+    // a round reads f, writes gp and fnext (the other two); with both orientations walked f_t[v] <= the smallest vertex within
+    // distance t of v, so only a false promise takes more than n rounds
+    PEM_TRY(graph_rounds(
+        ctx, fn, n, words, RoundPolicy{symmetric != 0, "%s: internal: the labels still changed in round %d of at most %lld"},
+        [&](int, int *changed, int *changed_next) {
+            int *const f = buf[at], *const gp = buf[(at + 1) % 3], *const fnext = buf[(at + 2) % 3];
+            PEM_LAUNCH(ctx, components_gp_kernel, egrid, 256, f, gp, fnext, n, changed, changed_next);
+            if (symmetric)
+                PEM_LAUNCH_NAMED(ctx, "components_hook_kernel<rows>", (components_hook_kernel<true>), line_grid(g), 256, g, f, gp, fnext, changed);
+            else
+                PEM_LAUNCH_NAMED(ctx, "components_hook_kernel<both>", (components_hook_kernel<false>), line_grid(g), 256, g, f, gp, fnext, changed);
+            at = (at + 2) % 3;
+        },
+        &r));
     if (at != 0) PEM_HIP(hipMemcpyAsync(d_label, buf[at], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
     // the ids: flags and ranks in the first scratch buffer, in place
     int *const rank = buf[1];

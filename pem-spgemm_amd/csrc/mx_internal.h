@@ -1,4 +1,4 @@
-// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip, sddmm.hip, frontier.hip, argmxv.hip, trsv.hip, colour.hip, components.hip; the wave sync also ilu0.hip):
+// mx_internal.h -- what the line walks over a tiling's rows or columns share (mxv.hip, spmm.hip, sddmm.hip, frontier.hip, argmxv.hip, trsv.hip; graph_internal.h, the one walk of colour.hip, components.hip and aggregate.hip; the wave sync also ilu0.hip):
 // the folds of the matrix-vector products and reductions, the wave sync around the staging area, the column-walk schedule, the
 // frontier's pack and mark, and the span of a dense row-major block.  SpMM folds with the
 // very functions mxv folds with, so column c of A (+).(x) X is bit for bit mxv of X's column c; SDDMM folds its chains with them too.

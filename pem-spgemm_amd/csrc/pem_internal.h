@@ -199,10 +199,9 @@ struct pem_ctx {
     pem::DevBuf fr_scratch;
     size_t fr_flags_off = 0;
     int64_t fr_lines = -1;
-    // pem_tiled_colour / pem_colour_order (colour.hip): the second colour buffer and the round words, resp. the sort's key and
-    // payload buffers; pem_tiled_components (components.hip): two parent buffers and the round words; pem_tiled_mis /
-    // pem_tiled_aggregate (aggregate.hip): state bytes, first-hop maxima, flags, a second aggregate buffer, the round words; grow-only
-    pem::DevBuf colour_scratch;
+    // the graph routines' scratch (colour.hip, components.hip, aggregate.hip), grow-only: every call lists its sub-buffers to
+    // graph_carve (graph_internal.h), which sizes this buffer and hands them out, and waits before it returns
+    pem::DevBuf graph_scratch;
     int dbg_trsv_split = 0;            // pem_test_trsv_split: 1 forces the triangular solve's and ILU(0)'s merge_width to 0 (one launch per level)
     int dbg_scan_force = 0;            // pem_debug_scan_i32: 0 automatic, 2 single-launch chained scan, 3 three-launch scan
     int dbg_scan_stall_ticket = -1;    // ... and the chained scan's block that stalls before it publishes

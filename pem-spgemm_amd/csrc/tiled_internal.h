@@ -162,7 +162,7 @@ __device__ __forceinline__ int tile_lower_bound(const int *__restrict__ m_rowptr
     return lo;
 }
 
-// ---- device: one wave per chunk of 64 consecutive tiles, one entry per lane (ewise.hip, select.hip; the search also trsv.hip, colour.hip) ----
+// ---- device: one wave per chunk of 64 consecutive tiles, one entry per lane (ewise.hip, select.hip; the search also trsv.hip and line_walk of graph_internal.h) ----
 // the wave's LDS writes visible to the whole wave (each wave keeps its own LDS rows: no workgroup barrier)
 __device__ __forceinline__ void wave_lds_sync()
 {
