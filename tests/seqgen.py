@@ -14,7 +14,7 @@ every kind in both value types).
 
 Text form: one JSON array [op, [ids], {arguments}] per line (dumps / loads); tools/seq_replay.py reads it back.
 
-Two operation sets.  A seed below SET2_FROM draws from the first set (_Gen), and program() returns for it what it returned when
+Three operation sets.  A seed below SET2_FROM draws from the first set (_Gen), and program() returns for it what it returned when
 the sequence test was added (tests/golden/seq_program_digests.json holds the digests of SEEDS' programs).  A seed from SET2_FROM
 on draws from the second set (_Gen2; SEEDS2 is its committed list): everything the first has, plus
   derivations with a refresh   apply, scale, transpose, extract, assign, kron, concat, build / build_device (keep_map), ilu0,
@@ -36,6 +36,27 @@ zero pivots, infinities and NaN by bits), so no special value is left out of the
 Left out, because the header lets the library round differently from the references there: runs of duplicates longer than
 BUILD_INORDER_MAX under plus and times (they may be regrouped; the other six dup ops get such runs), and set_values_sampled_mxm
 with accumulate under plus_pair (a tile pair's count enters in one addition).  Also left out: refusals of trsv_info / ilu0_info.
+
+A seed from SET3_FROM on draws from the third set (_Gen3; SEEDS3 is its committed list): everything the second has, plus
+  graph readers                colour (seeds 0 and 12345, the "equal" and "ties" priority arrays of test_gpu_colour.py, each from the
+                               host and from the device), colour_order (on a colouring, and on component ids with ncolours =
+                               ncomponents), components (with and without ids), mis (distances 1 and 2), aggregate (with and
+                               without roots)
+  solvers                      krylov_create (CG or BiCGStab; none, diag, lu, or amg through pem_krylov_create_amg; check_every is
+                               an option of create: 1, 3, 8 or above max_iters), krylov_solve (with and without history and guess),
+                               krylov_close, tiled_solve (the Tiled.solve convenience)
+  hierarchies                  amg_create (tests/amgcases.py's option grid, refreshable 0 / 1), amg_refresh, amg_apply, amg_info,
+                               amg_level (a borrowed A_l, P_l or R_l handed to mxv, reduce, export_csr or a graph routine), amg_close
+in two pools of their own (MAX_SOLVERS, MAX_HIERARCHIES), and the refusals of REFUSALS3.  The rules the third set keeps: symmetric =
+1 only where the model knows the pattern to be symmetric; no tiling destroyed that a live solver or hierarchy names, no hierarchy
+that a live solver names; a borrowed level handle is read within its record only.  Solves run on whatever values the program wrote
+last (krylovref follows the header's NONFINITE and BREAKDOWN line by line); max_iters is at most 30.  Graphs and systems: the
+matgen cases, colourref.built_graphs(), tests/amgcases.py's systems (krylovcases' among them), the smallest weighted most.  Three
+scenarios (start_scenario3): the life of a solver (ilu0, krylov_create lu, solve, a writer on A, set_values_from_ilu0, solve, a graph
+routine on another tiling, solve), the life of a hierarchy (amg_create, krylov_create amg, solve, a writer on A, amg_refresh, solve,
+trim or reserve, amg_apply, amg_refresh, amg_info), the reorder (colour, colour_order, extract with the permutation as both lists,
+ilu0, trsv_info, a solver on the reordered matrix and its solve).  r_provenance is an owed draw as r_needy's: the third set's kinds
+leave the second's derivations fewer draws, so a program makes the derived tilings its graph routines have not met yet.
 
 The second set's pool holds MAX_TILINGS2 = 10 tilings (more kinds of derived tilings have to be alive at once).  Most of its draws
 go to r_needy, which serves the (kind, value type) a program ran least in a fixed round that every program enters at its own
@@ -109,6 +130,36 @@ MAX_SAMPLED_WORK = 300_000             # matched-pair candidates of one sampled 
 BOOST2 = dict(build_refresh_no_map=8.0, build_refresh_wrong_nnz=3.0, concat_swapped=3.0, ilu0_info=14.0, lu_solve=9.0, kron=4.0, ilu0=6.0, assign=3.0, concat=1.5, trsv_info=30.0, bfs=14.0, bfs_parents=12.0, apply=1.5, transpose=1.5, extract=2.0, select_topk=1.5,
               set_values_from_extract=2.0)
 
+# ---- the third operation set (_Gen3): seeds from SET3_FROM on draw from it; SEEDS3 is dealt to the context kinds as SEEDS is
+SET3_FROM = 2000
+# How SEEDS3 was found: as SEEDS2 was -- with the weights below, runs of 24 consecutive seeds starting at 2001, 2101, ... were tried
+# against test_third_set_coverage_conditions (tests/test_seq_cpu.py); three of the first five meet every condition (2101, 2201, 2301;
+# 2001 has no graph routine on a tiling made from a plan, 2401 no mis on a non-square tiling), and 2101 was taken.  After a change to
+# the weights or a draw: search again the same way, then take the figures of the third set's controls in seqcontrol.NEGATIVE from
+# seqcontrol.first_divergence.
+SEEDS3 = tuple(range(2101, 2125))
+MAX_SOLVERS, MAX_HIERARCHIES = 3, 2     # the third set's two pools
+GRAPH_SOURCES = ("k70_in_75", "k131", "path_203_one_way")            # colourref.built_graphs(): window overflow, column direction
+SYSTEMS = ("spd_dense_1", "spd_dense_15", "spd_dense_17", "spd_dense_33", "diag_50", "spd_tridiagonal_200", "gen_tridiagonal_200", "gen_dense_33",
+           "poisson_40", "spd_tridiagonal_4097")                     # tests/amgcases.py's (krylovcases' among them), the smallest weighted most
+SYSTEM_WEIGHT = (1, 1.5, 3, 3, 3, 3, 2, 2, 1.5, 0.05)
+MAX_ITERS3 = (0, 1, 2, 3, 5, 8, 13, 30)
+RTOLS, ATOLS = (1e-8, 1e-4, 1e-2), (0.0, 0.0, 1e-3)
+AMG_SMOOTH, AMG_COARSE, AMG_SWEEPS = (0, 1), (8, 40), ((1, 4), (2, 1))   # tests/amgcases.py's option grid
+# size guards of the third set: entries of a graph (colourref and aggref walk them in Python), entries of a solve's A times max_iters
+# (of its factor: trsvref walks them in Python), the entries and the scalar products (sum of squared row lengths) of a hierarchy's A
+MAX_GRAPH_NNZ, MAX_SOLVE_WORK, MAX_LU_WORK, MAX_AMG_NNZ, MAX_AMG_PRODUCTS = 30_000, 250_000, 60_000, 13_000, 120_000
+GRAPH_KINDS = sm.GRAPH_KINDS
+SOLVER_KINDS = ("krylov_create", "krylov_solve", "krylov_close", "tiled_solve")
+AMG_KINDS = ("amg_create", "amg_refresh", "amg_apply", "amg_info", "amg_level", "amg_close")
+KINDS3_T = GRAPH_KINDS + SOLVER_KINDS + AMG_KINDS
+NEEDY3_SHARE = dict(krylov_solve=3.0, amg_apply=1.5, amg_refresh=2.0, amg_level=1.5, krylov_close=0.7, amg_close=0.6)
+PRIORITIES = ("seed_0", "seed_12345", "equal_host", "equal_device", "ties_host", "ties_device")
+METHOD_PRECOND = tuple((m, p) for m in ("cg", "bicgstab") for p in ("none", "diag", "lu", "amg"))
+REFUSALS3 = ("colour_nonsquare", "components_nonsquare", "mis_nonsquare", "aggregate_nonsquare", "krylov_nonsquare", "mis_distance_3",
+             "lu_no_factor", "factor_other_precond", "factor_other_dtype", "amg_other_matrix", "amg_missing_diag", "refresh_not_refreshable",
+             "solve_wrong_form", "priority_overlap")
+
 KINDS_T = ("from_coo", "from_csr", "from_coo_device", "set_values", "set_values_device", "set_values_from_cplan", "set_values_from_ewise",
            "set_values_from_select", "set_values_sddmm", "from_cplan", "ewise", "select", "sddmm", "mxv", "reduce", "spmm", "save_load", "close")
 KINDS_P = ("plan_create", "step1", "step2", "step3", "spgemm", "set_semiring", "set_option", "export_csr", "export_coo", "plan_close")
@@ -140,6 +191,8 @@ def record_dtype(model, rec):
     if "dtype" in a:
         return a["dtype"]
     h = ids[0]
+    if h in model.k or h in model.h:     # a solver or a hierarchy: the value type of its A
+        h = (model.k[h] if h in model.k else model.h[h]).a
     return sm.dtname(model.p[h].A.dtype if h in model.p else model.t[h].dtype)
 
 
@@ -1194,20 +1247,485 @@ class _Gen2(_Gen):
         return getattr(self, "r_" + cat)(dtype)
 
 
+class _Gen3(_Gen2):
+    """the third operation set: everything _Gen2 draws, plus the graph routines, the solvers and the hierarchies"""
+
+    def __init__(self, seed):
+        super().__init__(seed)
+        self.nk = self.nh = 0
+        self.turn3 = (int(seed) * 13) % (2 * len(KINDS3_T))
+        self.script3, self.cast3, self.kind3, self.stalls3 = [], {}, None, 0
+        self.started3, self.args3 = {}, None
+        self.sched_by = {}             # tiling -> who built its column schedule ("reader" / "graph")
+        self.last_graph = None           # the kind of the last graph call
+        self.after_trim = False          # a trim ran and no graph call since
+
+    # ---- the pools -------------------------------------------------------------------------------------------------------------
+    def named(self, tid):
+        if tid in self.cast3.values() or any(tid in (K.a, K.pre) for K in self.m.k.values()) or any(tid == H.a for H in self.m.h.values()):
+            return True
+        return super().named(tid)
+
+    def held(self, hid):
+        """a live solver names this hierarchy, or a scenario works on it"""
+        return hid in self.cast3.values() or any(K.pre == hid for K in self.m.k.values())
+
+    def new_k(self):
+        self.nk += 1
+        return f"k{self.nk}"
+
+    def new_h(self):
+        self.nh += 1
+        return f"h{self.nh}"
+
+    def system_convert(self, dtype, graph=False):
+        op = self.least(("from_coo", "from_csr", "from_coo_device"), dtype)
+        src = {"graph": self.pick(GRAPH_SOURCES)} if graph else {"system": self.pick(SYSTEMS, SYSTEM_WEIGHT)}
+        return (op, (), dict(out=self.new_t(), src=src, dtype=dtype, transpose=False))
+
+    def square_convert(self, dtype):
+        """a third of the square matrices are the Krylov / multigrid tests' systems, some the colouring tests' graphs"""
+        x = self.rng.random()
+        return self.system_convert(dtype, graph=x < 0.1) if x < 0.45 else super().square_convert(dtype)
+
+    def room(self, dtype):
+        """a record that makes room for a new tiling, or None where there is room"""
+        return self.r_close(dtype) if len(self.m.t) >= self.MAX_T else None
+
+    # ---- graph routines ----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def graphable(T):
+        return T.rows == T.cols and T.nnz <= MAX_GRAPH_NNZ and T.rows <= MAX_DIM2
+
+    def graph_args(self, kind, T, name):
+        sym = sm.symmetric(T) and self.chance(0.3)
+        a = dict(symmetric=sym)
+        if kind in ("colour", "mis", "aggregate") or (kind == "colour_order" and self.cycle("order_of", ("colour", "components")) == "colour"):
+            p = self.cycle("prio_" + kind, PRIORITIES).split("_")
+            a["prio"] = ["seed", int(p[1])] if p[0] == "seed" else p
+        if kind == "colour_order":
+            a["of"] = "colour" if "prio" in a else "components"
+        elif kind == "components":
+            a["ids"] = self.cycle("cc_ids", (True, False))
+        elif kind == "mis":
+            a["distance"] = self.cycle("mis_distance", (1, 2))
+        elif kind == "aggregate":
+            a["roots"] = self.cycle("agg_roots", (True, False))
+        return a
+
+    def sched_state(self, i):
+        return self.sched_by.get(i, "none") if "mx_cols" in self.m.t[i].built else "none"
+
+    def n_graph(self, dtype, kind, i=None):
+        ts = [i] if i is not None else self.of(dtype, self.graphable)
+        if not ts:
+            return self.room(dtype) or self.square_convert(dtype)
+        prov = lambda j: (self.m.t[j].prov or ("plain",))[0]
+        w = [1.0 / ((1 + self.count.get((kind, self.sched_state(j)), 0)) ** 2 * (1 + self.count.get((kind, prov(j)), 0)) ** 2
+                    * (1 + self.count.get(("graph", prov(j)), 0))) for j in ts]
+        i = self.pick(ts, w)
+        a = self.graph_args(kind, self.m.t[i], kind)
+        if not a["symmetric"]:
+            self.count[(kind, self.sched_state(i))] = self.count.get((kind, self.sched_state(i)), 0) + 1
+        for k in (kind, "graph"):
+            self.count[(k, prov(i))] = self.count.get((k, prov(i)), 0) + 1
+        return (kind, (i,), a)
+
+    def r_provenance(self, dtype):
+        """an owed draw, as r_needy's: a graph routine on a tiling of a provenance no graph routine of this program has met -- or,
+        where none is alive, a step towards one (the third set's own kinds leave the second set's derivations fewer draws)"""
+        missing = [k for k in sm.KINDS2 + ("cplan",) if not self.count.get(("graph", k), 0)]
+        if not missing:
+            return None
+        kind = missing[(self.turn3 + len(missing)) % len(missing)]
+        alive = [i for i in self.tilings(self.graphable) if (self.m.t[i].prov or ("",))[0] == kind]
+        if alive:
+            return self.n_graph(dtype, self.next_graph_kind() if self.last_graph else "colour", self.pick(alive))
+        if len(self.m.t) >= self.MAX_T:
+            return self.r_close(dtype)
+        squares = self.of(dtype, lambda T: self.graphable(T) and T.nnz <= 3000 and T.rows <= 700)
+        if kind == "cplan":
+            ps = self.plans(lambda p: p.A.rows == p.B.cols and self.graphable(p.A))
+            cur = [i for i in ps if self.m.current(self.m.p[i]) and len(self.m.p[i].C[1]) <= MAX_GRAPH_NNZ]
+            if cur:
+                return ("from_cplan", (self.pick(cur),), dict(out=self.new_t(), transpose=self.chance(0.5)))
+            if ps:
+                return ("spgemm", (self.pick(ps),), {})
+            if len(self.m.p) >= MAX_PLANS:
+                return self.r_plan_close(dtype)
+            squares = [i for i in squares if self.m.products(self.m.t[i], self.m.t[i]) <= MAX_PRODUCTS // 4]
+            return ("plan_create", (i := self.pick(squares), i, None), dict(out=self.new_p(), complement=False, lo=0, hi=-1, semiring="plus_times")) \
+                if squares else None
+        if kind == "kron":
+            small = self.of(dtype, lambda T: T.rows == T.cols and T.rows <= 48 and T.nnz <= 150)
+            if not small:
+                n = int(self.pick((9, 16)))
+                return (self.least(("from_coo", "from_csr", "from_coo_device"), dtype), (),
+                        dict(out=self.new_t(), src={"randdiag": [self.seed(), n, 2 * n]}, dtype=dtype, transpose=False))
+            return ("kron", (self.pick(small), self.pick(small)), dict(out=self.new_t(), op=self.cycle("kron_op", kronref.BINOPS)))
+        if not squares:
+            return None
+        i = self.pick(squares)
+        if kind == "concat":
+            return ("concat", (i, None, None, i), dict(out=self.new_t(), dtype=sm.dtname(self.m.t[i].dtype), grid=[2, 2],
+                                                      row_sizes=[self.m.t[i].rows] * 2, col_sizes=[self.m.t[i].cols] * 2))
+        if kind == "extract":
+            return self.d_extract_all(i)
+        if kind == "assign":
+            return ("assign", (i, i), dict(out=self.new_t(), rows=None, cols=None, accum=self.cycle("assign_accum", (None,) + applyref.BINOPS)))
+        return getattr(self, "d_" + kind)(dtype, i)
+
+    def next_graph_kind(self):
+        """the graph routine that followed the last one least (or, after a trim, that ran first after one least)"""
+        key = "after_trim" if self.after_trim else self.last_graph
+        kinds = [k for k in GRAPH_KINDS if k != key]
+        return min(kinds, key=lambda k: (self.count.get(((k, key), "after"), 0), self.rng.random()))
+
+    # ---- solvers -------------------------------------------------------------------------------------------------------------------
+    def system_ok(self, T, max_iters=1):
+        return T.rows == T.cols and T.nnz > 0 and T.nnz * max(max_iters, 1) <= MAX_SOLVE_WORK
+
+    def amg_ok(self, T):
+        return T.rows == T.cols and 0 < T.nnz <= MAX_AMG_NNZ and sm.ilu0_cost(T) <= MAX_AMG_PRODUCTS and sm.missing_diag(T)[0] == 0
+
+    def solver_opts(self, nnz, fnnz=0):
+        its = [k for k in MAX_ITERS3 if nnz * max(k, 1) <= MAX_SOLVE_WORK and fnnz * max(k, 1) <= MAX_LU_WORK] or [0]
+        max_iters = int(self.cycle("max_iters", its))
+        every = self.cycle("check_every", ("1", "3", "8", "above"))
+        return dict(max_iters=max_iters, check_every=max_iters + 5 if every == "above" else int(every), rtol=self.pick(RTOLS), atol=self.pick(ATOLS))
+
+    def n_krylov_create(self, dtype, a=None, pair=None, pre=None):
+        if len(self.m.k) >= MAX_SOLVERS:
+            return self.n_krylov_close(dtype, force=True)
+        method, pc = pair or self.cycle("method_precond", [f"{m} {p}" for m, p in METHOD_PRECOND]).split()
+        ts = [a] if a is not None else self.of(dtype, self.system_ok)
+        if pc == "amg" and pre is None:
+            hs = [(h, H.a) for h, H in self.m.h.items() if H.a in ts]
+            if not hs:
+                return self.n_amg_create(dtype)
+            pre, a = self.pick(hs)
+        elif pc == "lu" and pre is None:
+            fs = [(f, F.prov[1]) for f, F in self.m.t.items() if F.prov is not None and F.prov[0] == "ilu0" and F.prov[1] in ts and self.solvable(F)]
+            if not fs:
+                cand = [i for i in ts if self.factorable(self.m.t[i])]
+                return self.room(dtype) or (("ilu0", (self.pick(cand),), dict(out=self.new_t())) if cand else self.system_convert(dtype))
+            pre, a = self.pick(fs)
+        elif a is None:
+            if not ts:
+                return self.room(dtype) or self.system_convert(dtype)
+            shared = [i for i in ts if any(K.a == i for K in self.m.k.values())]
+            a = self.pick(shared) if shared and self.chance(0.35) else self.pick(ts, [1.0 / (1 + self.m.t[i].nnz) ** 0.5 for i in ts])
+        A = self.m.t[a]
+        opts = self.solver_opts(A.nnz, self.m.t[pre].nnz if pc == "lu" else 3 * A.nnz if pc == "amg" else 0)
+        return ("krylov_create", (a, pre), dict(out=self.new_k(), method=method, precond=pc, **opts))
+
+    def solve_args(self):
+        return dict(x0=self.cycle("x0", (True, False)), history=self.cycle("history", (True, False)), seed=self.seed(), special=self.chance(0.15))
+
+    def n_krylov_solve(self, dtype, k=None):
+        ks = [k] if k is not None else [k for k, K in self.m.k.items() if sm.dtname(self.m.t[K.a].dtype) == dtype]
+        if not ks:
+            return self.n_krylov_create(dtype)
+        # the solver that solved least, those whose A, factor or hierarchy changed since first
+        return ("krylov_solve", (min(ks, key=lambda k: (len(self.m.k[k].trail), self.rng.random())),), self.solve_args())
+
+    def n_krylov_close(self, dtype, force=False):
+        ks = [k for k, K in self.m.k.items() if k not in self.cast3.values() and (force or sm.dtname(self.m.t[K.a].dtype) == dtype)]
+        ks = [k for k in ks if self.m.k[k].trail] or ([] if not force else ks)      # (a solver that never solved is closed last)
+        return ("krylov_close", (self.pick(ks),), {}) if ks else None
+
+    def n_tiled_solve(self, dtype):
+        pc = self.cycle("tiled_precond", ("none", "ilu0"))
+        ts = self.of(dtype, lambda T: self.system_ok(T) and (pc == "none" or (self.factorable(T) and len(self.m.t) < self.MAX_T)))
+        if not ts:
+            return self.room(dtype) or self.system_convert(dtype)
+        a = self.pick(ts)
+        opts = self.solver_opts(self.m.t[a].nnz, self.m.t[a].nnz if pc == "ilu0" else 0)
+        return ("tiled_solve", (a,), dict(method=self.cycle("tiled_method", ("cg", "bicgstab")), precond=pc, **opts, **self.solve_args()))
+
+    # ---- hierarchies -----------------------------------------------------------------------------------------------------------------
+    def n_amg_create(self, dtype, a=None, refreshable=None):
+        if len(self.m.h) >= MAX_HIERARCHIES:
+            return self.n_amg_close(dtype, force=True)
+        ts = [a] if a is not None else self.of(dtype, self.amg_ok)
+        if not ts:
+            return self.room(dtype) or self.system_convert(dtype)
+        a = self.pick(ts)
+        sweeps, coarse_sweeps = self.cycle("amg_sweeps", AMG_SWEEPS)
+        if refreshable is None:
+            refreshable = self.cycle("refreshable", (1, 0, 1))
+        return ("amg_create", (a,), dict(out=self.new_h(), smooth=int(self.cycle("amg_smooth", AMG_SMOOTH)), coarse_size=int(self.cycle("amg_coarse", AMG_COARSE)),
+                                         sweeps=int(sweeps), coarse_sweeps=int(coarse_sweeps), symmetric=bool(sm.symmetric(self.m.t[a]) and self.chance(0.6)),
+                                         refreshable=int(refreshable)))
+
+    def hierarchies(self, dtype, pred=lambda H: True):
+        return [h for h, H in self.m.h.items() if sm.dtname(self.m.t[H.a].dtype) == dtype and pred(H)]
+
+    def n_amg_refresh(self, dtype):
+        hs = self.hierarchies(dtype, lambda H: H.opts["refreshable"])
+        return ("amg_refresh", (self.pick(hs),), {}) if hs else self.n_amg_create(dtype, refreshable=1)
+
+    def n_amg_apply(self, dtype):
+        hs = self.hierarchies(dtype)
+        return ("amg_apply", (self.pick(hs),), self.vals_args()) if hs else self.n_amg_create(dtype)
+
+    def n_amg_info(self, dtype):
+        hs = self.hierarchies(dtype)
+        return ("amg_info", (self.pick(hs),), {}) if hs else self.n_amg_create(dtype)
+
+    def n_amg_level(self, dtype):
+        hs = self.hierarchies(dtype)
+        if not hs:
+            return self.n_amg_create(dtype)
+        h = self.pick(hs)
+        H = self.m.h[h]
+        which = self.cycle("level_which", ("A", "P", "R"))
+        if len(H.levels) == 1:
+            which = "A"
+        level = int(self.rng.integers(0, len(H.levels) - (which != "A")))
+        T = self.m.level_tiling(H, level, which)
+        what = self.cycle("level_reader", ("mxv", "reduce", "export_csr", "graph") if which == "A" and self.graphable(T) else ("mxv", "reduce", "export_csr"))
+        if what == "graph":
+            what = self.cycle("level_graph", ("colour", "components", "mis", "aggregate"))
+            args = self.graph_args(what, T, what)
+        elif what == "export_csr":
+            args = {}
+        else:
+            tr, acc = self.chance(0.5), self.chance(0.4)
+            args = dict(semiring=self.pick(SEMIRINGS), transpose=tr, accumulate=acc, **self.vals_args()) if what == "mxv" else \
+                dict(op=self.pick(ewiseref.OPS), dim="cols" if tr else "rows", accumulate=acc, **self.vals_args())
+        return ("amg_level", (h,), dict(level=level, which=which, reader=[what, args]))
+
+    def n_amg_close(self, dtype, force=False):
+        hs = [h for h in (self.m.h if force else self.hierarchies(dtype)) if not self.held(h)]
+        if hs:
+            return ("amg_close", (self.pick(hs),), {})
+        return self.n_krylov_close(dtype, force=True) if force else None
+
+    def r_needy3(self, dtype):
+        """r_needy over the third set's kinds: the (kind, value type) this program ran least (a solve counts a third), the first the
+        pool allows; ties go round from a place every program has of its own"""
+        cells = [(k, d) for k in KINDS3_T for d in ("f64", "f32")]
+        order = sorted(range(len(cells)), key=lambda c: (self.count.get(cells[c], 0) / NEEDY3_SHARE.get(cells[c][0], 1.0), (c - self.turn3) % len(cells)))
+        for c in order[:10]:
+            k, d = cells[c]
+            if k in GRAPH_KINDS:
+                # the routine the round asks for; where the order of the graph calls has a gap, the one that fills it
+                rec = self.n_graph(d, self.next_graph_kind() if self.last_graph and self.chance(0.5) else k)
+            else:
+                rec = getattr(self, "n_" + k)(d)
+            if rec is not None:
+                return rec
+        return None
+
+    # ---- deliberate refusals ---------------------------------------------------------------------------------------------------------
+    def r_refusal(self, dtype):
+        if self.chance(0.45):
+            return super().r_refusal(dtype)
+        m = self.m
+        oblong = [i for i, T in m.t.items() if T.rows != T.cols]
+        square = [i for i, T in m.t.items() if self.graphable(T)]
+        systems = [i for i, T in m.t.items() if self.system_ok(T)]
+        holed = [i for i, T in m.t.items() if T.rows == T.cols and sm.missing_diag(T)[0] and T.nnz <= MAX_AMG_NNZ]
+        diag = lambda T: T.rows == T.cols and sm.missing_diag(T)[0] == 0 and T.nnz <= MAX_TRSV_NNZ
+        factors = [(i, f) for i in systems for f, F in m.t.items() if diag(F) and F.rows == m.t[i].rows]
+        same = [(i, f) for i, f in factors if m.t[f].dtype == m.t[i].dtype]
+        other = [(i, f) for i, f in factors if m.t[f].dtype != m.t[i].dtype]
+        foreign = [(i, h) for h, H in m.h.items() for i in systems if i != H.a and m.t[i].dtype == m.t[H.a].dtype]
+        fixed = [h for h, H in m.h.items() if not H.opts["refreshable"]]
+        single = [k for k, K in m.k.items() if m.t[K.a].dtype == np.float32]
+        opts = ["colour_nonsquare", "components_nonsquare", "mis_nonsquare", "aggregate_nonsquare", "krylov_nonsquare"] if oblong else []
+        opts += ["mis_distance_3", "priority_overlap"] if square else []
+        opts += ["lu_no_factor"] if systems else []
+        opts += ["factor_other_precond"] if same else []
+        opts += ["factor_other_dtype"] if other else []
+        opts += ["amg_other_matrix"] if foreign else []
+        opts += ["amg_missing_diag"] if holed else []
+        opts += ["refresh_not_refreshable"] if fixed else []
+        opts += ["solve_wrong_form"] if single else []
+        if not opts:
+            return super().r_refusal(dtype)
+        why = self.least(opts, "refusal")
+        plain = dict(symmetric=False, expect=why)
+        kopts = dict(max_iters=5, check_every=8, rtol=1e-8, atol=0.0, expect=why)
+        if why.endswith("_nonsquare") and why != "krylov_nonsquare":
+            kind = why[:-10]
+            extra = dict(colour=dict(prio=["seed", 0]), components=dict(ids=True), mis=dict(prio=["seed", 0], distance=2), aggregate=dict(prio=["seed", 0], roots=True))
+            return (kind, (self.pick(oblong),), dict(plain, **extra[kind]))
+        if why == "krylov_nonsquare":
+            return ("krylov_create", (self.pick(oblong), None), dict(kopts, out=self.new_k(), method=self.pick(("cg", "bicgstab")), precond="none"))
+        if why == "mis_distance_3":
+            return ("mis", (self.pick(square),), dict(plain, prio=["seed", 0], distance=3))
+        if why == "priority_overlap":
+            return ("colour", (self.pick(square),), dict(plain, prio=[self.pick(("equal", "ties")), "device"], overlap=True))
+        if why == "lu_no_factor":
+            return ("krylov_create", (self.pick(systems), None), dict(kopts, out=self.new_k(), method=self.pick(("cg", "bicgstab")), precond="lu"))
+        if why in ("factor_other_precond", "factor_other_dtype"):
+            i, f = self.pick(same if why == "factor_other_precond" else other)
+            pc = self.pick(("none", "diag")) if why == "factor_other_precond" else "lu"
+            return ("krylov_create", (i, f), dict(kopts, out=self.new_k(), method=self.pick(("cg", "bicgstab")), precond=pc))
+        if why == "amg_other_matrix":
+            i, h = self.pick(foreign)
+            return ("krylov_create", (i, h), dict(kopts, out=self.new_k(), method=self.pick(("cg", "bicgstab")), precond="amg"))
+        if why == "amg_missing_diag":
+            return ("amg_create", (self.pick(holed),), dict(out=self.new_h(), smooth=1, coarse_size=8, sweeps=1, coarse_sweeps=4, symmetric=False,
+                                                           refreshable=1, expect=why))
+        if why == "refresh_not_refreshable":
+            return ("amg_refresh", (self.pick(fixed),), dict(expect=why))
+        return ("krylov_solve", (self.pick(single),), dict(self.solve_args(), wrong_form=True, expect=why))
+
+    # ---- scenarios of the third set: the life of a solver, the life of a hierarchy, the reorder ------------------------------------------
+    SCRIPTS3 = dict(solver=("ilu0", "create_lu", "solve", "write", "refresh_factor", "solve", "graph_other", "solve"),
+                    hierarchy=("amg_create", "create_amg", "solve", "write", "amg_refresh", "solve", "ctx", "amg_apply", "amg_refresh", "amg_info"),
+                    reorder=("colour", "colour_order", "extract", "ilu0", "trsv_info", "create_lu", "solve"))
+
+    def start_scenario3(self):
+        kinds = [k for k in SCRIPTS3_ORDER if self.started3.get(k, 0) < 1]
+        if not kinds:
+            return
+        kind = kinds[(self.turn3 + len(self.prog)) % len(kinds)]
+        small = lambda T: T.nnz > 0 and self.factorable(T) and T.nnz * 30 <= MAX_LU_WORK
+        if kind == "solver":
+            ts = self.tilings(small)
+        elif kind == "hierarchy":
+            ts = self.tilings(lambda T: self.amg_ok(T) and T.nnz * 3 * 8 <= MAX_LU_WORK * 4)
+        else:
+            ts = self.tilings(lambda T: small(T) and T.rows <= MAX_LIST)
+        if ts:
+            self.kind3, self.script3, self.cast3, self.stalls3 = kind, list(self.SCRIPTS3[kind]), {"A": self.pick(ts)}, 0
+            self.started3[kind] = self.started3.get(kind, 0) + 1
+
+    def end_scenario3(self):
+        self.script3, self.cast3, self.kind3 = [], {}, None
+        return None
+
+    def r_script3(self, dtype):
+        c, m = self.cast3, self.m
+        if any((v not in m.t and v not in m.k and v not in m.h) for v in c.values()) or self.stalls3 > 10:
+            return self.end_scenario3()
+        what = self.script3[0]
+        base = c.get("R", c["A"])            # (the reorder's later steps work on the reordered matrix)
+        dtype = sm.dtname(m.t[c["A"]].dtype)
+        rec = None
+        if what in ("ilu0", "extract") and len(m.t) >= self.MAX_T:
+            self.stalls3 += 1
+            return self.r_close(dtype)
+        if what in ("create_lu", "create_amg") and len(m.k) >= MAX_SOLVERS:
+            self.stalls3 += 1
+            return self.n_krylov_close(dtype, force=True)
+        if what == "amg_create" and len(m.h) >= MAX_HIERARCHIES:
+            self.stalls3 += 1
+            return self.n_amg_close(dtype, force=True)
+        if what == "ilu0":
+            rec = ("ilu0", (base,), dict(out=self.new_t()))
+            c["F"] = rec[2]["out"]
+        elif what in ("create_lu", "create_amg"):
+            pair = (self.cycle("scenario_method", ("cg", "bicgstab")), what[7:])
+            rec = self.n_krylov_create(dtype, a=base, pair=pair, pre=c["F"] if what == "create_lu" else c["H"])
+            c["K"] = rec[2]["out"]
+        elif what == "solve":
+            rec = ("krylov_solve", (c["K"],), self.solve_args())
+        elif what == "write":
+            rec = _Gen.r_writer(self, None, c["A"])
+        elif what == "refresh_factor":
+            rec = ("set_values_from_ilu0", (c["F"], base), {})
+        elif what == "graph_other":
+            others = [i for i in self.of(dtype, self.graphable) + self.tilings(self.graphable) if i not in c.values()]
+            if not others:
+                self.stalls3 += 1
+                return self.room(dtype) or self.square_convert(dtype)
+            rec = self.n_graph(dtype, self.next_graph_kind() if self.last_graph else "colour", others[0] if self.chance(0.5) else self.pick(others))
+        elif what == "amg_create":
+            rec = self.n_amg_create(dtype, a=c["A"], refreshable=1)
+            c["H"] = rec[2]["out"]
+        elif what in ("amg_refresh", "amg_info"):
+            rec = (what, (c["H"],), {})
+        elif what == "amg_apply":
+            rec = (what, (c["H"],), self.vals_args())
+        elif what == "ctx":
+            rec = ("trim", (), {}) if self.cycle("scenario_ctx", ("trim", "reserve")) == "trim" else ("reserve", (), dict(bytes=int(self.pick(RESERVES))))
+        elif what == "colour":
+            p = self.cycle("prio_colour", PRIORITIES).split("_")
+            self.args3 = dict(symmetric=False, prio=["seed", int(p[1])] if p[0] == "seed" else p)
+            rec = ("colour", (base,), dict(self.args3))
+        elif what == "colour_order":
+            rec = ("colour_order", (base,), dict(self.args3, of="colour"))
+        elif what == "extract":              # the permutation as both lists, as Tiled.reorder_by_colour hands it to extract
+            perm = [int(v) for v in m.apply(("colour_order", (base,), dict(self.args3, of="colour"))).out[1]]
+            rec = ("extract", (base,), dict(out=self.new_t(), rows=["device", perm], cols=["device", perm]))
+            c["R"] = rec[2]["out"]
+        elif what == "trsv_info":
+            rec = ("trsv_info", (c["F"],), dict(uplo=self.cycle("uplo", ("lower", "upper"))))
+        if rec is None:
+            return self.end_scenario3()
+        self.script3 = self.script3[1:]
+        if not self.script3:
+            self.count[(self.kind3, "scenario3")] = self.count.get((self.kind3, "scenario3"), 0) + 1
+            self.end_scenario3()
+        return rec
+
+    def step(self):
+        before = {i: "mx_cols" in T.built for i, T in self.m.t.items()}
+        super().step()
+        op, ids, a = self.prog[-1]
+        if "expect" in a:
+            return
+        for i, T in self.m.t.items():
+            if "mx_cols" in T.built and not before.get(i, False):
+                self.sched_by[i] = "graph" if op in GRAPH_KINDS else "amg" if op == "amg_create" else "reader"
+        if op in GRAPH_KINDS:
+            key = "after_trim" if self.after_trim else self.last_graph
+            self.count[((op, key), "after")] = self.count.get(((op, key), "after"), 0) + 1
+            self.last_graph, self.after_trim = op, False
+        elif op == "trim":
+            self.after_trim = True
+
+    def draw(self):
+        dtype = self.want_dtype()
+        if self.script3 and self.chance(0.55):
+            return self.r_script3(dtype)
+        if not self.script3 and not self.script2 and len(self.m.t) >= 2 and self.chance(0.3):
+            self.start_scenario3()
+        if len(self.m.t) >= 2 and not self.script and not self.script2:
+            if self.after_trim and self.chance(0.6):
+                return self.n_graph(dtype, self.next_graph_kind())
+            if self.refusals * 12 < len(self.prog) and self.chance(0.06):
+                return self.r_refusal(dtype)
+            if self.chance(0.06):
+                rec = self.r_provenance(dtype)
+                if rec is not None:
+                    return rec
+            hot =self.hot if self.hot in self.m.t else None
+            if hot is not None and self.chance(0.3):     # what holds the tiling written last reads it next
+                ks = [k for k, K in self.m.k.items() if hot in (K.a, K.pre)]
+                hs = [h for h, H in self.m.h.items() if H.a == hot and H.opts["refreshable"]]
+                if hs and self.chance(0.5):
+                    return ("amg_refresh", (self.pick(hs),), {})
+                if ks:
+                    return self.n_krylov_solve(dtype, self.pick(ks))
+            if self.chance(0.62):
+                return self.r_needy3(dtype)
+        return super().draw()
+
+
+SCRIPTS3_ORDER = ("solver", "hierarchy", "reorder")
+
+
 def op_set(seed):
-    """the operation set a seed draws from: the second from SET2_FROM on"""
-    return 2 if int(seed) >= SET2_FROM else 1
+    """the operation set a seed draws from: the second from SET2_FROM on, the third from SET3_FROM on"""
+    return 3 if int(seed) >= SET3_FROM else 2 if int(seed) >= SET2_FROM else 1
 
 
 def context_kind(seed):
     """the context kind a committed seed runs on (any other seed: by its value)"""
-    if seed in SEEDS2:
-        return CONTEXT_KINDS[SEEDS2.index(seed) % 3]
+    for seeds in (SEEDS2, SEEDS3):
+        if seed in seeds:
+            return CONTEXT_KINDS[seeds.index(seed) % 3]
     return CONTEXT_KINDS[(SEEDS.index(seed) if seed in SEEDS else int(seed)) % 3]
 
 
 def program(seed, steps):
-    g = (_Gen2 if op_set(seed) == 2 else _Gen)(int(seed))
+    g = {1: _Gen, 2: _Gen2, 3: _Gen3}[op_set(seed)](int(seed))
     while len(g.prog) < steps:
         g.step()
     return g.prog

@@ -10,32 +10,42 @@ Plain Python / numpy, no GPU import.  The model holds, per live handle, what inc
           ilu0 source), and which lazily built structures it holds (the refresh maps, the two trsv schedules)
   MPlan   its operands, mask + complement, tile-row range, semiring, options, state 0-3, C as CSR, and the operand versions and
           semiring under which step 3 last ran: "C is current" is computed from those, never assumed
+  MKrylov the ids of A and of its factor or hierarchy (handles, not copies: a solve reads their current values) and create's options
+  MAmg    the id of A, create's options and amgref's levels as of the last create or refresh -- a refresh is a rebuild from A's
+          current values, the header's "array for array"; level 0's matrix is A itself, read as it is now
 
 Model.apply(record) executes one record of a program.  It first evaluates the precondition the header documents and returns either
 the result or the documented status (PEM_E_STATE, PEM_E_INVALID); only refusals the header spells out are modelled.  It adds no
 arithmetic: every value comes from the reference the feature's own GPU test uses (oracle.csr_spgemm, semiringref, maskref,
 ewiseref, selectref, mxvref, spmmref, sddmmref; applyref, extractref, assignref, kronref, concatref, buildref, topkref,
-sampledref, frontierref, argref, trsvref, ilu0ref); what is here is the reshaping between CSR and COO those references ask for.
+sampledref, frontierref, argref, trsvref, ilu0ref; of the third set colourref, ccref, aggref, krylovref, amgref, with numpy's stable
+argsort for the colour order); what is here is the reshaping between CSR and COO those references ask for.
 
-`mutations` switches on one of six deliberate mistakes of the MODEL (negative controls of tests/test_gpu_seq.py; the library
+`mutations` switches on one of nine deliberate mistakes of the MODEL (negative controls of tests/test_gpu_seq.py; the library
 is never touched): "no_bump" (a refresh leaves the value version alone), "stale_vals_t" (in-place writers leave the values the
 audit's vals_t readers use as they were), "no_option_reset" (set_option leaves the plan's state alone), "concat_stale_block" (a
 concat's refresh takes the blocks' values as of its first refresh: a pointer table that is not rewritten), "ilu0_stale_source"
 (set_values_from_ilu0 factors the source's values as of the build), "trsv_stale_values" (a solve takes the values the tiling had
-when that triangle's schedule was built).
+when that triangle's schedule was built), "amg_stale_weights" (a refresh leaves the weights of levels >= 1 as they were),
+"krylov_stale_factor" (a solve takes the factor's values as of create), "colour_ties_high" (a colouring's ties go to the higher index).
 """
 import numpy as np
 
+import aggref
+import amgref
 import applyref
 import argref
 import assignref
 import buildref
+import ccref
+import colourref
 import concatref
 import ewiseref
 import extractref
 import frontierref
 import ilu0ref
 import kronref
+import krylovref
 import maskref
 import mxvref
 import sampledref
@@ -50,7 +60,11 @@ from matgen import cases
 PEM_OK, PEM_E_INVALID, PEM_E_STATE = 0, -1, -6
 MINMAX = ("min_plus", "max_plus", "max_times")
 SPECIAL = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 3.0e-310, 1.0e-40, 0.5, -0.5, 2.0])   # test_gpu_sddmm.py's mix
-MUTATIONS = ("no_bump", "stale_vals_t", "no_option_reset", "concat_stale_block", "ilu0_stale_source", "trsv_stale_values")
+MUTATIONS = ("no_bump", "stale_vals_t", "no_option_reset", "concat_stale_block", "ilu0_stale_source", "trsv_stale_values",
+             "amg_stale_weights", "krylov_stale_factor", "colour_ties_high")
+# the third operation set (seqgen.py): the graph routines, and the solve of a pem_krylov by status
+GRAPH_KINDS = ("colour", "colour_order", "components", "mis", "aggregate")
+AMG_OMEGA = 2 / 3                        # tests/amgcases.py's, with seed 0 and max_levels 16
 # the derivation kinds of the second operation set (seqgen.py): each has a set_values_from_<kind>
 KINDS2 = ("apply", "scale", "transpose", "extract", "assign", "kron", "concat", "ilu0")
 
@@ -102,6 +116,7 @@ def rand_matrix(seed, rows, cols, nnz, clustered):
 
 
 _SQUARE = {}
+_SYSTEMS = None
 
 
 def square_case(kind, name, side=0):
@@ -142,6 +157,16 @@ def matrix(src):
     if "randdiag" in src:
         seed, n, nnz = src["randdiag"]
         return (n, n) + rand_square(seed, n, nnz)
+    if "graph" in src:                   # colourref.built_graphs(): a pattern; the values are never read by the graph routines
+        n, I, J = colourref.built_graphs()[src["graph"]]
+        return n, n, I, J, 0.5 + (np.arange(len(I)) % 5) * 0.25
+    if "system" in src:                  # tests/amgcases.py's systems (krylovcases' spd_* and gen_*, poisson_40, diag_50)
+        global _SYSTEMS
+        if _SYSTEMS is None:
+            import amgcases
+            _SYSTEMS = amgcases.cases()
+        n, I, J, V = _SYSTEMS[src["system"]][0]
+        return n, n, np.asarray(I, np.int32), np.asarray(J, np.int32), np.asarray(V, np.float64)
     seed, rows, cols, nnz, clustered = src["rand"]
     return (rows, cols) + rand_matrix(seed, rows, cols, nnz, bool(clustered))
 
@@ -230,12 +255,46 @@ class MPlan:
         return min(16 * self.hi, self.A.rows)
 
 
+class MKrylov:
+    """a pem_krylov: the ids of A and of its factor or hierarchy (handles, not copies), and the options of create"""
+
+    def __init__(self, a, pre, method, precond, max_iters, check_every, rtol, atol):
+        self.a, self.pre, self.method, self.precond = a, pre, method, precond
+        self.max_iters, self.check_every, self.rtol, self.atol = int(max_iters), int(check_every), float(rtol), float(atol)
+        self.kept = {}                   # the factor's values as of create (the "krylov_stale_factor" mutation)
+        self.trail = []                  # coverage bookkeeping only
+
+
+class MAmg:
+    """a pem_amg: the id of A, the options of create, and amgref's levels as of the last create / refresh (level 0's matrix is A
+    itself, a handle: Model.levels puts A's current values there)"""
+
+    def __init__(self, a, opts, levels):
+        self.a, self.opts, self.levels = a, dict(opts), levels
+        self.stalled = False             # the aggregation returned naggregates == n (coverage bookkeeping only)
+        self.trail = []                  # coverage bookkeeping only
+
+
+def priority(n, spec):
+    """the uint32 priorities of a graph record: ["seed", s] (the hash), ["equal", where] or ["ties", where] (test_gpu_colour.py's
+    arrays; where: "host" / "device")"""
+    return aggref.priority_array(n, spec[1] if spec[0] == "seed" else spec[0])
+
+
+def graph_demand(kind, n):
+    """bytes of the context's graph scratch a call of `kind` on n vertices carves (csrc: every part rounded up to 256 bytes)"""
+    r = lambda b: (b + 255) & ~255
+    return {"colour": r(4 * n) + r(12), "colour_order": 2 * r(8 * n) + 2 * r(4 * n), "components": 2 * r(4 * (n + 1)) + r(8),
+            "mis": r(n) + r(8 * n) + r(4 * (n + 1)) + r(8), "aggregate": 2 * r(n) + r(8 * n) + 2 * r(4 * (n + 1)) + r(8)}[kind]
+
+
 class Result:
     """what one record did: status; wrote = the id of the handle whose contents it (re)wrote, with the `kind` its values are
     compared under ("exact", or "minmax": +0 == -0); out = what the call returns to the caller (CSR / COO triple or dense array)"""
 
-    def __init__(self, status=PEM_OK, wrote=None, kind="exact", out=None):
+    def __init__(self, status=PEM_OK, wrote=None, kind="exact", out=None, extra=None):
         self.status, self.wrote, self.kind, self.out = status, wrote, kind, out
+        self.extra = extra               # of a solve: what res->launches follows from (the runner adds the trsv launches of the device)
 
 
 def _kind(name):
@@ -313,6 +372,7 @@ class Model:
         assert all(m in MUTATIONS for m in mutations)
         self.mut = set(mutations)
         self.t, self.p = {}, {}
+        self.k, self.h = {}, {}          # the third set's pools: solvers, hierarchies
 
     # ---- helpers -----------------------------------------------------------------------------------------------------------
     def current(self, p):
@@ -905,6 +965,207 @@ class Model:
         T = self.t[ids[0]]
         levels, parents, depth, reached = argref.bfs_parents(T.rows, T.rp, T.ci, a["source"], a["transpose"])
         return Result(out=(levels, parents, np.array([depth, reached], np.int64)))
+
+    # ---- the third operation set: graph routines ---------------------------------------------------------------------------------
+    def _graph(self, T, a):
+        """(n, I, J, priorities) of a graph record, or None where the header refuses it; symmetric = 0 builds the column schedule"""
+        if T.rows != T.cols or a.get("overlap"):
+            return None
+        if not a["symmetric"]:
+            T.built.add("mx_cols")
+        I, J, _ = T.coo()
+        return T.rows, I, J, priority(T.rows, a["prio"]) if "prio" in a else None
+
+    def _colouring(self, n, I, J, prio, symmetric):
+        if "colour_ties_high" in self.mut:       # (ties to the higher index: the mirrored graph's colouring, mirrored back)
+            c, nc, rounds = colourref.colouring(n, n - 1 - I, n - 1 - J, priority=prio[::-1], symmetric=symmetric)
+            return c[::-1].copy(), nc, rounds
+        return colourref.colouring(n, I, J, priority=prio, symmetric=symmetric)
+
+    def op_colour(self, ids, a):
+        g = self._graph(self.t[ids[0]], a)
+        if g is None:
+            return Result(PEM_E_INVALID)
+        c, nc, rounds = self._colouring(*g, a["symmetric"])
+        return Result(out=(c, np.array([nc, rounds], np.int64)))
+
+    def op_components(self, ids, a):
+        g = self._graph(self.t[ids[0]], a)
+        if g is None:
+            return Result(PEM_E_INVALID)
+        labels, rounds = ccref.components_model(g[0], g[1], g[2], symmetric_walk=a["symmetric"])
+        cid, nc = ccref.ids_of(labels)
+        return Result(out=(labels,) + ((cid,) if a["ids"] else ()) + (np.array([nc, rounds], np.int64),))
+
+    def op_colour_order(self, ids, a):
+        """the keys (a colouring, or the component ids with ncolours = ncomponents) and their stable order"""
+        g = self._graph(self.t[ids[0]], a)
+        if a["of"] == "colour":
+            keys, nk, _ = self._colouring(*g, a["symmetric"])
+        else:
+            keys, nk = ccref.ids_of(ccref.components_model(g[0], g[1], g[2], symmetric_walk=a["symmetric"])[0])
+        perm = np.argsort(keys, kind="stable").astype(np.int32)
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(keys, minlength=nk))]).astype(np.int32)
+        return Result(out=(np.asarray(keys, np.int32), perm, offsets, np.array([nk], np.int64)))
+
+    def op_mis(self, ids, a):
+        g = self._graph(self.t[ids[0]], a)
+        if g is None or a["distance"] not in (1, 2):
+            return Result(PEM_E_INVALID)
+        s, count, rounds = aggref.mis(g[0], g[1], g[2], a["distance"], priority=g[3], symmetric=a["symmetric"])
+        return Result(out=(s, np.array([count, rounds], np.int64)))
+
+    def op_aggregate(self, ids, a):
+        g = self._graph(self.t[ids[0]], a)
+        if g is None:
+            return Result(PEM_E_INVALID)
+        agg, roots, nc, rounds = aggref.aggregate(g[0], g[1], g[2], priority=g[3], symmetric=a["symmetric"])
+        return Result(out=(agg,) + ((roots,) if a["roots"] else ()) + (np.array([nc, rounds], np.int64),))
+
+    # ---- the third operation set: solvers ------------------------------------------------------------------------------------------
+    def op_krylov_create(self, ids, a):
+        A = self.t[ids[0]]
+        pre, pc = ids[1], a["precond"]
+        F = self.t.get(pre) if pc != "amg" else None
+        if A.rows != A.cols or (pc == "lu") != (F is not None) or (pc != "amg" and pre is not None and F is None):
+            return Result(PEM_E_INVALID)
+        if F is not None and ((F.rows, F.cols) != (A.rows, A.cols) or F.dtype != A.dtype or missing_diag(F)[0]):
+            return Result(PEM_E_INVALID)
+        if pc == "amg" and self.t.get(self.h[pre].a) is not A:
+            return Result(PEM_E_INVALID)
+        K = MKrylov(ids[0], pre, a["method"], pc, a["max_iters"], a["check_every"], a["rtol"], a["atol"])
+        if F is not None:
+            self._schedule(F, "lower")
+            self._schedule(F, "upper")
+            K.kept["factor"] = F.vals
+        self.k[a["out"]] = K
+        return Result()
+
+    def solve_operands(self, n, a, dtype):
+        """b, the guess (zeros where the record draws none) and the DIAG preconditioner's minv of a solve record"""
+        b = values(n, a["seed"], a["special"], dtype)
+        x0 = (0.1 * values(n, a["seed"] + 1, False, np.float64)).astype(dtype) if a["x0"] else np.zeros(n, dtype)
+        return b, x0, (0.5 + np.abs(values(n, a["seed"] + 2, False, np.float64))).astype(dtype)
+
+    def _solve(self, K, a):
+        A = self.t[K.a]
+        b, x0, minv = self.solve_operands(A.rows, a, A.dtype)
+        opt = dict(method=K.method, max_iters=K.max_iters, rtol=K.rtol, atol=K.atol)
+        if K.precond == "amg":
+            H = self.h[K.pre]
+            r = amgref.solve(self.levels(H), b, x0, oracle(), sweeps=H.opts["sweeps"], coarse_sweeps=H.opts["coarse_sweeps"], **opt)
+        else:
+            factor = None
+            if K.precond == "lu":
+                F = self.t[K.pre]
+                factor = (F.rp, F.ci, K.kept["factor"] if "krylov_stale_factor" in self.mut else F.vals)
+            r = krylovref.solve(A.rows, A.rp, A.ci, A.vals, b, x0, precond=K.precond, minv=minv if K.precond == "diag" else None, factor=factor,
+                                dtype=A.dtype, oracle=oracle(), **opt)
+        K.trail.append(krylovref.STATUS[r["status"]])
+        ints = np.array([r["iters"], r["status"], krylovref.readbacks(r["stop_iter"], K.check_every)], np.int64)
+        out = (np.asarray(r["x"], A.dtype), ints, np.array([r["bb"], r["rr"], r["threshold"]], np.float64))
+        if a["history"]:
+            out += (np.asarray(r["history"], np.float64),)
+        return Result(out=out, extra=dict(method=K.method, precond=K.precond, stop_iter=r["stop_iter"], check_every=K.check_every,
+                                          max_iters=K.max_iters, pre=K.pre))
+
+    def op_krylov_solve(self, ids, a):
+        if a.get("wrong_form"):                  # the fp64 entry point on an fp32 solver
+            return Result(PEM_E_INVALID)
+        return self._solve(self.k[ids[0]], a)
+
+    def op_krylov_close(self, ids, a):
+        del self.k[ids[0]]
+        return Result()
+
+    def op_tiled_solve(self, ids, a):
+        """Tiled.solve: a solver made, used and closed in one call; precond "ilu0" makes and closes its own factor"""
+        A = self.t[ids[0]]
+        K = MKrylov(ids[0], None, a["method"], "lu" if a["precond"] == "ilu0" else "none", a["max_iters"], a["check_every"], a["rtol"], a["atol"])
+        if a["precond"] == "ilu0":
+            K.pre = "~factor"
+            self.t[K.pre] = MTiled(A.rows, A.cols, A.dtype, A.rp, A.ci, ilu0ref.ilu0(A.rows, A.rp, A.ci, A.vals, A.dtype)[0])
+            K.kept["factor"] = self.t[K.pre].vals
+        try:
+            r = self._solve(K, a)
+        finally:
+            self.t.pop("~factor", None)
+        r.extra["trail"] = K.trail
+        return r
+
+    # ---- the third operation set: hierarchies ----------------------------------------------------------------------------------------
+    def _hierarchy(self, A, o):
+        I, J, V = A.coo()
+        return amgref.hierarchy((A.rows, I, J, V), A.dtype, oracle(), smooth=o["smooth"], symmetric=o["symmetric"], seed=0,
+                                max_levels=amgref.MAX_LEVELS, coarse_size=o["coarse_size"], omega=AMG_OMEGA)
+
+    def levels(self, H):
+        """H's levels as the device holds them now: level 0's matrix is A itself, with its current values"""
+        A = self.t[H.a]
+        first = dict(H.levels[0], A=(A.rows, A.cols, A.rp, A.ci, A.vals))
+        return [first] + H.levels[1:]
+
+    def op_amg_create(self, ids, a):
+        A = self.t[ids[0]]
+        if A.rows != A.cols or missing_diag(A)[0]:
+            return Result(PEM_E_INVALID)
+        H = MAmg(ids[0], a, self._hierarchy(A, a))
+        last = H.levels[-1]["A"][0]
+        H.stalled = len(H.levels) < amgref.MAX_LEVELS and last > a["coarse_size"]
+        if not a["symmetric"] and (len(H.levels) > 1 or H.stalled):      # (pem_tiled_aggregate ran on A itself: its column schedule)
+            A.built.add("mx_cols")
+        H.trail.append("create")
+        self.h[a["out"]] = H
+        return Result()
+
+    def op_amg_refresh(self, ids, a):
+        H = self.h[ids[0]]
+        if not H.opts["refreshable"]:
+            return Result(PEM_E_STATE)
+        new = self._hierarchy(self.t[H.a], H.opts)
+        if "amg_stale_weights" in self.mut:      # (the weights of levels >= 1 stay as they were)
+            for old, L in list(zip(H.levels, new))[1:]:
+                L["w"] = old["w"]
+        H.levels = new
+        H.trail.append("refresh")
+        return Result()
+
+    def op_amg_apply(self, ids, a):
+        H = self.h[ids[0]]
+        A = self.t[H.a]
+        H.trail.append("apply")
+        z = amgref.apply(self.levels(H), values(A.rows, a["seed"], a["special"], A.dtype), oracle(), H.opts["sweeps"], H.opts["coarse_sweeps"])
+        return Result(out=np.asarray(z, A.dtype))
+
+    def amg_fields(self, H):
+        """pem_amg_info's fields, bytes apart, in one array: levels, launches, then rows, nnz, p_nnz, aggregate_rounds of every level"""
+        i = amgref.info(self.levels(H), H.opts["sweeps"], H.opts["coarse_sweeps"])
+        return np.array([i["levels"], i["launches"]] + i["rows"] + i["nnz"] + i["p_nnz"] + i["aggregate_rounds"], np.int64)
+
+    def op_amg_info(self, ids, a):
+        self.h[ids[0]].trail.append("info")
+        return Result(out=self.amg_fields(self.h[ids[0]]))
+
+    def level_tiling(self, H, level, which):
+        rows, cols, rp, ci, v = self.levels(H)[level][which]
+        return MTiled(rows, cols, self.t[H.a].dtype, rp, ci, v)
+
+    def op_amg_level(self, ids, a):
+        """a borrowed A_l, P_l or R_l handed to a reader: a["reader"] is the reader's record without its handle"""
+        H = self.h[ids[0]]
+        op, args = a["reader"]
+        T = self.level_tiling(H, a["level"], a["which"])
+        if op == "export_csr":
+            return Result(out=(np.asarray(T.rp, np.int32), np.asarray(T.ci, np.int32), T.vals))
+        self.t["~level"] = T
+        try:
+            return self.apply((op, ("~level",), args))
+        finally:
+            del self.t["~level"]
+
+    def op_amg_close(self, ids, a):
+        del self.h[ids[0]]
+        return Result()
 
     # housekeeping: nothing a caller can observe changes
     def _ctx_event(self):

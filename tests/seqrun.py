@@ -6,19 +6,27 @@ After every step:
   - a call the model accepts must succeed;
   - the handle the step wrote is compared in full: a tiling by export_csr() (structure exact, values by `same`: equal bits, NaN equals
     NaN, +0 equals -0 only under min / max), a plan whose C is current by export_csr() alike, a dense result element for element.
-Every AUDIT_EVERY steps and at the end, every live handle is audited (audit_tiling, audit_plan): the damage this suite looks for is
+Every AUDIT_EVERY steps and at the end, every live handle is audited (audit_tiling, audit_plan, audit_hierarchy): the damage this suite looks for is
 to a handle the step did not name.  There is no tolerance anywhere and no entry is left out.
 
 Where the header leaves bits open (the sign of a zero under min / max, NaN payloads) the model adopts the device's bits after the
 comparison under that rule has passed, so that everything computed from them later is compared exactly again.
 
+The third operation set (graph routines, solvers, hierarchies): every output buffer holds a poison value before the call; of a solve
+the history past iters must still hold it.  Solvers and hierarchies go through the Python classes, as the feature tests call them;
+the four refusals those classes cannot express (mis at distance 3, lu without a factor, a factor under another preconditioner, the
+fp64 solve on an fp32 solver) call the C entry points.  _graph_call holds the graph scratch's allocation rule.
+
 A mismatch raises SeqMismatch; its message carries the seed, the step, the failing record and the program up to that step in the
 text form tools/seq_replay.py reads.  A HIP error status (PEM_E_HIP) raises SeqGpuError, after which nothing more is run.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
 import argref
+import krylovref
 import seqgen as sg
 import seqmodel as sm
 from semiringref import coo_to_csr
@@ -32,6 +40,7 @@ ARRAYS = ("tile_keys", "tile_nnz_ptr", "masks", "rowptr", "rowcolidx", "vals", "
 TRSV_FIELDS = ("levels", "max_width", "missing_diag", "first_missing_row")       # of pem_tiled_trsv_info; sm.trsv_fields' order
 PIVOT_FIELDS = ("zero_pivots", "first_zero_pivot_row")                           # of pem_tiled_ilu0_info; sm.pivot_fields' order
 SYMBOLIC = ("c_tile_rowptr", "c_tile_colidx", "c_mask", "c_tile_nnz_ptr")
+POISON_I, POISON_B, POISON_F = -77777, 7, -7.25      # what every output buffer of the third set holds before the call
 
 
 class SeqMismatch(AssertionError):
@@ -54,6 +63,8 @@ class Runner:
         self.pkg, self.ctx, self.tmpdir, self.on_stream, self.log = pkg, ctx, str(tmpdir), on_stream, log
         self.m = sm.Model(mutations)
         self.t, self.p = {}, {}
+        self.k, self.h = {}, {}          # the third set's pools: solvers, hierarchies
+        self.res, self.pre_built = None, {}
         self.keep = []                   # device tensors a stream-ordered call may still read
         self.snap = {}                   # plan id -> (option epoch, symbolic arrays) of the last audit
         self.dense_a = {}
@@ -80,6 +91,11 @@ class Runner:
         return t.cpu().numpy()
 
     def close(self):
+        for k in self.k.values():
+            k.close()
+        for h in self.h.values():
+            h.close()
+        self.k, self.h = {}, {}
         for p in self.p.values():
             p.close()
         for t in self.t.values():
@@ -222,12 +238,36 @@ class Runner:
                         self.fail(f"{pid}: symbolic array {a} changed since the last audit with no option change", where)
             self.snap[pid] = (M.option_epoch, arrays)
 
-    def audit(self, tids=None, pids=None, where="audit"):
+    def audit_hierarchy(self, hid, where):
+        """the info fields (bytes: not negative, nothing more) and every level's A_l, P_l, R_l by export_csr against the model"""
+        H, M = self.h[hid], self.m.h[hid]
+        info = H.info
+        got, want = self._amg_fields(info), self.m.amg_fields(M)
+        if not np.array_equal(got, want):
+            self.fail(f"{hid}: info fields {got.tolist()}, the model has {want.tolist()}", where)
+        if info["bytes"] < 0:
+            self.fail(f"{hid}: info bytes = {info['bytes']}", where)
+        for l, L in enumerate(self.m.levels(M)):
+            for name, T in zip("APR", H.level(l)):
+                if (T is None) != (L[name] is None):
+                    self.fail(f"{hid}: level {l}: {name} is {'missing' if T is None else 'there'}, the model disagrees", where)
+                if T is None:
+                    continue
+                rows, cols, mrp, mci, mv = L[name]
+                rp, ci, v = T.export_csr()
+                if (T.rows, T.cols) != (rows, cols) or not (np.array_equal(rp, mrp) and np.array_equal(ci, mci)):
+                    self.fail(f"{hid}: level {l}: the structure of {name} differs from the model", where)
+                if not same(v, mv):
+                    self.fail(f"{hid}: level {l}: the values of {name} differ from the model", where)
+
+    def audit(self, tids=None, pids=None, where="audit", hids=None):
         self.audits += 1
         for tid in (self.m.t if tids is None else tids):
             self.audit_tiling(tid, where)
         for pid in (self.m.p if pids is None else pids):
             self.audit_plan(pid, where)
+        for hid in (self.m.h if hids is None else hids):
+            self.audit_hierarchy(hid, where)
         self.keep.clear()
 
     # ---- the operations on the device: each returns what the call handed back (or None) ------------------------------------------------
@@ -522,6 +562,192 @@ class Runner:
     def g_ilu0_info(self, ids, a):
         return self._fields(self.t[ids[0]].ilu0_info(), PIVOT_FIELDS)
 
+    # ---- the third operation set: graph routines -------------------------------------------------------------------------------------
+    def _graph_call(self, kind, tid, n, symmetric, fn):
+        """fn() under the allocation rule of the graph scratch: a call whose demand does not exceed the largest any graph call has
+        made on this context allocates nothing (where it does not build the column schedule either).  The demand is tracked per
+        context for its whole life: Context.trim returns wholly free slabs only, and the scratch is a block in use, so it survives a
+        trim.  The hierarchies' own aggregate calls are not counted: the bound stays a lower one."""
+        demand, known = sm.graph_demand(kind, n), getattr(self.ctx, "_seq_graph_demand", 0)
+        quiet = tid in self.pre_built and demand <= known and (symmetric or "mx_cols" in self.pre_built[tid])
+        before = self.ctx.memory_stats()
+        out = fn()
+        after = self.ctx.memory_stats()
+        if quiet and any(after[k] != before[k] for k in ("block_allocs", "driver_allocs")):
+            self.fail(f"{kind} with a scratch demand of {demand} bytes allocated ({before} -> {after}); the context had served {known}")
+        self.ctx._seq_graph_demand = max(known, demand)
+        return out
+
+    def _prio_dev(self, n, a):
+        """seed / priority of a graph call: a seed, a host array or a device tensor"""
+        spec = a["prio"]
+        if spec[0] == "seed":
+            return dict(seed=spec[1])
+        arr = sm.priority(n, spec)
+        return dict(priority=self.dev(arr.view(np.int32)) if spec[1] == "device" else arr)
+
+    def _poison(self, n, dtype=np.int32, value=POISON_I):
+        return self.dev(np.full(n, value, dtype))
+
+    def g_colour(self, ids, a):
+        T, n = self.t[ids[0]], self.m.t[ids[0]].rows
+        kw = self._prio_dev(n, a)
+        out = kw["priority"] if a.get("overlap") else self._poison(n)
+        self.uploaded()
+        c, nc, rounds = self._graph_call("colour", ids[0], n, a["symmetric"], lambda: T.colour(symmetric=a["symmetric"], out=out, **kw))
+        return self.host(c), np.array([nc, rounds], np.int64)
+
+    def g_components(self, ids, a):
+        T, n = self.t[ids[0]], self.m.t[ids[0]].rows
+        out, out_ids = self._poison(n), self._poison(n) if a["ids"] else None
+        self.uploaded()
+        labels, cid, nc, rounds = self._graph_call("components", ids[0], n, a["symmetric"],
+                                                   lambda: T.components(symmetric=a["symmetric"], out=out, ids=a["ids"], out_ids=out_ids))
+        return (self.host(labels),) + ((self.host(cid),) if a["ids"] else ()) + (np.array([nc, rounds], np.int64),)
+
+    def g_colour_order(self, ids, a):
+        T, n = self.t[ids[0]], self.m.t[ids[0]].rows
+        out = self._poison(n)
+        if a["of"] == "colour":
+            kw = self._prio_dev(n, a)
+            self.uploaded()
+            keys, nk, _ = self._graph_call("colour", ids[0], n, a["symmetric"], lambda: T.colour(symmetric=a["symmetric"], out=out, **kw))
+        else:
+            labels = self._poison(n)
+            self.uploaded()
+            _, keys, nk, _ = self._graph_call("components", ids[0], n, a["symmetric"],
+                                              lambda: T.components(symmetric=a["symmetric"], out=labels, out_ids=out))
+        self.pre_built.get(ids[0], set()).add("mx_cols")    # (the first call built the schedule, if any had to)
+        perm, offsets = self._graph_call("colour_order", ids[0], n, True, lambda: self.pkg.colour_order(self.ctx, keys, nk))
+        return self.host(keys), self.host(perm), self.host(offsets), np.array([nk], np.int64)
+
+    def g_mis(self, ids, a):
+        T, n = self.t[ids[0]], self.m.t[ids[0]].rows
+        out = self._poison(n, np.uint8, POISON_B)
+        kw = self._prio_dev(n, a)
+        self.uploaded()
+        if a["distance"] not in (1, 2):          # (Tiled.mis refuses it itself: the library's own refusal is asked for)
+            count, rounds = C.c_int64(), C.c_int32()
+            self.pkg._check(self.pkg.lib().pem_tiled_mis(self.ctx._h, T._h, int(a["distance"]), int(a["symmetric"]), kw.get("seed", 0), None,
+                                                         C.c_void_p(out.data_ptr()), C.byref(count), C.byref(rounds)))
+            return None
+        s, count, rounds = self._graph_call("mis", ids[0], n, a["symmetric"], lambda: T.mis(a["distance"], symmetric=a["symmetric"], out=out, **kw))
+        return self.host(s), np.array([count, rounds], np.int64)
+
+    def g_aggregate(self, ids, a):
+        T, n = self.t[ids[0]], self.m.t[ids[0]].rows
+        out = self._poison(n)
+        kw = self._prio_dev(n, a)
+        self.uploaded()
+        agg, roots, nc, rounds = self._graph_call("aggregate", ids[0], n, a["symmetric"],
+                                                  lambda: T.aggregate(symmetric=a["symmetric"], out=out, roots=a["roots"], **kw))
+        return (self.host(agg),) + ((self.host(roots),) if a["roots"] else ()) + (np.array([nc, rounds], np.int64),)
+
+    # ---- the third operation set: solvers --------------------------------------------------------------------------------------------
+    def g_krylov_create(self, ids, a):
+        A, pc, pre = self.t[ids[0]], a["precond"], ids[1]
+        if (pc == "lu") != (pre in self.t):      # (the Krylov class cannot say it: lu without a factor, a factor under none / diag)
+            opts = self.pkg.KrylovOpts(self.pkg.KRYLOV_METHODS.index(a["method"]), ("none", "diag", "lu").index(pc), a["max_iters"],
+                                       a["check_every"], a["rtol"], a["atol"])
+            h = C.c_void_p()
+            self.pkg._check(self.pkg.lib().pem_krylov_create(self.ctx._h, A._h, C.byref(opts), self.t[pre]._h if pre in self.t else None, C.byref(h)))
+            self.fail("pem_krylov_create accepted a call the header refuses")
+        precond = {"none": None, "diag": "diag"}[pc] if pc in ("none", "diag") else self.t[pre] if pc == "lu" else self.h[pre]
+        self.k[a["out"]] = self.pkg.Krylov(A, a["method"], precond, a["max_iters"], a["check_every"], a["rtol"], a["atol"])
+
+    def g_krylov_close(self, ids, a):
+        self.k.pop(ids[0]).close()
+
+    def _solve_dev(self, M, a, max_iters, diag):
+        b, x0, minv = self.m.solve_operands(M.rows, a, M.dtype)
+        d = dict(b=self.dev(b), x=self.dev(x0) if a["x0"] else None, minv=self.dev(minv) if diag else None,
+                 hist=self.dev(np.full(max_iters + 1, POISON_F)) if a["history"] else False)
+        self.uploaded()
+        return d
+
+    def _solved(self, a, x, info, hist, launches):
+        """what a solve handed back, in the model's order; the part of the history past iters still holds what it held"""
+        if launches is not None and info["launches"] != launches:
+            self.fail(f"launches = {info['launches']}, the header's formula gives {launches}")
+        out = (self.host(x), np.array([info["iters"], info["status_code"], info["readbacks"]], np.int64),
+               np.array([info["bb"], info["rr"], info["threshold"]], np.float64))
+        if a["history"]:
+            h = self.host(hist)
+            if not np.all(h[info["iters"] + 1:] == POISON_F):
+                self.fail(f"the history was written past entry iters = {info['iters']}")
+            out += (h[:info["iters"] + 1],)
+        return out
+
+    def _launches(self, e, T):
+        return krylovref.launches(e["method"], "lu" if e["precond"] in ("lu", "amg") else e["precond"], e["stop_iter"], e["check_every"], e["max_iters"], T)
+
+    def g_krylov_solve(self, ids, a):
+        K, MK = self.k[ids[0]], self.m.k[ids[0]]
+        M = self.m.t[MK.a]
+        d = self._solve_dev(M, a, MK.max_iters, MK.precond == "diag")
+        if a.get("wrong_form"):                  # the fp64 entry point on an fp32 solver
+            res = self.pkg.KrylovResult()
+            self.pkg._check(self.pkg.lib().pem_krylov_solve(self.ctx._h, K._h, C.c_void_p(d["b"].data_ptr()), C.c_void_p(d["x"].data_ptr()) if a["x0"] else
+                                                            C.c_void_p(d["b"].data_ptr()), None, None, C.byref(res)))
+            return None
+        x, info = K.solve(d["b"], x=d["x"], minv=d["minv"], history=d["hist"])
+        T = 0
+        if MK.precond == "lu":
+            F = self.t[MK.pre]
+            T = F.trsv_info("lower")["launches"] + F.trsv_info("upper")["launches"]
+        elif MK.precond == "amg":
+            T = int(self.m.amg_fields(self.m.h[MK.pre])[1])
+        return self._solved(a, x, info, d["hist"], self._launches(self.res.extra, T))
+
+    def g_tiled_solve(self, ids, a):
+        M = self.m.t[ids[0]]
+        d = self._solve_dev(M, a, a["max_iters"], False)
+        x, info = self.t[ids[0]].solve(d["b"], a["method"], None if a["precond"] == "none" else a["precond"], x=d["x"], max_iters=a["max_iters"],
+                                       check_every=a["check_every"], rtol=a["rtol"], atol=a["atol"], history=d["hist"])
+        # (the launches of its own factor's solves are not to be had: the formula is checked without a preconditioner only)
+        return self._solved(a, x, info, d["hist"], self._launches(self.res.extra, 0) if a["precond"] == "none" else None)
+
+    # ---- the third operation set: hierarchies ------------------------------------------------------------------------------------------
+    def g_amg_create(self, ids, a):
+        self.h[a["out"]] = self.pkg.Amg(self.t[ids[0]], smooth=bool(a["smooth"]), symmetric=a["symmetric"], seed=0, max_levels=16,
+                                        coarse_size=a["coarse_size"], sweeps=a["sweeps"], coarse_sweeps=a["coarse_sweeps"], omega=sm.AMG_OMEGA,
+                                        refreshable=bool(a["refreshable"]))
+
+    def g_amg_refresh(self, ids, a):
+        self.h[ids[0]].refresh()
+
+    def g_amg_apply(self, ids, a):
+        M = self.m.t[self.m.h[ids[0]].a]
+        r, out = self.dev(sm.values(M.rows, a["seed"], a["special"], M.dtype)), self._poison(M.rows, M.dtype, POISON_F)
+        self.uploaded()
+        return self.host(self.h[ids[0]].apply(r, out=out))
+
+    @staticmethod
+    def _amg_fields(i):
+        return np.array([i["levels"], i["launches"]] + i["rows"] + i["nnz"] + i["p_nnz"] + i["aggregate_rounds"], np.int64)
+
+    def g_amg_info(self, ids, a):
+        info = self.h[ids[0]].info
+        if info["bytes"] < 0:
+            self.fail(f"info bytes = {info['bytes']}")
+        return self._amg_fields(info)
+
+    def g_amg_level(self, ids, a):
+        """the borrowed handle goes to the reader under a name of its own, next to the model's copy of that level"""
+        H = self.m.h[ids[0]]
+        T = self.h[ids[0]].level(a["level"])["APR".index(a["which"])]
+        op, args = a["reader"]
+        if op == "export_csr":
+            return T.export_csr()
+        self.t["~level"], self.m.t["~level"] = T, self.m.level_tiling(H, a["level"], a["which"])
+        try:
+            return getattr(self, "g_" + op)(("~level",), args)
+        finally:
+            del self.t["~level"], self.m.t["~level"]
+
+    def g_amg_close(self, ids, a):
+        self.h.pop(ids[0]).close()
+
     def g_trim(self, ids, a):
         self.ctx.trim()
 
@@ -537,7 +763,9 @@ class Runner:
         op, ids, a = rec
         named_t = [h for h in ids if h in self.m.t]
         named_p = [h for h in ids if h in self.m.p]
-        res = self.m.apply(rec)
+        named_h = [h for h in ids if h in self.m.h]
+        self.pre_built = {h: set(self.m.t[h].built) for h in named_t}
+        res = self.res = self.m.apply(rec)
         if self.log:
             self.log(f"step {i}: {sg.dumps([rec])} -> model status {res.status}")
         try:
@@ -548,9 +776,9 @@ class Runner:
                 self.fail(f"the model accepts the call, the library raised {e}")
             if e.status != res.status:
                 self.fail(f"the model predicts status {res.status}, the library raised {e}")
-            if "out" in a and a["out"] in self.t:
+            if "out" in a and (a["out"] in self.t or a["out"] in self.k or a["out"] in self.h):
                 self.fail("a refused call left a handle behind")
-            self.audit(named_t, named_p, where="after the refusal")   # a refused call leaves every handle it named as it was
+            self.audit(named_t, named_p, where="after the refusal", hids=named_h)   # a refused call leaves every handle it named as it was
             return
         if res.status != 0:
             self.fail(f"the model predicts status {res.status}, the library accepted the call")
@@ -561,6 +789,8 @@ class Runner:
         if res.out is not None:
             want = res.out if isinstance(res.out, tuple) else (res.out,)
             got = got if isinstance(got, tuple) else (got,)
+            if len(got) != len(want):
+                self.fail(f"the call handed back {len(got)} results, the model has {len(want)}")
             for n, (x, y) in enumerate(zip(got, want)):
                 ok = same(x, y, res.kind) if np.asarray(y).dtype.kind == "f" else np.array_equal(x, y)
                 if not ok:

@@ -2,7 +2,8 @@
 """Replay one program of the sequence test (tests/test_gpu_seq.py) with per-step output.
 
     python tools/seq_replay.py --seed 107 [--steps 120] [--context session|torch_stream|graph_replay]
-    python tools/seq_replay.py --seed 1203            (a seed from seqgen.SET2_FROM on draws from the second operation set)
+    python tools/seq_replay.py --seed 1203            (a seed from seqgen.SET2_FROM on draws from the second operation set,
+                                                       one from seqgen.SET3_FROM on from the third)
     python tools/seq_replay.py --program failing.txt [--context ...]
 
 --program reads the text a failing test printed (one JSON record per line; other lines are ignored), --seed regenerates the
@@ -29,17 +30,25 @@ def handles(rec):
         wrote.add(ids[0])
     if op in ("trsv", "trsv_info", "lu_solve"):   # (the first of them builds the triangle's schedule, which stays with the tiling)
         wrote.add(ids[0])
+    if op == "amg_refresh" or (op in ("colour", "colour_order", "components", "mis", "aggregate", "amg_create") and not a.get("symmetric")):
+        wrote.add(ids[0])                         # (a refresh rewrites its hierarchy; symmetric = 0 may build the column schedule)
     return read, wrote
 
 
 def closure(prog, step, live=None):
     """indices of the steps that created or wrote a handle step `step` reads (live: every handle, for an audit), transitively"""
-    operands = {r[2]["out"]: {h for h in r[1] if h is not None} for r in prog[:step + 1] if r[0] == "plan_create"}
+    operands = {r[2]["out"]: {h for h in r[1] if h is not None} for r in prog[:step + 1]
+                if r[0] in ("plan_create", "krylov_create", "amg_create") and "out" in r[2]}
     # (a derived tiling's refresh names its sources itself -- a concat every cell -- so they are among the handles that step reads;
     # the solves count as writers of their tiling: the kept schedule a later solve uses was built by one of them)
 
-    def with_operands(hs):   # (a plan reads its operands' values whenever it runs, not only when it is made)
-        return set(hs) | {t for h in hs for t in operands.get(h, ())}
+    def with_operands(hs):   # (a plan reads its operands' values whenever it runs, not only when it is made; so does a solver --
+        out = set(hs)        # its A, its factor, its hierarchy and that one's A -- and a hierarchy)
+        while True:
+            more = out | {t for h in out for t in operands.get(h, ())}
+            if more == out:
+                return out
+            out = more
 
     want = with_operands(live if live is not None else handles(prog[step])[0])
     keep = [] if live is not None else [step]
@@ -90,7 +99,7 @@ def main():
             status = 2
         except seqrun.SeqMismatch as e:
             print(e)
-            live = None if e.where == "step" else [h for h in list(runner.m.t) + list(runner.m.p)]
+            live = None if e.where == "step" else [h for h in list(runner.m.t) + list(runner.m.p) + list(runner.m.k) + list(runner.m.h)]
             if e.where == "after the refusal":
                 live = [h for h in e.rec[1] if h is not None]
             keep = closure(prog, e.step, live)
