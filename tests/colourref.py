@@ -21,6 +21,17 @@ def hash_priority(n, seed):
     return np.array([fmix32(v + seed * 0x9E3779B9) for v in range(n)], np.uint32)
 
 
+def hash_priority_at(idx, seed):
+    """hash_priority(n, seed)[idx] for any n above every index, computed for those vertices alone"""
+    h = (np.asarray(idx, np.uint64) + np.uint64((seed * 0x9E3779B9) & M32)) & np.uint64(M32)
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & np.uint64(M32)
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(M32)
+    h ^= h >> np.uint64(16)
+    return h.astype(np.uint32)
+
+
 def adjacency(n, I, J, symmetric=False):
     """a list of neighbour sets: every stored off-diagonal (i, j) is the edge {i, j}; symmetric=True reads what the device reads under
     that promise, the row orientation only (vertex i sees j, and j sees i only if (j, i) is stored too)"""

@@ -232,3 +232,81 @@ class IndexMap:
         rp = np.zeros(self.cdim + 1, np.int64)
         np.cumsum(np.bincount(i, minlength=self.cdim), out=rp[1:])
         return rp, j[o], np.asarray(V)[o]
+
+
+# ---- the graph routines and the solves: references on the lines that carry an off-diagonal entry ------------------------------------
+# A vertex without an off-diagonal entry has no neighbour, a row without one no fma: what the operation gives it is known without
+# running anything, and the others never look at it.  The map is monotone, so "ties to the lower index", the ascending roots and
+# the ascending-j fma chains keep their order.  tests/test_compact_cpu.py holds every rule below equal to the plain reference.
+
+def offdiag_map(n, I, J):
+    """the IndexMap over the indices that carry an off-diagonal entry, as a row or as a column"""
+    I, J = np.asarray(I, np.int64), np.asarray(J, np.int64)
+    off = I != J
+    return IndexMap(np.concatenate([I[off], J[off]]), n)
+
+
+def compact_pattern(m, I, J):
+    """the off-diagonal entries in the compacted index space: (I, J) int32, in the input's order"""
+    I, J = np.asarray(I, np.int64), np.asarray(J, np.int64)
+    off = I != J
+    return m.fwd(I[off]).astype(np.int32), m.fwd(J[off]).astype(np.int32)
+
+
+def compact_system(m, I, J, V):
+    """(csr, kept): the sorted CSR of the rows in m.used (their columns lie in m.used too: an off-diagonal entry puts both of its
+    indices there) and the bool mask of those entries in the (row, col) order of the whole matrix"""
+    I, J = np.asarray(I, np.int64), np.asarray(J, np.int64)
+    o = np.lexsort((J, I))
+    kept = np.isin(I[o], m.used)
+    return m.csr(I[o][kept], J[o][kept], np.asarray(V)[o][kept]), kept
+
+
+def lift_colours(m, colours_c):
+    """a vertex without a neighbour takes colour 0 in round 1; ncolours and rounds are the compacted run's (which has a vertex)"""
+    return m.scatter(colours_c, 0)
+
+
+def lift_mis(m, in_set_c, count_c):
+    """a vertex without a neighbour is in every maximal independent set, at either distance -> (in_set, count)"""
+    return m.scatter(in_set_c, 1), int(count_c) + m.dim - m.cdim
+
+
+def lift_aggregate(m, agg_c, roots_c, nc_c):
+    """(agg, roots, naggregates): a vertex without a neighbour is the root of its own aggregate; the roots are numbered in ascending
+    vertex order, so agg[v] is the rank of v's root among all of them"""
+    root_of = np.arange(m.dim, dtype=np.int64)
+    if m.cdim:
+        root_of[m.used] = m.used[np.asarray(roots_c, np.int64)[np.asarray(agg_c, np.int64)]]
+    is_root = np.ones(m.dim, bool)
+    is_root[m.used] = False
+    is_root[m.used[np.asarray(roots_c, np.int64)]] = True
+    roots = np.flatnonzero(is_root)
+    rank = np.cumsum(is_root) - 1
+    assert len(roots) == int(nc_c) + m.dim - m.cdim
+    return rank[root_of].astype(np.int32), roots.astype(np.int32), len(roots)
+
+
+def lift_solution(m, x_c, b, diag=None):
+    """a triangular solve's x: a row without an off-diagonal entry is b_i / a_ii, one division in the value type (diag: the full
+    diagonal; None under unit_diag: b_i), the others the compacted system's"""
+    b = np.asarray(b)
+    with np.errstate(all="ignore"):
+        rest = b.copy() if diag is None else b / np.asarray(diag, b.dtype)
+    return m.scatter(np.asarray(x_c, b.dtype), rest)
+
+
+def lift_factor(kept, f_c, V_sorted):
+    """ILU(0)'s values in the (row, col) order of the whole matrix: a row without an off-diagonal entry keeps its a_ii (no fma, no
+    division), the others take the compacted factor's, whose CSR order is theirs"""
+    out = np.array(V_sorted)
+    out[kept] = f_c
+    return out
+
+
+def lift_index(m, idx_c, none=-1):
+    """an index output over the compacted lines (an argmin's column, a BFS parent): the indices renamed back, `none` kept, absent lines
+    `none` (or, `none` a full-length vector, what they held)"""
+    idx_c = np.asarray(idx_c, np.int64)
+    back = np.where(idx_c >= 0, m.used[np.maximum(idx_c, 0)], idx_c).astype(np.int32) if m.cdim else idx_c.astype(np.int32)
+    return m.scatter(back, none)

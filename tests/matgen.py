@@ -186,3 +186,16 @@ def hypersparse(seed=777):
     key = np.unique(np.concatenate([ci * n + cj, pi.ravel() * n + pj.ravel(), rows * n + cols, di.ravel().astype(np.int64) * n + dj.ravel()]))
     key = rng.permutation(key)
     return n, (key // n).astype(np.int32), (key % n).astype(np.int32), _vals(rng, len(key)), S.astype(np.int32)
+
+
+def hypersparse_diag(seed=777):
+    """(n, I, J, V, S): hypersparse() with a stored diagonal entry on every row, a_ii = 4 + the sum of |a_ij| over the row's stored
+    off-diagonal entries, so that the matrix is strictly diagonally dominant by rows and no pivot of its (incomplete) factorisation
+    vanishes: the operand of the solves that refuse a row without a diagonal.  The off-diagonal entries come first, in hypersparse()'s
+    order; the n diagonal entries follow, ascending (a diagonal entry hypersparse() stores is replaced).  About 4.5 million entries."""
+    n, I, J, V, S = hypersparse(seed)
+    off = I != J
+    I, J, V = I[off], J[off], V[off]
+    d = 4.0 + np.bincount(I, weights=np.abs(V), minlength=n)
+    diag = np.arange(n, dtype=np.int32)
+    return n, np.concatenate([I, diag]), np.concatenate([J, diag]), np.concatenate([V, d]), S

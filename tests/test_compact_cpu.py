@@ -159,3 +159,187 @@ def test_index_map_vector_references_equal_the_full_ones(oracle, all_cases):
         wy, wp = fr.mxv_frontier(rows, cols, *full, x, "min_plus", np.float64, present=present, transpose=tr)
         gy, gp = fr.mxv_frontier(m.cdim, m.cdim, *comp, m.gather(x), "min_plus", np.float64, present=m.gather(present), transpose=tr)
         assert np.array_equal(m.scatter(gy, np.inf), wy) and np.array_equal(m.scatter(gp, 0), wp)
+
+
+# ---- the lifting rules of the graph routines, the solves and the arg folds (compactref, second half) --------------------------------
+def _isolated_610():
+    """700 vertices of which 610 carry no off-diagonal entry (20 of those a diagonal entry only); the pattern is not symmetric"""
+    rng = np.random.default_rng(17)
+    n = 700
+    act = np.sort(rng.choice(n, 90, replace=False))
+    k = rng.choice(90 * 90, 400, replace=False)
+    I, J = act[k // 90], act[k % 90]
+    used = np.unique(np.concatenate([I[I != J], J[I != J]]))
+    assert len(used) == 90
+    lone = rng.choice(np.setdiff1d(np.arange(n), act), 20, replace=False)
+    I, J = np.concatenate([I, lone]), np.concatenate([J, lone])
+    p = rng.permutation(len(I))
+    return n, I[p].astype(np.int32), J[p].astype(np.int32), rng.uniform(-1.0, 1.0, len(I))
+
+
+@pytest.fixture(scope="module")
+def lift_graphs(all_cases):
+    out = {name: (all_cases[name][0], *all_cases[name][2:5]) for name in ("empty_rows", "ragged_37")}
+    out["isolated_610"] = _isolated_610()
+    return out
+
+
+LIFT_NAMES = ["isolated_610", "empty_rows", "ragged_37"]
+
+
+def _with_diagonal(n, I, J, V):
+    """the recipe of matgen.hypersparse_diag on a small matrix"""
+    off = I != J
+    I, J, V = I[off], J[off], V[off]
+    d = 4.0 + np.bincount(I, weights=np.abs(V), minlength=n)
+    k = np.arange(n, dtype=np.int32)
+    return np.concatenate([I, k]), np.concatenate([J, k]), np.concatenate([V, d]), d
+
+
+def _full_csr(n, I, J, V):
+    o = np.lexsort((J, I))
+    rp = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(I, minlength=n), out=rp[1:])
+    return rp, J[o].astype(np.int64), np.asarray(V)[o]
+
+
+def test_hash_priority_at_is_the_hash():
+    import colourref as cr
+    for seed in (0, 5, 12345, 2 ** 32 - 1):
+        full = cr.hash_priority(3000, seed)
+        idx = np.array([0, 1, 17, 2998, 2999, 5, 5], np.int64)
+        assert np.array_equal(cr.hash_priority_at(idx, seed), full[idx])
+        assert np.array_equal(cr.hash_priority_at(np.arange(3000), seed), full)
+    big = np.array([4_194_324, 2 ** 31 - 1], np.int64)
+    assert cr.hash_priority_at(big, 7).tolist() == [cr.fmix32(int(v) + 7 * 0x9E3779B9) for v in big]
+
+
+@pytest.mark.parametrize("symmetric", [False, True])
+@pytest.mark.parametrize("name", LIFT_NAMES)
+def test_graph_lifts_equal_the_plain_models(lift_graphs, name, symmetric):
+    """colour, mis and aggregate on the vertices with a neighbour, lifted, against the models on the whole graph: bit for bit, the
+    counts and the rounds too.  Under symmetric=True also the rounds model, which is what the device runs where the promise is false."""
+    import aggref as ag
+    import colourref as cr
+    n, I, J, _ = lift_graphs[name]
+    m = compactref.offdiag_map(n, I, J)
+    assert (m.cdim < n) == (name != "ragged_37")
+    cI, cJ = compactref.compact_pattern(m, I, J)
+    rng = np.random.default_rng(23)
+    for prio in (rng.integers(0, 2 ** 32, n).astype(np.uint32), ag.priority_array(n, "ties"), cr.hash_priority(n, 12345)):
+        pc = prio[m.used]
+        c, nc, rounds = cr.colouring(n, I, J, priority=prio, symmetric=symmetric)
+        cc, ncc, rc = cr.colouring(m.cdim, cI, cJ, priority=pc, symmetric=symmetric)
+        assert np.array_equal(compactref.lift_colours(m, cc), c) and (ncc, rc) == (nc, rounds)
+        if symmetric:
+            c, _, nc, rounds = cr.jones_plassmann(cr.adjacency(n, I, J, True), prio)
+            cc, _, ncc, rc = cr.jones_plassmann(cr.adjacency(m.cdim, cI, cJ, True), pc)
+            assert np.array_equal(compactref.lift_colours(m, cc), c) and (ncc, rc) == (nc, rounds)
+        for distance in (1, 2):
+            s, count, rounds = ag.mis(n, I, J, distance, priority=prio, symmetric=symmetric)
+            sc, cc_, rc = ag.mis(m.cdim, cI, cJ, distance, priority=pc, symmetric=symmetric)
+            ls, lcount = compactref.lift_mis(m, sc, cc_)
+            assert ls.dtype == s.dtype and np.array_equal(ls, s) and (lcount, rc) == (count, rounds)
+        agg, roots, nagg, rounds = ag.aggregate(n, I, J, priority=prio, symmetric=symmetric)
+        ac, rootc, naggc, rc = ag.aggregate(m.cdim, cI, cJ, priority=pc, symmetric=symmetric)
+        la, lr, ln = compactref.lift_aggregate(m, ac, rootc, naggc)
+        assert la.dtype == agg.dtype and lr.dtype == roots.dtype
+        assert np.array_equal(la, agg) and np.array_equal(lr, roots) and (ln, rc) == (nagg, rounds)
+    assert np.array_equal(cr.hash_priority_at(m.used, 12345), cr.hash_priority(n, 12345)[m.used])
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=("f64", "f32"))
+@pytest.mark.parametrize("name", LIFT_NAMES)
+def test_solve_lifts_equal_the_plain_references(lift_graphs, name, dtype):
+    """ilu0, trsv (both triangles, with and without unit_diag), lu_solve and the level schedule on the rows with an off-diagonal
+    entry, lifted, against trsvref / ilu0ref on the whole system.  The upper solve needs index=: its fma order goes by the tile edge"""
+    import ilu0ref
+    import trsvref as tr
+    n, I, J, V = lift_graphs[name]
+    I, J, V, d = _with_diagonal(n, I, J, V.astype(dtype))
+    V, d = V.astype(dtype), d.astype(dtype)
+    m = compactref.offdiag_map(n, I, J)
+    (crp, cci, cv), kept = compactref.compact_system(m, I, J, V)
+    rp, ci, v = _full_csr(n, I, J, V)
+    assert np.array_equal(v[kept], cv) and kept.sum() == len(cv)
+    b = np.random.default_rng(29).standard_normal(n).astype(dtype)
+    bc = m.gather(b)
+    f, _ = ilu0ref.ilu0(n, rp, ci, v, dtype)
+    fc, _ = ilu0ref.ilu0(m.cdim, crp, cci, cv, dtype)
+    lifted = compactref.lift_factor(kept, fc, v)
+    assert lifted.dtype == f.dtype and np.array_equal(lifted, f)
+    assert ilu0ref.pivots(n, rp, ci, f)[0] == 0
+    for uplo in tr.UPLO:
+        for unit in (False, True):
+            want = tr.trsv(n, rp, ci, v, b, uplo, unit, dtype)
+            got = tr.trsv(m.cdim, crp, cci, cv, bc, uplo, unit, dtype, index=m.used)
+            got = compactref.lift_solution(m, got, b, None if unit else d)
+            assert got.dtype == want.dtype and np.array_equal(got, want), (uplo, unit)
+        lv = tr.levels(n, rp, ci, uplo)
+        lvc = tr.levels(m.cdim, crp, cci, uplo, index=m.used)
+        lines = np.unique(m.used // 16)
+        assert np.array_equal(lv[lines], lvc) and np.all(np.delete(lv, lines) == 1), uplo
+    z = tr.trsv(n, rp, ci, f, tr.trsv(n, rp, ci, f, b, "lower", True, dtype), "upper", False, dtype)
+    wc = tr.trsv(m.cdim, crp, cci, fc, bc, "lower", True, dtype, index=m.used)
+    zc = tr.trsv(m.cdim, crp, cci, fc, wc, "upper", False, dtype, index=m.used)
+    assert np.array_equal(compactref.lift_solution(m, zc, b, d), z), "lu_solve"
+    if name == "isolated_610":     # (what index= is for: squeezing moves the tile edge, and a row's fmas change their order)
+        plain = tr.trsv(m.cdim, crp, cci, cv, bc, "upper", False, dtype)
+        assert not np.array_equal(plain, tr.trsv(m.cdim, crp, cci, cv, bc, "upper", False, dtype, index=m.used))
+    ident = np.arange(n)
+    assert np.array_equal(tr.trsv(n, rp, ci, v, b, "upper", False, dtype, index=ident), tr.trsv(n, rp, ci, v, b, "upper", False, dtype))
+
+
+@pytest.mark.parametrize("name", LIFT_NAMES)
+def test_arg_fold_lifts_equal_the_plain_reference(lift_graphs, name):
+    """mxv_arg, reduce_arg and bfs_parents on the used lines, indices renamed back, against argref on the whole matrix"""
+    import argref as ar
+    n, I, J, V = lift_graphs[name]
+    m = compactref.IndexMap(np.concatenate([I, J]), n)
+    full, comp = _full_csr(n, I, J, V), m.csr(I, J, V)
+    rng = np.random.default_rng(31)
+    x, y0 = rng.standard_normal(n), rng.standard_normal(n)
+    present = (rng.random(n) < 0.4).astype(np.uint8)
+    i0 = np.where(rng.random(n) < 0.5, -1, m.used[rng.integers(0, m.cdim, n)]).astype(np.int32)
+    i0c = np.where(m.gather(i0) >= 0, np.searchsorted(m.used, np.maximum(m.gather(i0), 0)), -1).astype(np.int32)
+    for tr in (False, True):
+        for kind in ar.KINDS:
+            for acc in (False, True):
+                old = dict(y_old=y0, idx_old=i0, accumulate=True) if acc else {}
+                oldc = dict(y_old=m.gather(y0), idx_old=i0c, accumulate=True) if acc else {}
+                y, idx, pres = ar.mxv_arg(n, n, *full, x, kind, np.float64, present=present, transpose=tr, **old)
+                yc, idxc, presc = ar.mxv_arg(m.cdim, m.cdim, *comp, m.gather(x), kind, np.float64, present=m.gather(present), transpose=tr, **oldc)
+                if y is not None:
+                    assert np.array_equal(m.scatter(yc, y0 if acc else ar.START[kind]), y, equal_nan=True), (tr, kind, acc)
+                got = compactref.lift_index(m, idxc, i0 if acc else -1)
+                assert got.dtype == idx.dtype and np.array_equal(got, idx), (tr, kind, acc)
+                assert np.array_equal(m.scatter(presc, 0), pres)
+        import mxvref as mr
+        for op in ("min", "max"):
+            dim = "cols" if tr else "rows"
+            y, idx = ar.reduce_arg(n, n, *full, op, np.float64, dim=dim)
+            yc, idxc = ar.reduce_arg(m.cdim, m.cdim, *comp, op, np.float64, dim=dim)
+            assert np.array_equal(m.scatter(yc, mr.IDENTITY[op]), y) and np.array_equal(compactref.lift_index(m, idxc), idx)
+        for source in (int(m.used[0]), int(m.used[-1])):
+            lv, par, depth, reached = ar.bfs_parents(n, full[0], full[1], source, tr)
+            lvc, parc, dc, rc = ar.bfs_parents(m.cdim, comp[0], comp[1], int(np.searchsorted(m.used, source)), tr)
+            assert np.array_equal(m.scatter(lvc, -1), lv) and np.array_equal(compactref.lift_index(m, parc), par)
+            assert (dc, rc) == (depth, reached)
+
+
+def test_hypersparse_diag_is_the_operand_of_the_solves():
+    from matgen import hypersparse_diag
+    n, I, J, V, S = hypersparse_diag()
+    n0, I0, J0, V0, S0 = hypersparse()
+    lim = 262_144
+    assert n == n0 == HYPER_N and np.array_equal(S, S0) and (n + 15) // 16 < 1 << 26
+    off = I != J
+    assert off.sum() == (I0 != J0).sum() and np.array_equal(I[off], I0[I0 != J0]) and np.array_equal(V[off], V0[I0 != J0])
+    assert np.array_equal(I[~off], np.arange(n)) and len(I) == off.sum() + n and 4_400_000 < len(I) < 4_600_000
+    key = I.astype(np.int64) * n + J
+    assert len(np.unique(key)) == len(key)
+    assert len(np.unique((I.astype(np.int64) >> 4) * (1 << 20) + (J >> 4))) > lim
+    rowsum = np.bincount(I[off], weights=np.abs(V[off]), minlength=n)
+    assert np.array_equal(V[~off], 4.0 + rowsum) and np.all(V[~off] > rowsum)
+    m = compactref.offdiag_map(n, I, J)
+    assert lim < m.cdim < 320_000, "the references run on the rows with an off-diagonal entry"

@@ -26,27 +26,15 @@ import selectref as sel
 import semiringref as sr
 import spmmref as sp
 from compactref import T_NAMES, Product, lift_coo, lift_csr, lift_plan_arrays
-from matgen import BIGDIM_RUNGS, HYPER_N, bigdim_case, hypersparse
+from hyperops import (DTYPES, IDS, SCAN_CHAINED_MAX, SORT_BLOCK_KEYS, _assert_same_tiling, _canonical, _dev, _host, _hyper, _Profiled, _same,
+                      _same_vec)
+from matgen import BIGDIM_RUNGS, HYPER_N, bigdim_case
 from prune_ref import C_NAMES, expected
 from s3cases import poisoned
 
 pytestmark = pytest.mark.gpu
 
 torch.cuda.is_available()   # (torch's runtime first, as in the other GPU files)
-
-SCAN_CHAINED_MAX = 262_144       # SCAN_MID_ITEMS * SCAN_MID_BLOCKS: longer arrays take the three-launch scan
-SORT_BLOCK_KEYS = 4096           # keys per block of the radix sort; its histogram scan is 256 words per block
-
-
-def _bits(a):
-    a = np.asarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32) if a.dtype.kind == "f" else a
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
 
 def _check_tiled(g, lifted, label, vals=None):
     """every tiled array of the device tiling g against a compactref.LiftedTiled (vals: the expected values in another dtype)"""
@@ -58,23 +46,6 @@ def _check_tiled(g, lifted, label, vals=None):
             assert _same(got, vals), f"{label}: tiled array vals differs"
         else:
             assert lifted.matches(arr, got), f"{label}: tiled array {arr} differs"
-
-
-class _Profiled:
-    """kernel names of the launches inside the block -> .names (and .stats: name -> calls, total_ms)"""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-
-    def __enter__(self):
-        self.ctx.set_kernel_profiling(True)
-        self.ctx.reset_kernel_stats()
-        return self
-
-    def __exit__(self, *exc):
-        self.stats = self.ctx.kernel_stats()
-        self.names = set(self.stats)
-        self.ctx.set_kernel_profiling(False)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -234,12 +205,6 @@ def test_ladder_masked_pass_at_rung_22(pkg, oracle, ctx, complement):
 # ------------------------------------------------------------------------------------------------------------------------------
 # part 2: a hypersparse square tiling through every operation
 # ------------------------------------------------------------------------------------------------------------------------------
-DTYPES = (np.float64, np.float32)
-IDS = ("f64", "f32")
-INFO = ("rows", "cols", "nnz", "tile_rows", "tile_cols", "ntiles", "value_bytes")
-MINMAX = ("min_plus", "max_plus", "max_times", "min", "max")
-
-
 @pytest.fixture(scope="module")
 def tctx(pkg):
     """a context on a torch stream made current for the module (as in test_gpu_mxv.py): torch's work and the library's calls are
@@ -251,86 +216,6 @@ def tctx(pkg):
     yield c
     c.close()
     torch.cuda.set_stream(prev)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def _same_vec(got, want, kind="plus_times"):
-    """the rule of test_gpu_mxv.py: bit for bit, NaN payloads not compared, zero signs free under min / max"""
-    got, want = np.asarray(got), np.asarray(want)
-    if got.dtype != want.dtype or got.shape != want.shape:
-        return False
-    u = np.uint64 if got.dtype == np.float64 else np.uint32
-    ok = (got.view(u) == want.view(u)) | (np.isnan(got) & np.isnan(want))
-    if kind in MINMAX:
-        ok |= (got == 0) & (want == 0)
-    return bool(np.all(ok))
-
-
-def _assert_same_tiling(got, want, label, past=True):
-    """the rule of the derived operations' own tests: every info field and all twelve arrays equal those of the tiling from_coo
-    builds from the reference's entries, values bit for bit (from_coo itself is held to the lifted oracle at this size below)"""
-    for k in INFO:
-        assert getattr(got, k) == getattr(want, k), f"{label}: {k} {getattr(got, k)} != {getattr(want, k)}"
-    for name in T_NAMES:
-        assert _same(got.array(name), want.array(name)), f"{label}: array {name} differs"
-    if past:
-        assert min(got.tile_rows, got.tile_cols, got.ntiles) > SCAN_CHAINED_MAX, f"{label}: the result is not past the chained scan"
-
-
-def _canonical(I, J, V, cols):
-    o = np.argsort(np.asarray(I, np.int64) * cols + np.asarray(J), kind="stable")
-    return np.asarray(I, np.int32)[o], np.asarray(J, np.int32)[o], np.asarray(V)[o]
-
-
-class _Hyper:
-    def __init__(self, pkg, ctx, dtype):
-        self.n, self.I, self.J, V, self.S = hypersparse()
-        n = self.n
-        self.dtype = np.dtype(dtype)
-        self.V = V.astype(dtype)
-        self.A = pkg.Tiled.from_coo(ctx, n, n, self.I, self.J, self.V, dtype=dtype)
-        assert min(self.A.tile_rows, self.A.tile_cols, self.A.ntiles, self.A.nnz) > SCAN_CHAINED_MAX
-        self.coo = _canonical(self.I, self.J, self.V, n)                      # sorted by (row, column)
-        self.map = compactref.IndexMap(np.concatenate([self.I, self.J]), n)   # the vector references run on the used lines
-        self.ccsr = self.map.csr(self.I, self.J, self.V)
-        self._c = {}
-
-    def product(self, oracle, V=None):
-        """lifted COO of A*A by the serial CSR oracle (cached for the tiling's own values)"""
-        f32 = self.dtype == np.float32
-        if V is not None:
-            return compactref.product_coo(oracle, self.n, (self.I, self.J, V), (self.I, self.J, V), f32=f32)
-        if "c" not in self._c:
-            self._c["c"] = compactref.product_coo(oracle, self.n, (self.I, self.J, self.V), (self.I, self.J, self.V), f32=f32)
-            if f32:
-                self._c["c"] = (*self._c["c"][:2], self._c["c"][2].astype(np.float32))
-        return self._c["c"]
-
-    def csr(self):
-        """the full-length CSR (int64 rowptr of n + 1) for the references that want one"""
-        if "csr" not in self._c:
-            rp = np.zeros(self.n + 1, np.int64)
-            np.cumsum(np.bincount(self.I, minlength=self.n), out=rp[1:])
-            self._c["csr"] = (rp, self.coo[1].astype(np.int64), self.coo[2])
-        return self._c["csr"]
-
-
-_HYPER = {}
-
-
-def _hyper(pkg, ctx, dtype):
-    key = np.dtype(dtype).name
-    if key not in _HYPER:
-        _HYPER[key] = _Hyper(pkg, ctx, dtype)
-    return _HYPER[key]
 
 
 def _past(plan):

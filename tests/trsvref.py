@@ -14,6 +14,10 @@ level(P) = 1 + the largest level it waits for, 1 with none.  A solve is one laun
 maximal run of consecutive levels each at most merge_width wide.
 
 Inputs are CSR triples (rowptr, colidx, vals) with sorted columns.
+
+index=: the rows of a larger system that carry an off-diagonal entry, squeezed together (compactref.IndexMap), solve to the same bits
+as they do inside it once the tile edge -- the one thing here that depends on where a row sits -- is taken from the original
+indices; tests/test_compact_cpu.py holds that equal to the plain solve.
 """
 import ctypes
 import ctypes.util
@@ -37,14 +41,19 @@ def fma(a, x, c, dtype=np.float64):
     return np.float64(_libm.fma(float(a), float(x), float(c)))
 
 
-def trsv(n, rp, ci, v, b, uplo="lower", unit_diag=False, dtype=np.float64):
-    """x = T^-1 b in the order above.  ValueError naming the first row (1-based) without a stored diagonal entry unless unit_diag."""
+def trsv(n, rp, ci, v, b, uplo="lower", unit_diag=False, dtype=np.float64, index=None):
+    """x = T^-1 b in the order above.  ValueError naming the first row (1-based) without a stored diagonal entry unless unit_diag.
+    index: for a system whose rows and columns are a subset of a larger one's, squeezed together in ascending order (compactref.IndexMap),
+    the original index of every row -- ascending, n of them.  The tile edge of the upper walk is then the original system's, 16 (index[i]
+    // 16 + 1) compared with index[j], so the fmas keep the order they have there; nothing else depends on it."""
     if uplo not in UPLO:
         raise ValueError(f"unknown uplo {uplo!r}")
     dtype = np.dtype(dtype).type
     f = _libm.fmaf if dtype is np.float32 else _libm.fma
     rp = [int(p) for p in np.asarray(rp)]
     ci = [int(j) for j in np.asarray(ci)]
+    at = list(range(n)) if index is None else [int(t) for t in np.asarray(index)]
+    assert len(at) == n and all(p < q for p, q in zip(at, at[1:])), "index: one ascending original index per row"
     a = [float(t) for t in np.asarray(v, dtype)]
     bb = [float(t) for t in np.asarray(b, dtype)]
     if not unit_diag:
@@ -57,8 +66,8 @@ def trsv(n, rp, ci, v, b, uplo="lower", unit_diag=False, dtype=np.float64):
         for i in (range(n - 1, -1, -1) if upper else range(n)):
             ks = range(rp[i], rp[i + 1])
             if upper:
-                edge = TILE * (i // TILE + 1)
-                walk = [k for k in ks if ci[k] >= edge] + [k for k in reversed(ks) if i < ci[k] < edge]
+                edge = TILE * (at[i] // TILE + 1)
+                walk = [k for k in ks if at[ci[k]] >= edge] + [k for k in reversed(ks) if i < ci[k] and at[ci[k]] < edge]
             else:
                 walk = [k for k in ks if ci[k] < i]
             acc = bb[i]
@@ -71,12 +80,21 @@ def trsv(n, rp, ci, v, b, uplo="lower", unit_diag=False, dtype=np.float64):
     return np.array(x, dtype)
 
 
-def levels(n, rp, ci, uplo="lower"):
-    """the level (1-based) of every tile row, as an int array of ceil(n / 16) entries"""
+def levels(n, rp, ci, uplo="lower", index=None):
+    """the level (1-based) of every tile row, as an int array of ceil(n / 16) entries.  index (as in trsv): the tile rows are the
+    original system's, index[i] // 16, and the result holds the levels of those among them that hold a row of this system, ascending;
+    a tile row of the original system that holds none of these rows waits for nothing there: level 1."""
     rp, ci = np.asarray(rp, np.int64), np.asarray(ci, np.int64)
-    tr = (n + TILE - 1) // TILE
-    I = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) // TILE
-    J = ci // TILE
+    I = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    if index is None:
+        tr = (n + TILE - 1) // TILE
+        I, J = I // TILE, ci // TILE
+    else:
+        index = np.asarray(index, np.int64)
+        assert len(index) == n and np.all(np.diff(index) > 0), "index: one ascending original index per row"
+        lines, at = np.unique(index // TILE, return_inverse=True)
+        tr = len(lines)
+        I, J = at[I], at[ci]
     deps = [set() for _ in range(tr)]
     for p, q in zip(I.tolist(), J.tolist()):
         if (q > p) if uplo == "upper" else (q < p):
