@@ -60,8 +60,8 @@ __device__ __forceinline__ int as_slot(const int *__restrict__ rowptr, const int
     return (w >> (j & 15)) & 1u ? src_slot(ptr[t], w, (unsigned)(j & 15)) : -1;
 }
 
-// the refresh map, once: one wave per chunk of 64 consecutive Z tiles, one entry of Z per lane (ex_map_kernel's shape).  Entry
-// (i, j) of Z: inside the region A's slot at (inv_i[i], inv_j[j]) and, with an accum, C's at (i, j); outside it C's.
+// the refresh map, once.  Entry (i, j) of Z: inside the region A's slot at (inv_i[i], inv_j[j]) and, with an accum, C's at (i, j);
+// outside it C's.
 __global__ void __launch_bounds__(256) as_map_kernel(const long long *__restrict__ z_keys, long long nt, const int *__restrict__ z_ptr,
                                                      const uint8_t *__restrict__ z_rci, const int *__restrict__ inv_i,
                                                      const int *__restrict__ inv_j, int accum, const int *__restrict__ c_rowptr,
@@ -70,30 +70,14 @@ __global__ void __launch_bounds__(256) as_map_kernel(const long long *__restrict
                                                      const int *__restrict__ a_colidx, const int *__restrict__ a_ptr,
                                                      const uint32_t *__restrict__ a_rec, int2 *__restrict__ map)
 {
-    const int lane = threadIdx.x & 63;
-    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
-    if (t0 >= nt) return;   // (wave-uniform)
-    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
-    const bool live = lane < ntl;
-    const long long o = t0 + (live ? lane : 0);
-    const int my_off = live ? z_ptr[o] : INT_MAX;
-    const int e_end = z_ptr[t0 + ntl];
-    const long long key = z_keys[o];
-    const int my_tr = (int)(key >> 32), my_tc = (int)(key & 0xFFFFFFFFll);
-    const int e_begin = __shfl(my_off, 0, 64);
-    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
-        const int e = ebase + lane;
-        const int ti = chunk_tile_of(my_off, e);
-        const int tr = __shfl(my_tr, ti, 64), tc = __shfl(my_tc, ti, 64);
-        if (e >= e_end) continue;
-        const unsigned rc = z_rci[e];
-        const int i = 16 * tr + (int)(rc >> 4), j = 16 * tc + (int)(rc & 15u);
+    for_tile_entries(z_keys, nt, z_ptr, z_rci, [&](const int e, const long long il, const long long jl) {
+        const int i = (int)il, j = (int)jl;   // (below Z's rows and columns)
         const int p = inv_i ? inv_i[i] : i, q = inv_j ? inv_j[j] : j;
         const bool inside = p >= 0 && q >= 0;
         const int sa = inside ? as_slot(a_rowptr, a_colidx, a_ptr, a_rec, p, q) : -1;
         const int sc = !inside || accum ? as_slot(c_rowptr, c_colidx, c_ptr, c_rec, i, j) : -1;
         map[e] = make_int2(sc, sa);
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------

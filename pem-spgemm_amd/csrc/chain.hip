@@ -10,6 +10,7 @@
 //   chain_scatter_kernel       16 lanes per C tile (lane = tile row r): tile key + entry offset, the (r<<4|c) bytes decoded from
 //                              c_mask, and the exclusive scan of the tile-head flags written directly (entry e of kept tile j:
 //                              j at the tile's first entry, j + 1 after it) -- so no head flags and no scan over the entries.
+//                              The row loop is the candidate-tile route's write_row_bits (tiled_internal.h) without values.
 //   vals                       one device copy of c_vals.
 // C^T: C's tiling first (its tile CSC lists C's tiles in column order and its vals_t holds each tile's entries column-major),
 // then chain_count_t_kernel + scan give C^T's entry offsets and chain_gather_t_kernel writes C^T's payload: tiles in C's CSC
@@ -50,6 +51,8 @@ __global__ void __launch_bounds__(256) chain_scatter_kernel(const int *__restric
         e1 = c_tile_nnz_ptr[t + 1];
         if (e1 > e0) m = c_mask16[16 * (size_t)t + (r ^ 1)];
     }
+    // (not cand_slots: the offsets are read before the scan here, because the mask load hangs on them, and reading them again
+    // after it cost chain_scatter_kernel 2 to 4 % on the MI355X: DESIGN.md, the candidate-tile route)
     const int cnt = __popc(m);
     int inc = cnt;
 #pragma unroll
@@ -68,16 +71,7 @@ __global__ void __launch_bounds__(256) chain_scatter_kernel(const int *__restric
         tile_keys[j] = ((long long)c_tile_rowidx[t] << 32) | (long long)(unsigned)c_tile_colidx[t];
         tile_nnz_ptr[j] = e0;
     }
-    int e = e0 + (inc - cnt);
-    while (m) {
-        const int c = __builtin_ctz(m);
-        m &= m - 1u;
-        if (e < e1) {   // (the masks and the offsets come from the same counts; never write past the tile)
-            rowcolidx[e] = (uint8_t)((r << 4) | c);
-            headx[e] = e == e0 ? j : j + 1;
-        }
-        ++e;
-    }
+    write_row_bits(m, 0u, r, e0 + (inc - cnt), e0, e1, j, rowcolidx, headx);
 }
 
 // C^T's tile q is C's tile at CSC position q: its entry count

@@ -5,29 +5,24 @@
 //
 // R's order is known in closed form, so no entry is ever sorted.  A block placed at (ro, co) keeps its row-major order, and only
 // ro % 16 and co % 16 decide how its tiles are cut: a source tile covers at most 16 consecutive rows and columns of R, so it
-// reaches at most 2 x 2 tiles of R.  The route is kron.hip's and ends at the sorted tile payload derive_tiled (convert.hip) starts
-// from.  The grid lives in device tables, not in kernel arguments (a grid of 1 x 1 blocks has hundreds of cells): the prefix sums
-// of the row and of the column sizes (int64), a CcCell per cell -- what the walks read of the block, or a null marker -- and the
-// scan of the blocks' tile counts, the flat list of all source tiles.
-//   cc_cand_kernel    one lane per source tile -- its (cell, tile) by a binary search in the scan of the tile counts, the tile's
-//                     corner from its key.  First form: the exact count of R tiles its rows ro + 16p .. (clipped at the block's last
-//                     row) and its columns alike reach (1, 2 or 4); after the scan of the counts, second form: their keys
-//                     (P << bits_tc) | Q.
-//   sort              radix_sort_u64_u32 over the candidate TILES' keys, always (the aligned one-column no-sort path was not built).
-//                     Duplicates -- a tile of R several source tiles reach, of one block or of neighbouring blocks -- end up
-//                     adjacent and all but the first are dropped by the count.
-//   cc_count_kernel   16 lanes per candidate (lane = local row r): row 16P + r -> (grid row a, local row i) by a binary search in
+// reaches at most 2 x 2 tiles of R.  The grid lives in device tables, not in kernel arguments (a grid of 1 x 1 blocks has hundreds
+// of cells): the prefix sums of the row and of the column sizes (int64), a CcCell per cell -- what the walks read of the block, or
+// a null marker -- and the scan of the blocks' tile counts, the flat list of all source tiles.  The build is the candidate-tile
+// route (tiled_internal.h, extract.hip: sort, pair scan, payload setup, derive_tiled) with these stages:
+//   cc_cand_kernel    (emit) one lane per source tile -- its (cell, tile) by a binary search in the scan of the tile counts, the
+//                     tile's corner from its key.  First form, before the route: the exact count of R tiles its rows ro + 16p ..
+//                     (clipped at the block's last row) and its columns alike reach (1, 2 or 4); after the scan of the counts,
+//                     second form: their keys (P << bits_tc) | Q.
+//   sort              always (the aligned one-column no-sort path was not built).  Duplicates: a tile of R several source tiles
+//                     reach, of one block or of neighbouring blocks.
+//   cc_count_kernel   (count) lane r of a candidate: row 16P + r -> (grid row a, local row i) by a binary search in
 //                     the row prefix; columns 16Q .. 16Q+15 are cut by the column prefix into at most 16 grid-column segments; for
 //                     each segment with a block, the block's row there is at most 16 consecutive columns, so at most two source
 //                     tiles, read as one 32-bit mask (row_seg) and shifted into place.  The row's 16-bit mask is kept per candidate
-//                     row; a 16-lane sum gives the tile's count and a non-empty flag (a source tile's bounding box can reach a
-//                     result tile in which it stores nothing: such a candidate is no tile of R).
-//   pair scan         entry offsets and tile ids; the totals are read back and checked (check_result_entries) before the payload is
-//                     allocated.
-//   cc_fill_kernel    16 lanes per candidate again, the same walk: the row prefix from a 16-lane scan of the kept masks' popcounts,
-//                     then tile_keys, tile_nnz_ptr, the (r << 4) | c bytes, the tile-head scan written directly and the values, each
-//                     written once, contiguously per row.
-//   derive_tiled      everything else.
+//                     row (rmask, this unit's own buffer); a source tile's bounding box can reach a result tile in which it stores
+//                     nothing: such a candidate is no tile of R.
+//   cc_fill_kernel    (fill) the same walk from the row's first slot (the kept masks' popcounts give it), the values copied once,
+//                     contiguously per row.
 // No atomics, and the order of every array is fixed by the grid alone.  ro + i and co + j reach 2^31 - 1: every global index is
 // formed in 64 bits and narrowed only once it is a tile index, a 4-bit offset or a block coordinate; launch indices are long long.
 //
@@ -119,28 +114,18 @@ __device__ __forceinline__ unsigned cc_walk(const CcGrid &G, const long long p, 
         const RowSeg sg = row_seg(c.s, i, tc);
         const unsigned sh = (unsigned)(llo - 16 * (long long)tc);       // ... in the segment: 0 .. 15
         const unsigned width = (unsigned)(hi - lo) + 1u;                // 1 .. 16
-        unsigned bits = (sg.m >> sh) & ((1u << width) - 1u);            // bit k = the block's column llo + k
+        const unsigned bits = (sg.m >> sh) & ((1u << width) - 1u);      // bit k = the block's column llo + k
         const unsigned place = (unsigned)(lo - q0);                     // its column in the tile: 0 .. 15, place + width <= 16
         rowmask |= bits << place;
         if constexpr (FILL) {
             const VT *__restrict__ src = static_cast<const VT *>(c.vals);
-            while (bits) {
-                const unsigned k = (unsigned)__builtin_ctz(bits);
-                bits &= bits - 1u;
-                if (e < e_end) {   // (the masks and the offsets come from the same counts; never write past the tile)
-                    rowcolidx[e] = (uint8_t)((r << 4) | (int)(place + k));
-                    headx[e] = e == e0 ? tile : tile + 1;
-                    vals[e] = src[seg_slot(sg, sh + k)];
-                }
-                ++e;
-            }
+            e = write_row_bits(bits, place, r, e, e0, e_end, tile, rowcolidx, headx, vals, [&](const unsigned k) { return src[seg_slot(sg, sh + k)]; });
         }
     }
     return rowmask;
 }
 
 // 16 lanes per candidate c, lane = local row r: rmask[16c + r] = the row's mask, cnt[c] = the tile's entries, flag[c] = it has any.
-// A candidate equal to the one before it is a duplicate and has none.
 __global__ void __launch_bounds__(256) cc_count_kernel(const uint64_t *__restrict__ keys, long long ncand, CcGrid G, long long r_rows,
                                                        long long r_cols, int bits_tc, uint16_t *__restrict__ rmask, int *__restrict__ cnt,
                                                        int *__restrict__ flag)
@@ -149,23 +134,15 @@ __global__ void __launch_bounds__(256) cc_count_kernel(const uint64_t *__restric
     const int r = threadIdx.x & 15;
     unsigned m = 0u;
     if (c < ncand) {
-        const uint64_t key = keys[c];
-        const long long p = 16 * (long long)(key >> bits_tc) + r;
-        if (!(c > 0 && keys[c - 1] == key) && p < r_rows)
-            m = cc_walk<false, float>(G, p, (long long)(key & ((1ull << bits_tc) - 1ull)), r_cols, r, 0, 0, 0, 0, nullptr, nullptr, nullptr);
+        const CandKey k = cand_key(keys, c, bits_tc);
+        const long long p = 16 * k.P + r;
+        if (!k.dup && p < r_rows) m = cc_walk<false, float>(G, p, k.Q, r_cols, r, 0, 0, 0, 0, nullptr, nullptr, nullptr);
         rmask[16 * c + r] = (uint16_t)m;
     }
-    int n = __popc(m);
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) n += __shfl_xor(n, d, 16);
-    if (c < ncand && r == 0) {
-        cnt[c] = n;
-        flag[c] = n != 0;
-    }
+    cand_count(__popc(m), c, ncand, r, cnt, flag);
 }
 
-// 16 lanes per candidate, lane = local row r.  roff / rid = the scanned counts / flags (ncand + 1 values each: roff[ncand] = the
-// result's entries, rid[ncand] = its tiles).
+// 16 lanes per candidate, lane = local row r: the walk again, from the row's first slot
 template <typename VT>
 __global__ void __launch_bounds__(256) cc_fill_kernel(const uint64_t *__restrict__ keys, long long ncand, CcGrid G, long long r_cols, int bits_tc,
                                                       const uint16_t *__restrict__ rmask, const int *__restrict__ roff, const int *__restrict__ rid,
@@ -174,56 +151,21 @@ __global__ void __launch_bounds__(256) cc_fill_kernel(const uint64_t *__restrict
 {
     const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int r = threadIdx.x & 15;
-    const bool live = c < ncand;   // (every lane of a 16-lane group takes part in the scan below)
-    const int n = live ? __popc((unsigned)rmask[16 * c + r]) : 0;
-    int inc = n;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-        const int v = __shfl_up(inc, d, 16);
-        if (r >= d) inc += v;
-    }
-    if (c == 0 && r == 0) {   // closing offsets: tile_nnz_ptr[T] = nnz, headx[nnz] = T
-        const int nt = rid[ncand], nnz = roff[ncand];
-        tile_nnz_ptr[nt] = nnz;
-        headx[nnz] = nt;
-    }
-    if (!live) return;
-    const int e0 = roff[c], e1 = roff[c + 1];
-    if (e1 == e0) return;
-    const int t = rid[c];
-    const uint64_t key = keys[c];
-    const long long P = (long long)(key >> bits_tc), Q = (long long)(key & ((1ull << bits_tc) - 1ull));
-    if (r == 0) {
-        tile_keys[t] = (P << 32) | Q;
-        tile_nnz_ptr[t] = e0;
-    }
-    if (!n) return;
-    cc_walk<true, VT>(G, 16 * P + r, Q, r_cols, r, e0 + (inc - n), e0, e1, t, rowcolidx, headx, vals);
+    const int n = c < ncand ? __popc((unsigned)rmask[16 * c + r]) : 0;
+    cand_slots(c, ncand, r, n, roff, rid, tile_nnz_ptr, headx, [&](const CandSlots &s) {
+        const CandKey k = cand_key(keys, c, bits_tc);
+        cand_tile_head(r, s, k.P, k.Q, tile_keys, tile_nnz_ptr);
+        if (!n) return;
+        cc_walk<true, VT>(G, 16 * k.P + r, k.Q, r_cols, r, s.e, s.e0, s.e1, s.t, rowcolidx, headx, vals);
+    });
 }
 
-// the refresh map, once: one wave per chunk of 64 consecutive R tiles, one entry of R per lane (kr_map_kernel's shape).  Entry
-// (p, q) of R is entry (p - ro_a, q - co_b) of block (a, b): the block's tile by mask_find_tile, its slot by src_slot.
+// the refresh map, once.  Entry (p, q) of R is entry (p - ro_a, q - co_b) of block (a, b): the block's tile by mask_find_tile, its
+// slot by src_slot.
 __global__ void __launch_bounds__(256) cc_map_kernel(const long long *__restrict__ r_keys, long long nt, const int *__restrict__ r_ptr,
                                                      const uint8_t *__restrict__ r_rci, CcGrid G, int2 *__restrict__ map)
 {
-    const int lane = threadIdx.x & 63;
-    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
-    if (t0 >= nt) return;   // (wave-uniform)
-    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
-    const bool live = lane < ntl;
-    const long long o = t0 + (live ? lane : 0);
-    const int my_off = live ? r_ptr[o] : INT_MAX;
-    const int e_end = r_ptr[t0 + ntl];
-    const long long key = r_keys[o];
-    const int my_tr = (int)(key >> 32), my_tc = (int)(key & 0xFFFFFFFFll);
-    const int e_begin = __shfl(my_off, 0, 64);
-    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
-        const int e = ebase + lane;
-        const int ti = chunk_tile_of(my_off, e);
-        const long long tr = __shfl(my_tr, ti, 64), tc = __shfl(my_tc, ti, 64);
-        if (e >= e_end) continue;
-        const unsigned rc = r_rci[e];
-        const long long p = 16 * tr + (rc >> 4), q = 16 * tc + (rc & 15u);   // (below R's rows and columns)
+    for_tile_entries(r_keys, nt, r_ptr, r_rci, [&](const int e, const long long p, const long long q) {   // (p, q below R's rows and columns)
         const int a = cc_strip(G.rpre, G.grid_rows, p), b = cc_strip(G.cpre, G.grid_cols, q);
         const int cell = a * G.grid_cols + b;
         const TileSide &S = G.cells[cell].s;
@@ -234,7 +176,7 @@ __global__ void __launch_bounds__(256) cc_map_kernel(const long long *__restrict
             if (t >= 0) slot = src_slot(S.ptr[t], S.rec[16 * (size_t)t + (i & 15)], (unsigned)(j & 15));
         }
         map[e] = make_int2(cell, slot);
-    }
+    });
 }
 
 // the blocks' vals pointers, 32 cells a launch
@@ -265,8 +207,7 @@ __global__ void __launch_bounds__(256) cc_refresh_kernel(const int2 *__restrict_
 static CcCell cell_of(const pem_tiled *T)
 {
     if (!T) return CcCell{TileSide{nullptr, nullptr, nullptr, nullptr, 0, 0}, nullptr, nullptr};
-    return CcCell{TileSide{T->tile_rowptr.as<int>(), T->tile_colidx.as<int>(), T->tile_nnz_ptr.as<int>(), T->tile_rec.as<uint32_t>(), T->rows, T->cols},
-                  T->tile_keys.as<long long>(), T->vals.p};
+    return CcCell{tile_side(T), T->tile_keys.as<long long>(), T->vals.p};
 }
 
 static CcGrid grid_of(const pem_tiled *R)
@@ -274,7 +215,6 @@ static CcGrid grid_of(const pem_tiled *R)
     const Derivation &d = R->derived;
     return CcGrid{d.idx[0].as<long long>(), d.idx[0].as<long long>() + d.op + 1, d.src_tiles.as<CcCell>(), d.op, d.pattern};
 }
-
 
 // the arguments were checked (concat_args_ok): the dimensions and the sum of the blocks' entries fit an int32
 template <typename VT>
@@ -304,7 +244,7 @@ static pem_status concat_build(pem_ctx *ctx, int grid_rows, int grid_cols, const
     for (size_t k = 0; k < ncells; ++k) d.srcs[k] = blocks[k] ? blocks[k]->serial : 0;
     PEM_TRY(zero_flags(ctx));
     PEM_TRY(check_result_entries(ctx, nnz_all, fn));   // (before any kernel: a tile never holds less than one entry)
-    const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
+    const int bits_tc = bits_for((uint64_t)R->tile_cols);
     const size_t ntall = (size_t)tstart[ncells];
 
     DevBuf d_tstart, coff;   // the scan of the cells' tile counts; per source tile: the R tiles it reaches -> where its keys start
@@ -317,56 +257,29 @@ static pem_status concat_build(pem_ctx *ctx, int grid_rows, int grid_cols, const
     PEM_HIP(hipMemcpyAsync(d.src_tiles.p, cells.data(), sizeof(CcCell) * ncells, hipMemcpyHostToDevice, ctx->stream));
     PEM_HIP(hipStreamSynchronize(ctx->stream));   // (the host tables go away with this scope, whichever way it is left)
     const CcGrid G = grid_of(R);
-    if (ntall)
-        PEM_LAUNCH(ctx, cc_cand_kernel, grid_for(ntall, 256), 256, G, d_tstart.as<long long>(), (long long)ntall, bits_tc, coff.as<int>(), nullptr,
-                   nullptr);
+    auto cand = [&](int *cnt, const int *off, uint64_t *keys) {   // the counts, then (with their scan) the keys
+        PEM_LAUNCH(ctx, cc_cand_kernel, grid_for(ntall, 256), 256, G, d_tstart.as<long long>(), (long long)ntall, bits_tc, cnt, off, keys);
+    };
+    if (ntall) cand(coff.as<int>(), nullptr, nullptr);
     PEM_TRY(exclusive_scan_i32(ctx, coff.as<int>(), coff.as<int>(), ntall, ctx->d_scalars));
-    int64_t tot[2] = {0, 0};
-    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 1, tot));
-    int hf[NUM_FLAGS];
-    PEM_TRY(read_flags(ctx, hf));
-    if (hf[FLAG_OVERFLOW] || tot[0] > 0x7FFFFFFFll) {
-        set_error("%s: the result's tiles exceed the int32 index range", fn);
-        return PEM_E_OVERFLOW;
-    }
-    PEM_TRY(check_internal(hf));
+    int64_t tot[1] = {0};
+    PEM_TRY(check_candidates(ctx, 1, tot, fn));
     const size_t ncand = (size_t)tot[0];
 
-    DevBuf k0, k1, v0, v1, rmask, roff, rid;   // candidate keys (and the sort's other half and payloads); per candidate: its 16 row masks, count -> entry offset, flag -> tile id
-    PEM_TRY(k0.reserve(sizeof(uint64_t) * (ncand + 1)));
+    DevBuf rmask;   // per candidate: its 16 row masks, from the count to the fill
     PEM_TRY(rmask.reserve(sizeof(uint16_t) * 16 * (ncand + 1)));
-    PEM_TRY(roff.reserve(sizeof(int) * (ncand + 4)));
-    PEM_TRY(rid.reserve(sizeof(int) * (ncand + 4)));
-    uint64_t *keys = k0.as<uint64_t>();
-    if (ncand) {
-        PEM_LAUNCH(ctx, cc_cand_kernel, grid_for(ntall, 256), 256, G, d_tstart.as<long long>(), (long long)ntall, bits_tc, nullptr, coff.as<int>(), keys);
-        PEM_TRY(k1.reserve(sizeof(uint64_t) * (ncand + 1)));
-        PEM_TRY(v0.reserve(sizeof(uint32_t) * (ncand + 1)));
-        PEM_TRY(v1.reserve(sizeof(uint32_t) * (ncand + 1)));
-        PEM_HIP(hipMemsetAsync(v0.p, 0, sizeof(uint32_t) * ncand, ctx->stream));   // (the payload is not used)
-        uint32_t *pv;
-        PEM_TRY(radix_sort_u64_u32(ctx, k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), ncand, bits_tr + bits_tc, &keys,
-                                   &pv));
+    CandidateStages st;
+    st.emit = [&](uint64_t *keys) { cand(nullptr, coff.as<int>(), keys); };
+    st.count = [&](const uint64_t *keys, int *cnt, int *flag) {
         PEM_LAUNCH(ctx, cc_count_kernel, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, G, (long long)R->rows, (long long)R->cols, bits_tc,
-                   rmask.as<uint16_t>(), roff.as<int>(), rid.as<int>());
-    }
-    PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ncand, ctx->d_scalars, ctx->d_scalars + 1));
-    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
-    PEM_TRY(check_result_entries(ctx, tot[0], fn));
-    if (tot[0] != nnz_all) {   // (every entry of every block is exactly one entry of R)
-        set_error("%s: internal: the walk counted %lld entries, not the blocks' %lld", fn, (long long)tot[0], nnz_all);
-        return PEM_E_HIP;
-    }
-    R->nnz = tot[0];
-    R->ntiles = tot[1];
-    PEM_TRY(reserve_payload(ctx, R));
-    int *headx;
-    PEM_TRY(begin_payload(ctx, R, &headx));
-    if (ncand)
+                   rmask.as<uint16_t>(), cnt, flag);
+    };
+    st.fill = [&](const uint64_t *keys, const int *roff, const int *rid, int *headx) {
         PEM_LAUNCH(ctx, cc_fill_kernel<VT>, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, G, (long long)R->cols, bits_tc, rmask.as<uint16_t>(),
-                   roff.as<int>(), rid.as<int>(), R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->rowcolidx.as<uint8_t>(), headx,
-                   R->vals.as<VT>());
-    return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
+                   roff, rid, R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(), R->rowcolidx.as<uint8_t>(), headx, R->vals.as<VT>());
+    };
+    // (every entry of every block is exactly one entry of R)
+    return tiling_from_candidates(ctx, R, fn, ncand, true, nnz_all, "the blocks'", st);
 }
 
 // everything the host knows, in 64 bits, before anything is launched or allocated; *value_bytes = the blocks' value type

@@ -13,18 +13,19 @@
 //   ex_slots_kernel   16 lanes per output tile row (lane = r).  Lane r is a LEADER when no lane below it reads the same source tile
 //                     row; a leader's slot gets the length of that tile row's tile list, every other slot 0.  The scan of the slots
 //                     places the concatenated lists: the candidates of P.  Indices are range-checked here (FLAG_RANGE).
-//   ex_cand_kernel    one lane per candidate: its slot by a binary search in the scanned slots, its key (P, tile column).
-//   sort              only where some output tile row has two leaders or more (a second scan, of the non-first leaders, tells):
-//                     radix_sort_u64_u32 over the candidate TILES' keys; duplicates end up adjacent and all but the first are dropped
-//                     by the count.  With one leader per output tile row -- I == NULL, aligned ranges, one index repeated -- the
-//                     concatenation is already A's order and nothing is sorted or merged.
-//   ex_count_kernel   16 lanes per candidate (lane = r): the source tile by mask_find_tile, one tile_rec word, a 16-lane sum: the
-//                     tile's entry count and a non-empty flag.
-//   pair scan         entry offsets and tile ids; the totals are read back and checked (check_result_entries) before the payload
-//                     is allocated.
-//   ex_fill_kernel    16 lanes per candidate again: tile_keys, tile_nnz_ptr, the (r << 4) | c bytes, the tile-head scan written
-//                     directly (chain_scatter_kernel's way) and the values, each written once.
-//   derive_tiled      everything else.
+// From there on it is the candidate-tile route, which this unit defines for kron.hip and concat.hip too (tiled_internal.h:
+// check_candidates, tiling_from_candidates; on the device cand_key, cand_count, cand_slots, cand_tile_head, write_row_bits) with these stages:
+//   ex_cand_kernel    (emit) one lane per candidate: its slot by a binary search in the scanned slots, its key (P, tile column).
+//   sort              only where some output tile row has two leaders or more (a second scan, of the non-first leaders, tells).
+//                     With one leader per output tile row -- I == NULL, aligned ranges, one index repeated -- the concatenation is
+//                     already A's order and nothing is sorted or merged.
+//   ex_count_kernel   (count) lane r of a candidate: the source tile by mask_find_tile, one tile_rec word.
+//   ex_fill_kernel    (fill) the same word again: the row's mask as it is, its values the source run.
+// The route: the candidate keys; radix_sort_u64_u32 over the candidate TILES' keys where asked (duplicates end up adjacent and the
+// count drops all but the first); the count, 16 lanes per candidate, whose 16-lane sum is the tile's entries and a non-empty flag;
+// the pair scan to entry offsets and tile ids, the totals read back and checked (check_result_entries) before the payload is
+// allocated; the fill, 16 lanes per candidate again: tile_keys, tile_nnz_ptr, the (r << 4) | c bytes, the tile-head scan written
+// directly and the values, each written once; derive_tiled for everything else.
 // No kernel walks a tile row serially: every candidate is a lane (ex_cand_kernel) or a 16-lane group, whatever its tile row's length.
 //
 // Refresh: both patterns are independent of A's values.  The first call builds an int32 per entry, its slot in A's vals -- for a
@@ -99,25 +100,22 @@ __global__ void ex_cand_kernel(const int *__restrict__ I, const int *__restrict_
     keys[c] = ((uint64_t)(lo >> 4) << bits_tc) | (uint64_t)(unsigned)tc;
 }
 
-// what lane r of candidate c reads: A's tile at (source tile row, tc) and the tile_rec word of the source row there (0: none).
-// A candidate equal to the one before it is a duplicate and reads nothing; so does a hole (a negative index, scatter_tiling).
+// what lane r of candidate k reads: A's tile at (source tile row, k.Q) and the tile_rec word of the source row there (0: none).
+// A duplicate reads nothing; so does a hole (a negative index, scatter_tiling).
 struct ExRow {
     int t;
     uint32_t rec;
 };
-__device__ __forceinline__ ExRow ex_row(const uint64_t *__restrict__ keys, const long long c, const int r, const int *__restrict__ I,
-                                        const long long ni, const int *__restrict__ a_rowptr, const int *__restrict__ a_colidx,
-                                        const uint32_t *__restrict__ a_rec, const int bits_tc, long long *key_out)
+__device__ __forceinline__ ExRow ex_row(const CandKey &k, const int r, const int *__restrict__ I, const long long ni,
+                                        const int *__restrict__ a_rowptr, const int *__restrict__ a_colidx, const uint32_t *__restrict__ a_rec)
 {
     ExRow x = {-1, 0u};
-    const uint64_t key = keys[c];
-    *key_out = (long long)key;
-    if (c > 0 && keys[c - 1] == key) return x;
-    const long long p = 16 * (long long)(key >> bits_tc) + r;
+    if (k.dup) return x;
+    const long long p = 16 * k.P + r;
     if (p >= ni) return x;
     const int s = ex_src(I, p);
     if (s < 0) return x;
-    x.t = mask_find_tile(a_rowptr, a_colidx, s >> 4, (int)(key & ((1ull << bits_tc) - 1ull)));
+    x.t = mask_find_tile(a_rowptr, a_colidx, s >> 4, (int)k.Q);
     if (x.t >= 0) x.rec = a_rec[16 * (size_t)x.t + (s & 15)];
     return x;
 }
@@ -131,20 +129,11 @@ __global__ void __launch_bounds__(256) ex_count_kernel(const uint64_t *__restric
     const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int r = threadIdx.x & 15;
     int n = 0;
-    if (c < ncand) {
-        long long key;
-        n = __popc(ex_row(keys, c, r, I, ni, a_rowptr, a_colidx, a_rec, bits_tc, &key).rec & 0xFFFFu);
-    }
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) n += __shfl_xor(n, d, 16);
-    if (c < ncand && r == 0) {
-        cnt[c] = n;
-        flag[c] = n != 0;
-    }
+    if (c < ncand) n = __popc(ex_row(cand_key(keys, c, bits_tc), r, I, ni, a_rowptr, a_colidx, a_rec).rec & 0xFFFFu);
+    cand_count(n, c, ncand, r, cnt, flag);
 }
 
-// 16 lanes per candidate, lane = local row r.  roff / rid = the scanned counts / flags (ncand + 1 values each: roff[ncand] = the
-// result's entries, rid[ncand] = its tiles).  Row r of output tile rid[c] is the source row's mask; its values are the source run.
+// 16 lanes per candidate, lane = local row r.  Row r of output tile rid[c] is the source row's mask; its values are the source run.
 template <typename VT>
 __global__ void __launch_bounds__(256) ex_fill_kernel(const uint64_t *__restrict__ keys, long long ncand, const int *__restrict__ I, long long ni,
                                                       const int *__restrict__ a_rowptr, const int *__restrict__ a_colidx,
@@ -156,75 +145,33 @@ __global__ void __launch_bounds__(256) ex_fill_kernel(const uint64_t *__restrict
 {
     const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int r = threadIdx.x & 15;
-    const bool live = c < ncand;   // (every lane of a 16-lane group takes part in the scan below)
     ExRow x = {-1, 0u};
-    long long key = 0;
-    if (live) x = ex_row(keys, c, r, I, ni, a_rowptr, a_colidx, a_rec, bits_tc, &key);
-    unsigned m = x.rec & 0xFFFFu;
-    const int n = __popc(m);
-    int inc = n;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-        const int v = __shfl_up(inc, d, 16);
-        if (r >= d) inc += v;
+    CandKey k = {0, 0, false};
+    if (c < ncand) {
+        k = cand_key(keys, c, bits_tc);
+        x = ex_row(k, r, I, ni, a_rowptr, a_colidx, a_rec);
     }
-    if (c == 0 && r == 0) {   // closing offsets: tile_nnz_ptr[T] = nnz, headx[nnz] = T
-        const int nt = rid[ncand], nnz = roff[ncand];
-        tile_nnz_ptr[nt] = nnz;
-        headx[nnz] = nt;
-    }
-    if (!live) return;
-    const int e0 = roff[c], e1 = roff[c + 1];
-    if (e1 == e0) return;
-    const int j = rid[c];
-    if (r == 0) {
-        tile_keys[j] = ((key >> bits_tc) << 32) | (key & ((1ll << bits_tc) - 1ll));
-        tile_nnz_ptr[j] = e0;
-    }
-    if (!m) return;
-    int e = e0 + (inc - n);
-    const VT *src = a_vals + a_ptr[x.t] + (int)(x.rec >> 16);
-    while (m) {
-        const int col = __builtin_ctz(m);
-        m &= m - 1u;
-        if (e < e1) {   // (the masks and the offsets come from the same counts; never write past the tile)
-            rowcolidx[e] = (uint8_t)((r << 4) | col);
-            headx[e] = e == e0 ? j : j + 1;
-            vals[e] = *src;
-        }
-        ++e;
-        ++src;
-    }
+    const unsigned m = x.rec & 0xFFFFu;
+    cand_slots(c, ncand, r, __popc(m), roff, rid, tile_nnz_ptr, headx, [&](const CandSlots &s) {
+        cand_tile_head(r, s, k.P, k.Q, tile_keys, tile_nnz_ptr);
+        if (!m) return;
+        const VT *src = a_vals + a_ptr[x.t] + (int)(x.rec >> 16);
+        write_row_bits(m, 0u, r, s.e, s.e0, s.e1, s.t, rowcolidx, headx, vals, [&](unsigned) { return *src++; });
+    });
 }
 
-// the refresh map of an extract, once: one wave per chunk of 64 consecutive R tiles, one entry of R per lane (sel_map_kernel's
-// shape).  Entry (p, q) of R is entry (I[p], J[q]) of A: A's tile there by mask_find_tile, its slot by src_slot.
+// the refresh map of an extract, once.  Entry (p, q) of R is entry (I[p], J[q]) of A: A's tile there by mask_find_tile, its slot by
+// src_slot.
 __global__ void __launch_bounds__(256) ex_map_kernel(const long long *__restrict__ r_keys, long long nt, const int *__restrict__ r_ptr,
                                                      const uint8_t *__restrict__ r_rci, const int *__restrict__ I, const int *__restrict__ J,
                                                      const int *__restrict__ a_rowptr, const int *__restrict__ a_colidx,
                                                      const int *__restrict__ a_ptr, const uint32_t *__restrict__ a_rec, int *__restrict__ map)
 {
-    const int lane = threadIdx.x & 63;
-    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
-    if (t0 >= nt) return;   // (wave-uniform)
-    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
-    const bool live = lane < ntl;
-    const long long o = t0 + (live ? lane : 0);
-    const int my_off = live ? r_ptr[o] : INT_MAX;
-    const int e_end = r_ptr[t0 + ntl];
-    const long long key = r_keys[o];
-    const int my_tr = (int)(key >> 32), my_tc = (int)(key & 0xFFFFFFFFll);
-    const int e_begin = __shfl(my_off, 0, 64);
-    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
-        const int e = ebase + lane;
-        const int ti = chunk_tile_of(my_off, e);
-        const long long tr = __shfl(my_tr, ti, 64), tc = __shfl(my_tc, ti, 64);
-        if (e >= e_end) continue;
-        const unsigned rc = r_rci[e];
-        const int si = ex_src(I, 16 * tr + (rc >> 4)), sj = ex_src(J, 16 * tc + (rc & 15u));
+    for_tile_entries(r_keys, nt, r_ptr, r_rci, [&](const int e, const long long p, const long long q) {
+        const int si = ex_src(I, p), sj = ex_src(J, q);
         const int t = mask_find_tile(a_rowptr, a_colidx, si >> 4, sj >> 4);
         map[e] = t >= 0 ? src_slot(a_ptr[t], a_rec[16 * (size_t)t + (si & 15)], (unsigned)(sj & 15)) : 0;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -237,7 +184,7 @@ static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, i
 {
     set_tiled_shape(G, A->value_bytes, (int)ni, A->cols);
     const size_t np = (size_t)G->tile_rows, ns = 16 * np;
-    const int bits_tr = bits_for((uint64_t)G->tile_rows), bits_tc = bits_for((uint64_t)G->tile_cols);
+    const int bits_tc = bits_for((uint64_t)G->tile_cols);
     DevBuf slots, later;   // per (output tile row, local row): candidates it leads -> their offset; a non-first leader
     PEM_TRY(slots.reserve(sizeof(int) * (ns + 4)));
     PEM_TRY(later.reserve(sizeof(int) * (ns + 4)));
@@ -245,30 +192,57 @@ static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, i
                slots.as<int>(), later.as<int>(), ctx->d_flags);
     PEM_TRY(exclusive_scan_i32_pair(ctx, slots.as<int>(), later.as<int>(), ns, ctx->d_scalars, ctx->d_scalars + 1));
     int64_t tot[2] = {0, 0};
-    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
-    int hf[NUM_FLAGS];
-    PEM_TRY(read_flags(ctx, hf));
-    if (hf[FLAG_RANGE]) {
+    PEM_TRY(check_candidates(ctx, 2, tot, fn, [&](const int *hf) {
+        if (!hf[FLAG_RANGE]) return PEM_OK;
         set_error("%s: an index is negative or not below the dimension (%d)", fn, A->rows);
         return PEM_E_INVALID;
-    }
+    }));
+    const size_t ncand = (size_t)tot[0];
+    const bool merge = tot[1] != 0;   // some output tile row draws on two source tile rows or more: only then are the candidates sorted
+    const long long nc = (long long)ncand;
+    const int *a_rowptr = A->tile_rowptr.as<int>(), *a_colidx = A->tile_colidx.as<int>();
+    const uint32_t *a_rec = A->tile_rec.as<uint32_t>();
+    CandidateStages st;
+    st.emit = [&](uint64_t *keys) {
+        PEM_LAUNCH(ctx, ex_cand_kernel, grid_for(ncand, 256), 256, dI, a_rowptr, a_colidx, slots.as<int>(), (long long)ns, nc, bits_tc, keys);
+    };
+    st.count = [&](const uint64_t *keys, int *cnt, int *flag) {
+        PEM_LAUNCH(ctx, ex_count_kernel, grid_for(16 * ncand, 256), 256, keys, nc, dI, (long long)ni, a_rowptr, a_colidx, a_rec, bits_tc, cnt, flag);
+    };
+    st.fill = [&](const uint64_t *keys, const int *roff, const int *rid, int *headx) {
+        PEM_LAUNCH(ctx, ex_fill_kernel<VT>, grid_for(16 * ncand, 256), 256, keys, nc, dI, (long long)ni, a_rowptr, a_colidx, a_rec,
+                   A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(), bits_tc, roff, rid, G->tile_keys.as<long long>(), G->tile_nnz_ptr.as<int>(),
+                   G->rowcolidx.as<uint8_t>(), headx, G->vals.as<VT>());
+    };
+    return tiling_from_candidates(ctx, G, fn, ncand, merge, -1, "", st);
+}
+
+// ---- the candidate-tile route's host half (tiled_internal.h) ----
+pem_status pem::check_candidates(pem_ctx *ctx, int ntot, int64_t *tot, const char *fn, const std::function<pem_status(const int *flags)> &refuse)
+{
+    PEM_TRY(read_scalars(ctx, ctx->d_scalars, ntot, tot));
+    int hf[NUM_FLAGS];
+    PEM_TRY(read_flags(ctx, hf));
+    if (refuse) PEM_TRY(refuse(hf));
     if (hf[FLAG_OVERFLOW] || tot[0] > 0x7FFFFFFFll) {
         set_error("%s: the result's tiles exceed the int32 index range", fn);
         return PEM_E_OVERFLOW;
     }
-    PEM_TRY(check_internal(hf));
-    const size_t ncand = (size_t)tot[0];
-    const bool merge = tot[1] != 0;   // some output tile row draws on two source tile rows or more
+    return check_internal(hf);
+}
 
+pem_status pem::tiling_from_candidates(pem_ctx *ctx, pem_tiled *R, const char *fn, size_t ncand, bool sort, int64_t expect_nnz,
+                                       const char *expect_what, const CandidateStages &stages)
+{
+    const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
     DevBuf k0, k1, v0, v1, roff, rid;   // candidate keys (and the sort's other half and payloads); per candidate: count -> entry offset, flag -> tile id
     PEM_TRY(k0.reserve(sizeof(uint64_t) * (ncand + 1)));
     PEM_TRY(roff.reserve(sizeof(int) * (ncand + 4)));
     PEM_TRY(rid.reserve(sizeof(int) * (ncand + 4)));
     uint64_t *keys = k0.as<uint64_t>();
     if (ncand) {
-        PEM_LAUNCH(ctx, ex_cand_kernel, grid_for(ncand, 256), 256, dI, A->tile_rowptr.as<int>(), A->tile_colidx.as<int>(), slots.as<int>(),
-                   (long long)ns, (long long)ncand, bits_tc, keys);
-        if (merge) {
+        stages.emit(keys);
+        if (sort) {   // duplicates end up adjacent, and the count drops all but the first
             PEM_TRY(k1.reserve(sizeof(uint64_t) * (ncand + 1)));
             PEM_TRY(v0.reserve(sizeof(uint32_t) * (ncand + 1)));
             PEM_TRY(v1.reserve(sizeof(uint32_t) * (ncand + 1)));
@@ -277,22 +251,23 @@ static pem_status gather_rows(pem_ctx *ctx, const pem_tiled *A, const int *dI, i
             PEM_TRY(radix_sort_u64_u32(ctx, k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), ncand, bits_tr + bits_tc,
                                        &keys, &pv));
         }
-        PEM_LAUNCH(ctx, ex_count_kernel, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, dI, (long long)ni, A->tile_rowptr.as<int>(),
-                   A->tile_colidx.as<int>(), A->tile_rec.as<uint32_t>(), bits_tc, roff.as<int>(), rid.as<int>());
+        stages.count(keys, roff.as<int>(), rid.as<int>());
     }
     PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ncand, ctx->d_scalars, ctx->d_scalars + 1));
+    int64_t tot[2] = {0, 0};
     PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
     PEM_TRY(check_result_entries(ctx, tot[0], fn));
-    G->nnz = tot[0];
-    G->ntiles = tot[1];
-    PEM_TRY(reserve_payload(ctx, G));
+    if (expect_nnz >= 0 && tot[0] != expect_nnz) {
+        set_error("%s: internal: the walk counted %lld entries, not %s %lld", fn, (long long)tot[0], expect_what, (long long)expect_nnz);
+        return PEM_E_HIP;
+    }
+    R->nnz = tot[0];
+    R->ntiles = tot[1];
+    PEM_TRY(reserve_payload(ctx, R));
     int *headx;
-    PEM_TRY(begin_payload(ctx, G, &headx));
-    if (ncand)
-        PEM_LAUNCH(ctx, ex_fill_kernel<VT>, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, dI, (long long)ni, A->tile_rowptr.as<int>(),
-                   A->tile_colidx.as<int>(), A->tile_rec.as<uint32_t>(), A->tile_nnz_ptr.as<int>(), A->vals.as<VT>(), bits_tc, roff.as<int>(),
-                   rid.as<int>(), G->tile_keys.as<long long>(), G->tile_nnz_ptr.as<int>(), G->rowcolidx.as<uint8_t>(), headx, G->vals.as<VT>());
-    return derive_tiled(ctx, G, headx, bits_tr, bits_tc);
+    PEM_TRY(begin_payload(ctx, R, &headx));
+    if (ncand) stages.fill(keys, roff.as<int>(), rid.as<int>(), headx);
+    return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
 }
 
 static pem_status gather(pem_ctx *ctx, const pem_tiled *A, const int *dI, int64_t ni, bool holes, pem_tiled *G, const char *fn)

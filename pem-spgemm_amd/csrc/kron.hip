@@ -4,27 +4,22 @@
 //
 // R's order is known in closed form, so no entry is ever sorted.  Row p = i*mB + k of R holds, in ascending column order,
 // "for j in A(i, :) ascending, for l in B(k, :) ascending": a tile's row-major order falls out of walking A's row and B's row.  An
-// (A entry, B tile) pair covers at most 16 consecutive rows and columns of R, so it reaches at most 2 x 2 tiles of R.  The route
-// mirrors extract.hip's and ends at the sorted tile payload derive_tiled (convert.hip) starts from:
-//   kr_cand_kernel    one lane per (A entry, B tile) pair -- A's entry coordinates from its tile key and (r << 4) | c byte, the tile by
-//                     a binary search in A's tile_nnz_ptr.  First form: the pair's exact count of R tiles (1, 2 or 4); after the scan
-//                     of the counts, second form: their keys (P << bits_tc) | Q.
-//   sort              radix_sort_u64_u32 over the candidate TILES' keys, always (the aligned no-sort path was not built: A's entries
-//                     come in tile order, not row order, so in-order candidates would need a pass of their own).  Duplicates -- a
-//                     tile of R several pairs reach, every tile when B is small -- end up adjacent and all but the first are dropped
-//                     by the count.
-//   kr_count_kernel   16 lanes per candidate (lane = local row r): row 16P + r -> (i, k) by one division; the at most 16 values of j
+// (A entry, B tile) pair covers at most 16 consecutive rows and columns of R, so it reaches at most 2 x 2 tiles of R.  The build
+// is the candidate-tile route (tiled_internal.h, extract.hip: sort, pair scan, payload setup, derive_tiled) with these stages:
+//   kr_cand_kernel    (emit) one lane per (A entry, B tile) pair -- A's entry coordinates from its tile key and (r << 4) | c byte, the
+//                     tile by a binary search in A's tile_nnz_ptr.  First form, before the route: the pair's exact count of R tiles
+//                     (1, 2 or 4); after the scan of the counts, second form: their keys (P << bits_tc) | Q.
+//   sort              always (the aligned no-sort path was not built: A's entries come in tile order, not row order, so in-order
+//                     candidates would need a pass of their own).  Duplicates: a tile of R several pairs reach, every tile when B is
+//                     small.
+//   kr_count_kernel   (count) lane r of a candidate: row 16P + r -> (i, k) by one division; the at most 16 values of j
 //                     whose blocks reach columns 16Q .. 16Q+15 lie in at most two tile columns of A, found once by tile_lower_bound
 //                     and read as one 32-bit row mask; for each stored A(i, j) the segment of B's row k lies in at most two tiles of
 //                     B, looked up only when its tile column changes (with nB <= 16 once per row), and is shifted into place.  The
-//                     row's 16-bit mask is kept per candidate row; a 16-lane sum gives the tile's count and a non-empty flag (a
-//                     candidate whose B tile has nothing in this corner is no tile of R).
-//   pair scan         entry offsets and tile ids; the totals are read back and checked (check_result_entries) before the payload is
-//                     allocated.
-//   kr_fill_kernel    16 lanes per candidate again, the same walk: the row prefix from a 16-lane scan of the kept masks' popcounts,
-//                     then tile_keys, tile_nnz_ptr, the (r << 4) | c bytes, the tile-head scan written directly
-//                     (chain_scatter_kernel's way) and the values op(a, b), each written once, contiguously per row.
-//   derive_tiled      everything else.
+//                     row's 16-bit mask is kept per candidate row (rmask, this unit's own buffer); a candidate whose B tile has
+//                     nothing in this corner is no tile of R.
+//   kr_fill_kernel    (fill) the same walk from the row's first slot (the kept masks' popcounts give it), the values op(a, b) written
+//                     once, contiguously per row.
 // No atomics, and the order of every array is fixed by the operands alone.  p = i*mB + k and q = j*nB + l reach 2^31 - 1: products
 // are formed in 64 bits and narrowed only once they are a tile index, a 4-bit offset or an operand coordinate.
 //
@@ -40,8 +35,8 @@ using namespace pem;
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
-// (what the walks read of an operand is a TileSide; a row's 32 columns from a tile column on come from row_seg / seg_slot:
-// tiled_internal.h, shared with concat.hip)
+// (what the walks read of an operand is a TileSide, tile_side(T); a row's 32 columns from a tile column on come from row_seg /
+// seg_slot: tiled_internal.h, shared with concat.hip)
 
 // One lane per (A entry ea, B tile tb), x = ea * tb_count + tb.  The pair's block of R is rows i*mB + 16K .. (clipped at B's last
 // row) and columns j*nB + 16L .. alike: 1 or 2 tile rows times 1 or 2 tile columns.  coff == null: cnt[x] = that count.  Else:
@@ -109,29 +104,20 @@ __device__ __forceinline__ unsigned kr_walk(const TileSide &A, const TileSide &B
         }
         const unsigned sh = (unsigned)(llo - 16 * (long long)c);           // B's column llo in the segment: 0 .. 15
         const unsigned width = (unsigned)(lhi - llo) + 1u;                 // 1 .. 16
-        unsigned bits = (sb.m >> sh) & ((1u << width) - 1u);               // bit b = B's column llo + b
+        const unsigned bits = (sb.m >> sh) & ((1u << width) - 1u);         // bit b = B's column llo + b
         const unsigned place = (unsigned)(off + llo);                      // its column in the tile: 0 .. 15, place + width <= 16
         rowmask |= bits << place;
         if constexpr (FILL) {
             if (!bits) continue;
             const VT a = a_vals[seg_slot(sa, ab)];
-            while (bits) {
-                const unsigned b = (unsigned)__builtin_ctz(bits);
-                bits &= bits - 1u;
-                if (e < e_end) {   // (the masks and the offsets come from the same counts; never write past the tile)
-                    rowcolidx[e] = (uint8_t)((r << 4) | (int)(place + b));
-                    headx[e] = e == e0 ? tile : tile + 1;
-                    vals[e] = pem_binop_value<VT>(op, a, b_vals[seg_slot(sb, sh + b)]);
-                }
-                ++e;
-            }
+            e = write_row_bits(bits, place, r, e, e0, e_end, tile, rowcolidx, headx, vals,
+                               [&](const unsigned b) { return pem_binop_value<VT>(op, a, b_vals[seg_slot(sb, sh + b)]); });
         }
     }
     return rowmask;
 }
 
 // 16 lanes per candidate c, lane = local row r: rmask[16c + r] = the row's mask, cnt[c] = the tile's entries, flag[c] = it has any.
-// A candidate equal to the one before it is a duplicate and has none.
 __global__ void __launch_bounds__(256) kr_count_kernel(const uint64_t *__restrict__ keys, long long ncand, TileSide A, TileSide B, long long r_rows,
                                                        int bits_tc, uint16_t *__restrict__ rmask, int *__restrict__ cnt, int *__restrict__ flag)
 {
@@ -139,24 +125,15 @@ __global__ void __launch_bounds__(256) kr_count_kernel(const uint64_t *__restric
     const int r = threadIdx.x & 15;
     unsigned m = 0u;
     if (c < ncand) {
-        const uint64_t key = keys[c];
-        const long long p = 16 * (long long)(key >> bits_tc) + r;
-        if (!(c > 0 && keys[c - 1] == key) && p < r_rows)
-            m = kr_walk<false, float>(A, B, p, (long long)(key & ((1ull << bits_tc) - 1ull)), r, 0, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr,
-                                      nullptr);
+        const CandKey k = cand_key(keys, c, bits_tc);
+        const long long p = 16 * k.P + r;
+        if (!k.dup && p < r_rows) m = kr_walk<false, float>(A, B, p, k.Q, r, 0, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr);
         rmask[16 * c + r] = (uint16_t)m;
     }
-    int n = __popc(m);
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) n += __shfl_xor(n, d, 16);
-    if (c < ncand && r == 0) {
-        cnt[c] = n;
-        flag[c] = n != 0;
-    }
+    cand_count(__popc(m), c, ncand, r, cnt, flag);
 }
 
-// 16 lanes per candidate, lane = local row r.  roff / rid = the scanned counts / flags (ncand + 1 values each: roff[ncand] = the
-// result's entries, rid[ncand] = its tiles).
+// 16 lanes per candidate, lane = local row r: the walk again, from the row's first slot
 template <typename VT>
 __global__ void __launch_bounds__(256) kr_fill_kernel(const uint64_t *__restrict__ keys, long long ncand, TileSide A, TileSide B, int bits_tc, int op,
                                                       const VT *__restrict__ a_vals, const VT *__restrict__ b_vals,
@@ -166,73 +143,34 @@ __global__ void __launch_bounds__(256) kr_fill_kernel(const uint64_t *__restrict
 {
     const long long c = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int r = threadIdx.x & 15;
-    const bool live = c < ncand;   // (every lane of a 16-lane group takes part in the scan below)
-    const int n = live ? __popc((unsigned)rmask[16 * c + r]) : 0;
-    int inc = n;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-        const int v = __shfl_up(inc, d, 16);
-        if (r >= d) inc += v;
-    }
-    if (c == 0 && r == 0) {   // closing offsets: tile_nnz_ptr[T] = nnz, headx[nnz] = T
-        const int nt = rid[ncand], nnz = roff[ncand];
-        tile_nnz_ptr[nt] = nnz;
-        headx[nnz] = nt;
-    }
-    if (!live) return;
-    const int e0 = roff[c], e1 = roff[c + 1];
-    if (e1 == e0) return;
-    const int t = rid[c];
-    const uint64_t key = keys[c];
-    const long long P = (long long)(key >> bits_tc), Q = (long long)(key & ((1ull << bits_tc) - 1ull));
-    if (r == 0) {
-        tile_keys[t] = (P << 32) | Q;
-        tile_nnz_ptr[t] = e0;
-    }
-    if (!n) return;
-    kr_walk<true, VT>(A, B, 16 * P + r, Q, r, op, a_vals, b_vals, e0 + (inc - n), e0, e1, t, rowcolidx, headx, vals);
+    const int n = c < ncand ? __popc((unsigned)rmask[16 * c + r]) : 0;
+    cand_slots(c, ncand, r, n, roff, rid, tile_nnz_ptr, headx, [&](const CandSlots &s) {
+        const CandKey k = cand_key(keys, c, bits_tc);
+        cand_tile_head(r, s, k.P, k.Q, tile_keys, tile_nnz_ptr);
+        if (!n) return;
+        kr_walk<true, VT>(A, B, 16 * k.P + r, k.Q, r, op, a_vals, b_vals, s.e, s.e0, s.e1, s.t, rowcolidx, headx, vals);
+    });
 }
 
-// the refresh map, once: one wave per chunk of 64 consecutive R tiles, one entry of R per lane (ex_map_kernel's shape).  Entry
-// (p, q) of R is A(p / mB, q / nB) op B(p % mB, q % nB): each operand's tile by mask_find_tile, its slot by src_slot.
+// the refresh map, once.  Entry (p, q) of R is A(p / mB, q / nB) op B(p % mB, q % nB): each operand's tile by mask_find_tile, its
+// slot by src_slot.
 __global__ void __launch_bounds__(256) kr_map_kernel(const long long *__restrict__ r_keys, long long nt, const int *__restrict__ r_ptr,
                                                      const uint8_t *__restrict__ r_rci, TileSide A, TileSide B, int2 *__restrict__ map)
 {
-    const int lane = threadIdx.x & 63;
-    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
-    if (t0 >= nt) return;   // (wave-uniform)
-    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
-    const bool live = lane < ntl;
-    const long long o = t0 + (live ? lane : 0);
-    const int my_off = live ? r_ptr[o] : INT_MAX;
-    const int e_end = r_ptr[t0 + ntl];
-    const long long key = r_keys[o];
-    const int my_tr = (int)(key >> 32), my_tc = (int)(key & 0xFFFFFFFFll);
-    const int e_begin = __shfl(my_off, 0, 64);
     const unsigned mB = (unsigned)B.rows, nB = (unsigned)B.cols;
-    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
-        const int e = ebase + lane;
-        const int ti = chunk_tile_of(my_off, e);
-        const long long tr = __shfl(my_tr, ti, 64), tc = __shfl(my_tc, ti, 64);
-        if (e >= e_end) continue;
-        const unsigned rc = r_rci[e];
-        const unsigned p = (unsigned)(16 * tr + (rc >> 4)), q = (unsigned)(16 * tc + (rc & 15u));   // (below R's rows and columns)
+    for_tile_entries(r_keys, nt, r_ptr, r_rci, [&](const int e, const long long pl, const long long ql) {
+        const unsigned p = (unsigned)pl, q = (unsigned)ql;   // (below R's rows and columns)
         const unsigned i = p / mB, k = p - i * mB, j = q / nB, l = q - j * nB;
         const int t_a = mask_find_tile(A.rowptr, A.colidx, (int)(i >> 4), (int)(j >> 4));
         const int t_b = mask_find_tile(B.rowptr, B.colidx, (int)(k >> 4), (int)(l >> 4));
         map[e] = make_int2(t_a >= 0 ? src_slot(A.ptr[t_a], A.rec[16 * (size_t)t_a + (i & 15u)], j & 15u) : 0,
                            t_b >= 0 ? src_slot(B.ptr[t_b], B.rec[16 * (size_t)t_b + (k & 15u)], l & 15u) : 0);
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static TileSide side_of(const pem_tiled *T)
-{
-    return TileSide{T->tile_rowptr.as<int>(), T->tile_colidx.as<int>(), T->tile_nnz_ptr.as<int>(), T->tile_rec.as<uint32_t>(), T->rows, T->cols};
-}
-
 // the arguments were checked (kron_sizes_ok): the dimensions and nnz(A) * nnz(B) fit an int32
 template <typename VT>
 static pem_status kron_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled *R, const char *fn)
@@ -244,64 +182,37 @@ static pem_status kron_build(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *
     d.src[1] = B->serial;
     d.op = op;
     PEM_TRY(zero_flags(ctx));
-    const int bits_tr = bits_for((uint64_t)R->tile_rows), bits_tc = bits_for((uint64_t)R->tile_cols);
+    const int bits_tc = bits_for((uint64_t)R->tile_cols);
     const size_t ta = (size_t)A->ntiles, tb = (size_t)B->ntiles;
     const size_t npairs = A->nnz && B->nnz ? (size_t)A->nnz * tb : 0;   // (<= nnz(A) * nnz(B))
     DevBuf coff;   // per (A entry, B tile): the R tiles it reaches -> where its keys start
     PEM_TRY(coff.reserve(sizeof(int) * (npairs + 4)));
-    if (npairs)
+    auto cand = [&](int *cnt, const int *off, uint64_t *keys) {   // the counts, then (with their scan) the keys
         PEM_LAUNCH(ctx, kr_cand_kernel, grid_for(npairs, 256), 256, A->tile_keys.as<long long>(), A->tile_nnz_ptr.as<int>(), (long long)ta,
-                   A->rowcolidx.as<uint8_t>(), B->tile_keys.as<long long>(), (long long)tb, (long long)npairs, B->rows, B->cols, bits_tc, coff.as<int>(),
-                   nullptr, nullptr);
+                   A->rowcolidx.as<uint8_t>(), B->tile_keys.as<long long>(), (long long)tb, (long long)npairs, B->rows, B->cols, bits_tc, cnt, off, keys);
+    };
+    if (npairs) cand(coff.as<int>(), nullptr, nullptr);
     PEM_TRY(exclusive_scan_i32(ctx, coff.as<int>(), coff.as<int>(), npairs, ctx->d_scalars));
-    int64_t tot[2] = {0, 0};
-    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 1, tot));
-    int hf[NUM_FLAGS];
-    PEM_TRY(read_flags(ctx, hf));
-    if (hf[FLAG_OVERFLOW] || tot[0] > 0x7FFFFFFFll) {
-        set_error("%s: the result's tiles exceed the int32 index range", fn);
-        return PEM_E_OVERFLOW;
-    }
-    PEM_TRY(check_internal(hf));
+    int64_t tot[1] = {0};
+    PEM_TRY(check_candidates(ctx, 1, tot, fn));
     const size_t ncand = (size_t)tot[0];
 
-    DevBuf k0, k1, v0, v1, rmask, roff, rid;   // candidate keys (and the sort's other half and payloads); per candidate: its 16 row masks, count -> entry offset, flag -> tile id
-    PEM_TRY(k0.reserve(sizeof(uint64_t) * (ncand + 1)));
+    DevBuf rmask;   // per candidate: its 16 row masks, from the count to the fill
     PEM_TRY(rmask.reserve(sizeof(uint16_t) * 16 * (ncand + 1)));
-    PEM_TRY(roff.reserve(sizeof(int) * (ncand + 4)));
-    PEM_TRY(rid.reserve(sizeof(int) * (ncand + 4)));
-    uint64_t *keys = k0.as<uint64_t>();
-    if (ncand) {
-        PEM_LAUNCH(ctx, kr_cand_kernel, grid_for(npairs, 256), 256, A->tile_keys.as<long long>(), A->tile_nnz_ptr.as<int>(), (long long)ta,
-                   A->rowcolidx.as<uint8_t>(), B->tile_keys.as<long long>(), (long long)tb, (long long)npairs, B->rows, B->cols, bits_tc, nullptr,
-                   coff.as<int>(), keys);
-        PEM_TRY(k1.reserve(sizeof(uint64_t) * (ncand + 1)));
-        PEM_TRY(v0.reserve(sizeof(uint32_t) * (ncand + 1)));
-        PEM_TRY(v1.reserve(sizeof(uint32_t) * (ncand + 1)));
-        PEM_HIP(hipMemsetAsync(v0.p, 0, sizeof(uint32_t) * ncand, ctx->stream));   // (the payload is not used)
-        uint32_t *pv;
-        PEM_TRY(radix_sort_u64_u32(ctx, k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(), ncand, bits_tr + bits_tc, &keys,
-                                   &pv));
-        PEM_LAUNCH(ctx, kr_count_kernel, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, side_of(A), side_of(B), (long long)R->rows, bits_tc,
-                   rmask.as<uint16_t>(), roff.as<int>(), rid.as<int>());
-    }
-    PEM_TRY(exclusive_scan_i32_pair(ctx, roff.as<int>(), rid.as<int>(), ncand, ctx->d_scalars, ctx->d_scalars + 1));
-    PEM_TRY(read_scalars(ctx, ctx->d_scalars, 2, tot));
-    PEM_TRY(check_result_entries(ctx, tot[0], fn));
-    if (tot[0] != A->nnz * B->nnz) {   // (every (A entry, B entry) pair is exactly one entry of R)
-        set_error("%s: internal: the walk counted %lld entries, not nnz(A) * nnz(B) = %lld", fn, (long long)tot[0], (long long)(A->nnz * B->nnz));
-        return PEM_E_HIP;
-    }
-    R->nnz = tot[0];
-    R->ntiles = tot[1];
-    PEM_TRY(reserve_payload(ctx, R));
-    int *headx;
-    PEM_TRY(begin_payload(ctx, R, &headx));
-    if (ncand)
-        PEM_LAUNCH(ctx, kr_fill_kernel<VT>, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, side_of(A), side_of(B), bits_tc, op, A->vals.as<VT>(),
-                   B->vals.as<VT>(), rmask.as<uint16_t>(), roff.as<int>(), rid.as<int>(), R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(),
+    const TileSide sa = tile_side(A), sb = tile_side(B);
+    CandidateStages st;
+    st.emit = [&](uint64_t *keys) { cand(nullptr, coff.as<int>(), keys); };
+    st.count = [&](const uint64_t *keys, int *cnt, int *flag) {
+        PEM_LAUNCH(ctx, kr_count_kernel, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, sa, sb, (long long)R->rows, bits_tc,
+                   rmask.as<uint16_t>(), cnt, flag);
+    };
+    st.fill = [&](const uint64_t *keys, const int *roff, const int *rid, int *headx) {
+        PEM_LAUNCH(ctx, kr_fill_kernel<VT>, grid_for(16 * ncand, 256), 256, keys, (long long)ncand, sa, sb, bits_tc, op, A->vals.as<VT>(),
+                   B->vals.as<VT>(), rmask.as<uint16_t>(), roff, rid, R->tile_keys.as<long long>(), R->tile_nnz_ptr.as<int>(),
                    R->rowcolidx.as<uint8_t>(), headx, R->vals.as<VT>());
-    return derive_tiled(ctx, R, headx, bits_tr, bits_tc);
+    };
+    // (every (A entry, B entry) pair is exactly one entry of R)
+    return tiling_from_candidates(ctx, R, fn, ncand, true, A->nnz * B->nnz, "nnz(A) * nnz(B) =", st);
 }
 
 // everything the host knows, in 64 bits, before anything is launched or allocated
@@ -350,7 +261,7 @@ static pem_status kron_map(pem_ctx *ctx, pem_tiled *t, const pem_tiled *A, const
     const size_t nnz = (size_t)t->nnz, nt = (size_t)t->ntiles;
     PEM_TRY(t->derived.map.reserve(sizeof(int2) * (nnz + 1)));
     PEM_LAUNCH(ctx, kr_map_kernel, grid_for((nt + 63) / 64 * 64, 256), 256, t->tile_keys.as<long long>(), (long long)nt, t->tile_nnz_ptr.as<int>(),
-               t->rowcolidx.as<uint8_t>(), side_of(A), side_of(B), t->derived.map.as<int2>());
+               t->rowcolidx.as<uint8_t>(), tile_side(A), tile_side(B), t->derived.map.as<int2>());
     return PEM_OK;
 }
 

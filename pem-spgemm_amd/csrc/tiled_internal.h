@@ -4,11 +4,16 @@
 // provenance is pem_tiled::derived (pem_internal.h), and refresh_derived runs its pem_tiled_set_values_from_*.  build.hip shares the
 // HEAD of pem_tiled_from_coo* (coo_sort_keys, then the radix sort) and this tail; its payload kernel is its own, because it compacts the
 // sorted positions to entries where convert.hip's conv_fill_kernel writes one value per position.
+// extract.hip, kron.hip and concat.hip build their result from a list of candidate result tiles: that route is written once, on the
+// host (check_candidates, tiling_from_candidates) and on the device (cand_key, cand_count, cand_slots, cand_tile_head, write_row_bits); chain.hip's
+// scatter uses the device half.  The refresh-map kernels of these units and of assign.hip are for_tile_entries around their own body.
 #pragma once
 #include "pem_internal.h"
 #include <chrono>
+#include <climits>
 #include <functional>
 #include <memory>
+#include <type_traits>
 
 namespace pem {
 
@@ -60,6 +65,26 @@ pem_status drop_region(pem_ctx *ctx, const pem_tiled *C, const uint16_t *rowbits
 // The caller sets R's provenance.  Synchronises.
 pem_status select_by_masks(pem_ctx *ctx, const pem_tiled *A, pem_tiled *R, const char *fn,
                            const std::function<void(uint32_t *nm, int *roff, int *rid)> &masks);
+// ---- the candidate-tile route (extract.hip; kron.hip, concat.hip): a result built from a list of candidate tiles, 16 lanes each ----
+// The read-back after the scan of the candidate counts, whose totals are in ctx->d_scalars[0 .. ntot): the totals into tot, the
+// flags (two synchronisations), the unit's own refusal where it has one to make first (refuse(flags): extract's FLAG_RANGE), then
+// "<fn>: the result's tiles exceed the int32 index range" on FLAG_OVERFLOW or tot[0] > INT32_MAX, then check_internal.
+pem_status check_candidates(pem_ctx *ctx, int ntot, int64_t *tot, const char *fn, const std::function<pem_status(const int *flags)> &refuse = {});
+// The launches of a unit on the route: emit writes the ncand candidate keys (tile row << bits_tc) | tile column; count writes per
+// candidate its entries and a non-empty flag (a candidate equal to the one before it has none); fill, with the scanned counts
+// (roff) and flags (rid), ncand + 1 values each, writes the payload (cand_slots and write_row_bits below).
+struct CandidateStages {
+    std::function<void(uint64_t *keys)> emit;
+    std::function<void(const uint64_t *keys, int *cnt, int *flag)> count;
+    std::function<void(const uint64_t *keys, const int *roff, const int *rid, int *headx)> fill;
+};
+// Everything after ncand is known, on an R whose shape and provenance are set: the keys, their radix sort over R's tile-row and
+// tile-column bits (sort), the count, the pair scan and its read-back (check_result_entries; with expect_nnz >= 0 the total must be
+// that, or "<fn>: internal: the walk counted %lld entries, not <expect_what> %lld"), R's nnz and ntiles, the payload arrays, the
+// fill, derive_tiled.  No stage runs when ncand == 0.  Synchronises: the caller's own temporaries may go once this returns.
+pem_status tiling_from_candidates(pem_ctx *ctx, pem_tiled *R, const char *fn, size_t ncand, bool sort, int64_t expect_nnz, const char *expect_what,
+                                  const CandidateStages &stages);
+
 // R = op(A, B) over the union of the patterns, alpha = beta = 1: pem_tiled_ewise's build under the caller's name (ewise.hip).
 // R's provenance is ewise's; the caller may replace it.
 pem_status union_tiling(pem_ctx *ctx, const pem_tiled *A, const pem_tiled *B, int op, pem_tiled *R, const char *fn);
@@ -207,6 +232,126 @@ __device__ __forceinline__ int src_slot(const int off, const uint32_t rec, const
     return off + (int)(rec >> 16) + __popc(rec & ((1u << c) - 1u));
 }
 
+// one wave per chunk of 64 consecutive tiles of a tiling R, one entry per lane, the trip count wave-uniform: visit(e, p, q) for
+// every entry e of the chunk, (p, q) its row and column in R (long long) from the tile's key and the entry's (r << 4) | c byte.
+// The whole body of a refresh-map kernel (extract.hip, assign.hip, kron.hip, concat.hip) but the statement that makes the map word.
+template <typename Visit>
+__device__ __forceinline__ void for_tile_entries(const long long *__restrict__ r_keys, const long long nt, const int *__restrict__ r_ptr,
+                                                 const uint8_t *__restrict__ r_rci, Visit visit)
+{
+    const int lane = threadIdx.x & 63;
+    const long long t0 = (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6;
+    if (t0 >= nt) return;   // (wave-uniform)
+    const int ntl = nt - t0 < 64 ? (int)(nt - t0) : 64;
+    const bool live = lane < ntl;
+    const long long o = t0 + (live ? lane : 0);
+    const int my_off = live ? r_ptr[o] : INT_MAX;
+    const int e_end = r_ptr[t0 + ntl];
+    const long long key = r_keys[o];
+    const int my_tr = (int)(key >> 32), my_tc = (int)(key & 0xFFFFFFFFll);
+    const int e_begin = __shfl(my_off, 0, 64);
+    for (int ebase = e_begin; ebase < e_end; ebase += 64) {   // wave-uniform trip count
+        const int e = ebase + lane;
+        const int ti = chunk_tile_of(my_off, e);
+        const long long tr = __shfl(my_tr, ti, 64), tc = __shfl(my_tc, ti, 64);
+        if (e >= e_end) continue;
+        const unsigned rc = r_rci[e];
+        visit(e, 16 * tr + (rc >> 4), 16 * tc + (rc & 15u));
+    }
+}
+
+// ---- device: 16 lanes per candidate result tile, lane = local row r (extract.hip, kron.hip, concat.hip; chain.hip's scatter) ----
+// candidate c's tile row and tile column from its key (P << bits_tc) | Q; dup: it equals the key before it (the keys are sorted),
+// so it is a duplicate and no tile of its own
+struct CandKey {
+    long long P, Q;
+    bool dup;
+};
+__device__ __forceinline__ CandKey cand_key(const uint64_t *__restrict__ keys, const long long c, const int bits_tc)
+{
+    const uint64_t key = keys[c];
+    return CandKey{(long long)(key >> bits_tc), (long long)(key & ((1ull << bits_tc) - 1ull)), c > 0 && keys[c - 1] == key};
+}
+
+// the end of a count kernel: n = the entries of the lane's row (0 past ncand); cnt[c] = the 16-lane sum, flag[c] = it is not 0.
+// Every lane of the group must get here.
+__device__ __forceinline__ void cand_count(int n, const long long c, const long long ncand, const int r, int *__restrict__ cnt,
+                                           int *__restrict__ flag)
+{
+#pragma unroll
+    for (int d = 8; d > 0; d >>= 1) n += __shfl_xor(n, d, 16);
+    if (c < ncand && r == 0) {
+        cnt[c] = n;
+        flag[c] = n != 0;
+    }
+}
+
+// the body of a fill kernel: n = the entries of the lane's row (0 past ncand), roff / rid = the scanned counts / flags (ncand + 1
+// values each: roff[ncand] = the result's entries, rid[ncand] = its tiles).  Where the candidate is a tile of the result, every
+// lane runs fill(s): [s.e0, s.e1) the tile's entries, s.t its id, s.e the row's first slot.  It comes last in the kernel (the
+// lanes of a candidate that is no tile have returned, as in a kernel written out), and every lane of the group must get here.
+// Nothing of the candidate's key is read: fill decodes it and hands it to cand_tile_head.
+struct CandSlots {
+    int e, e0, e1, t;
+};
+template <typename Fill>
+__device__ __forceinline__ void cand_slots(const long long c, const long long ncand, const int r, const int n, const int *__restrict__ roff,
+                                           const int *__restrict__ rid, int *__restrict__ tile_nnz_ptr, int *__restrict__ headx, Fill fill)
+{
+    int inc = n;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+        const int v = __shfl_up(inc, d, 16);
+        if (r >= d) inc += v;
+    }
+    if (c == 0 && r == 0) {   // closing offsets: tile_nnz_ptr[T] = nnz, headx[nnz] = T
+        const int nt = rid[ncand], nnz = roff[ncand];
+        tile_nnz_ptr[nt] = nnz;
+        headx[nnz] = nt;
+    }
+    if (c >= ncand) return;
+    const int e0 = roff[c], e1 = roff[c + 1];
+    if (e1 == e0) return;
+    fill(CandSlots{e0 + (inc - n), e0, e1, rid[c]});
+}
+// what lane 0 writes of tile s.t: its key from its tile row and tile column, and its first entry
+__device__ __forceinline__ void cand_tile_head(const int r, const CandSlots &s, const long long P, const long long Q,
+                                               long long *__restrict__ tile_keys, int *__restrict__ tile_nnz_ptr)
+{
+    if (r == 0) {
+        tile_keys[s.t] = (P << 32) | Q;
+        tile_nnz_ptr[s.t] = s.e0;
+    }
+}
+
+// the entries of `bits` (bit b = column place + b of row r of tile `tile`, whose entries are [e0, e_end)) into the payload from slot
+// e on: the (r << 4) | c byte, the tile-head scan written directly (tile at the tile's first entry, tile + 1 after it) and the
+// value val(b), unless val returns void; returns the slot after them.  val is called once for every bit that is written, in
+// ascending order of b, and for no other: a callable may step through a source run (extract.hip).
+template <typename VT, typename Val>
+__device__ __forceinline__ int write_row_bits(unsigned bits, const unsigned place, const int r, int e, const int e0, const int e_end,
+                                              const int tile, uint8_t *__restrict__ rowcolidx, int *__restrict__ headx, VT *__restrict__ vals,
+                                              Val val)
+{
+    while (bits) {
+        const unsigned b = (unsigned)__builtin_ctz(bits);
+        bits &= bits - 1u;
+        if (e < e_end) {   // (the masks and the offsets come from the same counts; never write past the tile)
+            rowcolidx[e] = (uint8_t)((r << 4) | (int)(place + b));
+            headx[e] = e == e0 ? tile : tile + 1;
+            if constexpr (!std::is_void<decltype(val(b))>::value) vals[e] = val(b);
+        }
+        ++e;
+    }
+    return e;
+}
+// rows that carry no values (chain.hip): nothing but the bytes and the tile-head scan is written
+__device__ __forceinline__ int write_row_bits(const unsigned bits, const unsigned place, const int r, const int e, const int e0, const int e_end,
+                                              const int tile, uint8_t *__restrict__ rowcolidx, int *__restrict__ headx)
+{
+    return write_row_bits(bits, place, r, e, e0, e_end, tile, rowcolidx, headx, (char *)nullptr, [](unsigned) {});
+}
+
 // ---- device: a row of a tiling read as masks, 32 columns at a time (kron.hip, concat.hip) ----
 // what such a walk reads of a tiling
 struct TileSide {
@@ -215,6 +360,10 @@ struct TileSide {
     const uint32_t *rec;          // tile_rec: row mask | entries of the rows above << 16
     int rows, cols;
 };
+inline TileSide tile_side(const pem_tiled *T)
+{
+    return TileSide{T->tile_rowptr.as<int>(), T->tile_colidx.as<int>(), T->tile_nnz_ptr.as<int>(), T->tile_rec.as<uint32_t>(), T->rows, T->cols};
+}
 
 // the 32 columns of row `row` of a tiling that start at tile column tc: the row's masks there (bit b = column 16 tc + b) and, for
 // the value slots, the two tiles' tile_rec words and first entries
