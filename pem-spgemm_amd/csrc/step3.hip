@@ -106,6 +106,106 @@ template <bool IDX32> __device__ __forceinline__ void s3_glds(const uint32_t *__
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, (__attribute__((address_space(3))) void *)strip_row, 4, 0, 0);
 }
 
+// The shallow kernel's two-pair block: pairs (a0, b0) and (a1, b1) of one entry (row r, column c), value offsets av* / bv*.
+// The four record gathers go out together, then the first product of either pair together (two round trips for the block, not
+// four); `between` runs while they are in flight and the values are pinned behind it; the sums run pair by pair, product by
+// product, in ascending order.  A lane without the first (second) pair issues nothing for it.
+// PEM_S3_PAIR_BLOCK: the staged third and later pairs run this block too, two pairs per round of the loop (0: one pair per
+// round, records then values).  PEM_S3_SECOND_EARLY: where the first pair meets in two or more products, the second product's
+// operands are gathered beside the first's (EARLY; four more registers on fp64), so the product loop starts at the third.
+// Measured together and apart (profiles/r06_s3_pair_block.txt): the pass 0.623 -> 0.609 ms with both, 0.617 with either alone
+// (inside twice the parent's spread): both are on, and neither is worth keeping without the other.
+#ifndef PEM_S3_PAIR_BLOCK
+#define PEM_S3_PAIR_BLOCK 1
+#endif
+#ifndef PEM_S3_SECOND_EARLY
+#define PEM_S3_SECOND_EARLY 1
+#endif
+template <typename VT, bool IDX32, typename SR, bool EARLY, typename F>
+__device__ __forceinline__ VT s3_pair_block(VT acc, const bool has_first, const bool has_second, const int a0, const int b0, const int av0,
+                                            const int bv0, const int a1, const int b1, const int av1, const int bv1, const int r, const int c,
+                                            const VT *__restrict__ a_vals, const uint32_t *__restrict__ a_rec,
+                                            const VT *__restrict__ b_vals_t, const uint32_t *__restrict__ b_rec_t, F &&between)
+{
+    unsigned aw = 0, bw = 0;
+    if (has_first) {
+        aw = s3_ld<IDX32>(a_rec, 16ll * a0 + r);
+        bw = s3_ld<IDX32>(b_rec_t, 16ll * b0 + c);
+    }
+    unsigned aw1 = 0, bw1 = 0;
+    if (has_second) {
+        aw1 = s3_ld<IDX32>(a_rec, 16ll * a1 + r);
+        bw1 = s3_ld<IDX32>(b_rec_t, 16ll * b1 + c);
+    }
+    const unsigned am = aw & 0xFFFFu, bm = bw & 0xFFFFu, am1 = aw1 & 0xFFFFu, bm1 = bw1 & 0xFFFFu;
+    unsigned m = am & bm, m1 = am1 & bm1;
+    const int ao = av0 + (int)(aw >> 16), bo = bv0 + (int)(bw >> 16), ao1 = av1 + (int)(aw1 >> 16), bo1 = bv1 + (int)(bw1 >> 16);
+    VT x0 = VT(0), y0 = VT(0), x1 = VT(0), y1 = VT(0), x0s = VT(0), y0s = VT(0);
+    if (SR::vals && m) {
+        const unsigned below = (1u << __builtin_ctz(m)) - 1u;
+        x0 = s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below));
+        y0 = s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below));
+        if constexpr (EARLY) {
+            const unsigned ms = m & (m - 1);
+            if (ms) {
+                const unsigned belows = (1u << __builtin_ctz(ms)) - 1u;
+                x0s = s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & belows));
+                y0s = s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & belows));
+            }
+        }
+    }
+    if (SR::vals && m1) {
+        const unsigned below = (1u << __builtin_ctz(m1)) - 1u;
+        x1 = s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below));
+        y1 = s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below));
+    }
+    between();
+    // Both pairs' first products (and whatever `between` issued) are in flight before either is used.  Without this the compiler
+    // moves the first fma -- acc may still be the start value, a constant -- up into pair 1's `if (m)` and waits for its operands
+    // there, in front of pair 2's gathers: three round trips for an entry with two pairs, not two.
+    if constexpr (SR::vals) {
+        s3_pin(x0);
+        s3_pin(y0);
+        if constexpr (EARLY) {
+            s3_pin(x0s);
+            s3_pin(y0s);
+        }
+        s3_pin(x1);
+        s3_pin(y1);
+    }
+    if constexpr (!SR::vals) {
+        acc = SR::template count<VT>(m1, SR::template count<VT>(m, acc));
+    } else {
+        if (m) {
+            acc = SR::template combine<VT>(x0, y0, acc);
+            m &= m - 1;
+            if constexpr (EARLY) {
+                if (m) {
+                    acc = SR::template combine<VT>(x0s, y0s, acc);
+                    m &= m - 1;
+                }
+            }
+            while (m) {
+                const int kk = __builtin_ctz(m);
+                m &= m - 1;
+                const unsigned below = (1u << kk) - 1u;
+                acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
+            }
+        }
+        if (m1) {
+            acc = SR::template combine<VT>(x1, y1, acc);
+            m1 &= m1 - 1;
+            while (m1) {
+                const int kk = __builtin_ctz(m1);
+                m1 &= m1 - 1;
+                const unsigned below = (1u << kk) - 1u;
+                acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below)), s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below)), acc);
+            }
+        }
+    }
+    return acc;
+}
+
 template <typename VT, bool DEEP, bool BAND = false, bool DECODE = false, bool IDX32 = false, bool MARK = false, typename SR = SrPlusTimes, bool BATCH = false>
 #ifndef PEM_S3_DEEP_WAVES
 #define PEM_S3_DEEP_WAVES 1   // (8 = at most 64 VGPRs for the deep variants too: 6 of them spill and a cage15 share's step 3 is 6.83 against 6.74 ms)
@@ -268,7 +368,7 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
             // records go out beside the first pair's, and the first product of either pair is gathered before anything is summed:
             // two round trips for an entry with two pairs instead of four.  The sums still run pair by pair, bit by bit.
             const bool has1 = p0 < p1, has2 = p0 + 1 < p1;
-            // the third and later pairs of the trip's tiles (64 % of webbase-1M's entries lie in tiles with three to eight pairs): the
+            // the third and later pairs of the trip's tiles (19 % of webbase-1M's entries lie in tiles with three to eight pairs): the
             // pairs of consecutive tiles are consecutive, so the wave fetches the trip's whole pair range ONCE, one pair per lane --
             // ids, then value offsets -- and a lane reads the record of ITS q-th pair by shuffle.  Before: every lane gathered ids,
             // offsets and records per pair (six wave-wide vector-memory instructions and four dependent round trips per pair; the
@@ -281,33 +381,12 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                 sa = s3_ld<IDX32>(pairs_a, (long long)P0 + lane);
                 sb = s3_ld<IDX32>(pairs_b, (long long)P0 + lane);
             }
-            unsigned aw = 0, bw = 0;
-            if (has1) {
-                aw = s3_ld<IDX32>(a_rec, 16ll * a0 + r);
-                bw = s3_ld<IDX32>(b_rec_t, 16ll * b0 + c);
-            }
-            unsigned aw1 = 0, bw1 = 0;
-            if (has2) {
-                aw1 = s3_ld<IDX32>(a_rec, 16ll * a1 + r);
-                bw1 = s3_ld<IDX32>(b_rec_t, 16ll * b1 + c);
-            }
-            const unsigned am = aw & 0xFFFFu, bm = bw & 0xFFFFu, am1 = aw1 & 0xFFFFu, bm1 = bw1 & 0xFFFFu;
-            unsigned m = am & bm, m1 = am1 & bm1;
-            const int ao = av0 + (int)(aw >> 16), bo = bv0 + (int)(bw >> 16), ao1 = av1 + (int)(aw1 >> 16), bo1 = bv1 + (int)(bw1 >> 16);
-            VT x0 = VT(0), y0 = VT(0), x1 = VT(0), y1 = VT(0);
-            if (SR::vals && m) {
-                const unsigned below = (1u << __builtin_ctz(m)) - 1u;
-                x0 = s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below));
-                y0 = s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below));
-            }
-            if (SR::vals && m1) {
-                const unsigned below = (1u << __builtin_ctz(m1)) - 1u;
-                x1 = s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below));
-                y1 = s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below));
-            }
             // (the batched 64-bit forms on fp64 values have no registers left beside the four first products: their first batch and
             // their value offsets go out after pairs 1 and 2 are summed, a round trip later)
             constexpr bool BATCH_EARLY = IDX32 || sizeof(VT) == 4;
+            // (nor do the plain 64-bit forms on fp64 values, at 64 registers already: with the later pairs in two-pair blocks or a second
+            // product gathered early they spill 8-24 bytes -- they keep one pair per round and one product per round trip)
+            constexpr bool ROOM = IDX32 || sizeof(VT) == 4;
             // the staged value offsets travel with the values of pairs 1 and 2 (the third pair is their first reader): in front of
             // them, the wait for the records would wait for these too -- the loads return in order -- and cost a round trip
             auto load_offsets = [&]() {
@@ -316,7 +395,6 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                     sbv = s3_ld<IDX32>(b_nnz_ptr, sb);
                 }
             };
-            if constexpr (!BATCH || BATCH_EARLY) load_offsets();
             // the records of pairs qb .. qb + S3_BATCH_R - 1 of every lane, into the strip (rounds no lane needs are left out: the
             // `on` lanes of a round are a superset of the next round's)
             auto issue_batch = [&](const int qb) {
@@ -330,42 +408,13 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                     s3_glds<IDX32>(b_rec_t, 16ll * b + c, my_strip + (2 * j + 1) * 64);
                 }
             };
-            // the first batch goes out behind the value gathers of pairs 1 and 2, before they are used: one round trip for all of them
-            if constexpr (BATCH && BATCH_EARLY)
-                if (staged) issue_batch(2);
-            // Both pairs' first products (and the batch) are in flight before either is used.  Without this the compiler moves the
-            // first fma -- acc is still the start value, a constant -- up into pair 1's `if (m)` and waits for its operands there,
-            // in front of pair 2's gathers: three round trips for an entry with two pairs, not two.
-            if constexpr (SR::vals) {
-                s3_pin(x0);
-                s3_pin(y0);
-                s3_pin(x1);
-                s3_pin(y1);
-            }
-            if constexpr (!SR::vals) {
-                acc = SR::template count<VT>(m1, SR::template count<VT>(m, acc));
-            } else {
-                if (m) {
-                    acc = SR::template combine<VT>(x0, y0, acc);
-                    m &= m - 1;
-                    while (m) {
-                        const int kk = __builtin_ctz(m);
-                        m &= m - 1;
-                        const unsigned below = (1u << kk) - 1u;
-                        acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao + __popc(am & below)), s3_ld<IDX32>(b_vals_t, (long long)bo + __popc(bm & below)), acc);
-                    }
-                }
-                if (m1) {
-                    acc = SR::template combine<VT>(x1, y1, acc);
-                    m1 &= m1 - 1;
-                    while (m1) {
-                        const int kk = __builtin_ctz(m1);
-                        m1 &= m1 - 1;
-                        const unsigned below = (1u << kk) - 1u;
-                        acc = SR::template combine<VT>(s3_ld<IDX32>(a_vals, (long long)ao1 + __popc(am1 & below)), s3_ld<IDX32>(b_vals_t, (long long)bo1 + __popc(bm1 & below)), acc);
-                    }
-                }
-            }
+            // the first block: pairs 1 and 2 from the per-tile registers.  The staged offsets -- and the first batch, behind the value
+            // gathers of pairs 1 and 2 and before they are used: one round trip for all of them -- go out inside it.
+            acc = s3_pair_block<VT, IDX32, SR, PEM_S3_SECOND_EARLY && ROOM && !BATCH>(acc, has1, has2, a0, b0, av0, bv0, a1, b1, av1, bv1, r, c, a_vals, a_rec, b_vals_t, b_rec_t, [&]() {
+                if constexpr (!BATCH || BATCH_EARLY) load_offsets();
+                if constexpr (BATCH && BATCH_EARLY)
+                    if (staged) issue_batch(2);
+            });
             p += has2 ? 2 : has1 ? 1 : 0;
             if constexpr (BATCH && !BATCH_EARLY) load_offsets();
             if (BATCH && staged) {
@@ -404,6 +453,23 @@ __global__ void __launch_bounds__(256, DEEP ? PEM_S3_DEEP_WAVES : 8) s3_accumula
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
+                }
+                p = p1;
+            } else if (PEM_S3_PAIR_BLOCK && ROOM && staged) {
+                // later blocks: pairs q and q + 1 of every lane's tile from the staged ids and offsets, by shuffle, through the
+                // same block -- two round trips for two pairs where one pair per round pays two each.  A lane whose tile has an
+                // odd number of later pairs runs its last block without a second pair; nothing is fetched ahead.
+                for (int q = 2;; q += 2) {
+                    const bool on = p0 + q < p1, on2 = p0 + q + 1 < p1;
+                    if (__ballot(on) == 0ull) break;                            // wave-uniform
+                    const int src = on ? p0 + q - P0 : 0;
+                    const int a = __shfl(sa, src, 64), b = __shfl(sb, src, 64), av = __shfl(sav, src, 64), bv = __shfl(sbv, src, 64);
+                    int a2 = 0, b2 = 0, av2 = 0, bv2 = 0;
+                    if (__ballot(on2) != 0ull) {                                // wave-uniform (on2 lanes: src + 1 < Pn <= 64)
+                        const int src2 = on2 ? src + 1 : 0;
+                        a2 = __shfl(sa, src2, 64), b2 = __shfl(sb, src2, 64), av2 = __shfl(sav, src2, 64), bv2 = __shfl(sbv, src2, 64);
+                    }
+                    acc = s3_pair_block<VT, IDX32, SR, false>(acc, on, on2, a, b, av, bv, a2, b2, av2, bv2, r, c, a_vals, a_rec, b_vals_t, b_rec_t, []() {});
                 }
                 p = p1;
             } else if (staged) {
